@@ -6,7 +6,13 @@ step (CIC paint -> R2C -> k-space -> 3 C2R -> fused read+kick+drift) plus its ha
 N = n^3 particles on an n^3 mesh, synthetic inputs of SURVEY.md 8(d).  The timed region runs K forward steps
 (writing checkpoints) followed by their K adjoint steps, with every input resident in HBM.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--mesh n]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--mesh n] [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints one JSON line (`metric`, `value`, `unit`, `ms_per_step`, ...).
+`--full` adds everything else the line used to carry: the per-stage profile pass (`stages`, `roofline`, `fwd_adj_step`),
+`force_cycle` with pm_forces timed on its own, the 256^3 / 128^3 / 64^3 sub-records and CPU baselines, the slab checks and,
+for N > 1, the `interleaved_chains` record.  `--dump-outputs DIR` writes what the timed path handed back after its last step
+as DIR/<name>.npy (dump_outputs below).
 
 N > 1 runs one rank per GPU (RCCL): the SAME mesh is x-slab decomposed over the ranks (montecosmo_amd/dist.py: ghost
 planes point-to-point, one all-to-all per FFT transpose), so the total work is fixed and scaling is "strong".  The ranks
@@ -43,8 +49,12 @@ def parse():
     ap.add_argument("--n-steps", type=int, default=10, help="BullFrog steps of the simulated a0 -> a1 run (the workload; memory ~ n-steps)")
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--mesh", type=int, default=int(os.environ.get("MCPM_BENCH_MESH", "512")))
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-sub-record", action="store_true", help="skip the second (--cpu-mesh) GPU record and the CPU baseline on it: "
+    ap.add_argument("--full", action="store_true", help="also the secondary measurements and checks (profile pass, roofline, pm_forces, "
+                    "sub-records, CPU baselines, slab checks, interleaved chains for N > 1); off: time the K steps only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what their last step computed "
+                    "(final state, cotangents; a seeded sample of rows when large) as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baselines")
+    ap.add_argument("--no-sub-record", action="store_true", help="--full: skip the second (--cpu-mesh) GPU record and the CPU baseline on it: "
                     "profiler passes want one mesh size per run, kernel names do not carry it")
     ap.add_argument("--replicas", action="store_true", help="N > 1: independent replicas instead of slabs")
     ap.add_argument("--force-slab", action="store_true", help="N = 1: run the slab code path with a local-copy communicator "
@@ -53,7 +63,7 @@ def parse():
     ap.add_argument("--ghost", type=int, default=8)
     ap.add_argument("--chains", type=int, default=0, help="slab path: ALSO time this many independent trajectories issued alternately "
                     "on their own streams / process groups (extra `interleaved_chains` record; `value` stays the single trajectory). "
-                    "0 = 2 when N > 1, else off")
+                    "0 = 2 when N > 1 under --full, else off")
     ap.add_argument("--fixed-ghost", action="store_true", help="slabs: always exchange all ghost planes (default: only the "
                     "planes each step's displacements can reach)")
     ap.add_argument("--cpu-mesh", type=int, default=256, help="mesh of the second GPU record and of the CPU baseline (unscaled)")
@@ -226,6 +236,8 @@ class Runner:
 
 class SlabRunner:
     """The same K forward + K adjoint steps on an x-slab of the mesh (one rank of N)."""
+
+    forward_only = False
 
     def __init__(self, n, K, device, ghost, adaptive_ghost=True, seed=0, group=None):
         """Everything (plan, buffers, kernels, collectives) lives on the torch stream that is current at construction
@@ -464,6 +476,35 @@ def sub_record(n, NS, K, W, device):
                "fwd_adj_step_frac_of_hbm_peak": round(B_PER_CELL_STEP * M / (dt / K) / 1e9 / HBM_PEAK_GBS, 4)}
 
 
+DUMP_ROWS = 1 << 19          # particle rows kept per (N, 3) array by --dump-outputs: 6 MB each, under 32 MB in all
+DUMP_SEED = 20261016         # fixed: the same rows in every run, so that two builds compare output for output
+
+
+def dump_outputs(r, K, out_dir):
+    """--dump-outputs: what the timed path handed back after its last step, written right after the timed region (before
+    anything else reuses the buffers).  The timed K steps replay the r.K-step simulation in blocks; of the last block (s steps)
+    the files hold the final state (x'_s, v_s) and, unless forward only, the cotangents of the loss <pos_bar, x'_s> +
+    <vel_bar, v_s> with respect to the start state (x'_0, v_0), float32, plus the scalar cotangents (float64; the library adds
+    into them, so they are summed over every block since set-up, warm-up included).  With more than DUMP_ROWS particles the
+    (N, 3) arrays keep a seeded sample of rows, whose particle indices are `row_index` (float64, exact).  Slab runs: the
+    calling rank's particles."""
+    os.makedirs(out_dir, exist_ok=True)
+    s = (K - 1) % r.K + 1
+    arrays = {"final_disp": r.states[s, 0], "final_vel": r.states[s, 1]}
+    if not r.forward_only:
+        arrays.update(pos_cotangent=r.xb, vel_cotangent=r.vb)
+    N = arrays["final_disp"].shape[0]
+    if N > DUMP_ROWS:
+        idx = np.sort(np.random.default_rng(DUMP_SEED).choice(N, DUMP_ROWS, replace=False))
+        np.save(os.path.join(out_dir, "row_index.npy"), idx.astype(np.float64))
+        sel = torch.from_numpy(idx).to(arrays["final_disp"].device)
+        arrays = {k: a.index_select(0, sel) for k, a in arrays.items()}
+    for k, a in arrays.items():
+        np.save(os.path.join(out_dir, k + ".npy"), a.float().cpu().numpy())
+    if not r.forward_only:
+        np.save(os.path.join(out_dir, "scalar_cotangents.npy"), r.sbar.double().cpu().numpy())
+
+
 def spawn_ranks(nproc):
     """`python bench.py --gpus N` without a launcher: start N fresh rank processes (this process has not touched the GPU
     and never will), one per GPU, rendezvous on 127.0.0.1, and relay their output.  Returns the worst exit code."""
@@ -577,13 +618,28 @@ def main():
         t = torch.tensor([dt], dtype=torch.float64, device=device if td.get_backend() == "nccl" else "cpu")
         td.all_reduce(t, op=td.ReduceOp.MAX)
         dt = float(t.item())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(r, K, args.dump_outputs)
 
     out = None
-    prof = r.profile() if (slab or rank == 0) else None     # slabbed: collective, every rank takes part
-    pmf_ms = r.force_cycle_ms() if (rank == 0 and not slab) else None
+    full = args.full
+    prof = r.profile() if full and (slab or rank == 0) else None     # slabbed: collective, every rank takes part
+    pmf_ms = r.force_cycle_ms() if (full and rank == 0 and not slab) else None
     if rank == 0:
         M = float(n) ** 3          # whole mesh: stage times below are rank 0's, which holds 1/world of it when slabbed
         steps_per_s = (1 if slab else world) * K / dt
+        out = {
+            "metric": "PM forward steps/sec" if args.forward_only else "PM forward+adjoint steps/sec", "value": round(steps_per_s, 3), "unit": "steps/s",
+            "n_gpus": world, "rccl_world": (td.get_world_size() if dist else 1), "comm_backend": (td.get_backend() if dist else None),
+            "steps": K, "warmup": W, "ms_per_step": round(dt / K * 1e3, 3),
+            "higher_is_better": True, "scaling": "weak" if args.replicas else "strong", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+            "config": {"workload": f"{n}^3 mesh, {n}^3 particles, {NS}-step BullFrog {'forward only' if args.forward_only else 'forward+VJP'}, CIC, 2LPT start (untimed), "
+                                   f"rms displacement 2 cells; " + ("single GPU" if world == 1 else
+                                                                    (f"x-slab decomposed over {world} GPUs (ghost {args.ghost} planes, RCCL all-to-all FFT transpose)"
+                                                                     if slab else f"{world} independent replicas")),
+                       "mesh": n, "n_steps": NS, "parallelism": (("slab1 (RCCL, one rank)" if dist else "slab1 (local-copy communicator)") if slab else "single") if world == 1 else (f"slab{world}" if slab else f"replicas{world}")},
+        }
+    if rank == 0 and full:
         names, fwd, bwd = prof
         stages = {}
         for i, nm in enumerate(names):
@@ -601,16 +657,7 @@ def main():
         cyc_ms = sum(fwd[0][names.index(k)] for k in ("paint", "fft_r2c", "kspace", "fft_c2r", "kick_drift")) / NS   # the profile pass runs the NS-step block once
         step_ms = (fwd_ms + bwd_ms) / NS
         step_b = B_PER_CELL_FWD if args.forward_only else B_PER_CELL_STEP
-        out = {
-            "metric": "PM forward steps/sec" if args.forward_only else "PM forward+adjoint steps/sec", "value": round(steps_per_s, 3), "unit": "steps/s",
-            "n_gpus": world, "rccl_world": (td.get_world_size() if dist else 1), "comm_backend": (td.get_backend() if dist else None),
-            "steps": K, "warmup": W, "ms_per_step": round(dt / K * 1e3, 3),
-            "higher_is_better": True, "scaling": "weak" if args.replicas else "strong", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
-            "config": {"workload": f"{n}^3 mesh, {n}^3 particles, {NS}-step BullFrog {'forward only' if args.forward_only else 'forward+VJP'}, CIC, 2LPT start (untimed), "
-                                   f"rms displacement 2 cells; " + ("single GPU" if world == 1 else
-                                                                    (f"x-slab decomposed over {world} GPUs (ghost {args.ghost} planes, RCCL all-to-all FFT transpose)"
-                                                                     if slab else f"{world} independent replicas")),
-                       "mesh": n, "n_steps": NS, "parallelism": (("slab1 (RCCL, one rank)" if dist else "slab1 (local-copy communicator)") if slab else "single") if world == 1 else (f"slab{world}" if slab else f"replicas{world}")},
+        out.update({
             "roofline": {"bound": "hbm", "kernel": dom, "achieved": stages[dom]["algorithmic_GBps"], "peak": HBM_PEAK_GBS,
                          "unit": "GB/s", "frac": round(stages[dom]["algorithmic_GBps"] / HBM_PEAK_GBS, 4),
                          "traffic": pmc_traffic(dom, n)[0] if world == 1 else None,
@@ -625,23 +672,24 @@ def main():
                 "algorithmic_GBps": round(step_b * Mloc / (step_ms * 1e-3) / 1e9, 1),
                 "frac_of_hbm_peak": round(step_b * Mloc / (step_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4)},
             "stages": stages,
-        }
+        })
         if pmf_ms is not None:
             out["force_cycle"].update({"pm_forces_ms": round(pmf_ms, 4),
                                        "pm_forces_GBps": round(B_PER_CELL_CYCLE * M / (pmf_ms * 1e-3) / 1e9, 1),
                                        "pm_forces_frac_of_hbm_peak": round(B_PER_CELL_CYCLE * M / (pmf_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4)})
-        if True:
-            out["layout"] = dict(r.layout, note="particle arrays in one flat buffer, array j at j * pitch_floats; the pitch is chosen by the library "
-                                             "(mcpm_plan_probe_particle_pitch: adjoint particle kernel timed on this buffer for 3 candidate pitches, untimed set-up)")
+    if rank == 0:
+        out["layout"] = dict(r.layout, note="particle arrays in one flat buffer, array j at j * pitch_floats; the pitch is chosen by the library "
+                                         "(mcpm_plan_probe_particle_pitch: adjoint particle kernel timed on this buffer for 3 candidate pitches, untimed set-up)")
         if slab:
-            out["comm_and_host_ms_per_step"] = round(dt / K * 1e3 - step_ms, 3)   # wall minus rank-0 kernel stages
-            out["deposits_beyond_ghost_rank0"] = r.pm.out_of_ghost()                # must be 0
+            if full:
+                out["comm_and_host_ms_per_step"] = round(dt / K * 1e3 - step_ms, 3)   # wall minus rank-0 kernel stages
+                out["deposits_beyond_ghost_rank0"] = r.pm.out_of_ghost()                # must be 0
             out["ghost_planes_exchanged_per_step"] = [int(d) for d in r.depths if d is not None]   # of --ghost allocated
             pm = r.pm       # who issues the exchanges: the library (csrc/slab.hip) unless its transport failed its self-test
             out["slab_transport"] = (("library, local copies" if world == 1 and not dist else "library, plan-owned RCCL communicator (self-test passed)")
                                      if pm.native else f"torch.distributed ({pm.native_fallback or 'MCPM_SLAB_NATIVE=0'})")
             out["a2a_chunks"] = r.pm.chunks      # all-to-alls per transposed spectrum (dist.SlabPM chunks; MCPM_SLAB_CHUNKS)
-        if world == 1 and not slab and not args.forward_only and not args.no_sub_record:
+        if full and world == 1 and not slab and not args.forward_only and not args.no_sub_record:
             # the metric names 256^3 as well: a second, smaller record in the same line, and the CPU baseline on ITS trajectory
             if n != args.cpu_mesh:
                 r2, out[f"mesh_{args.cpu_mesh}"] = sub_record(args.cpu_mesh, NS, K, W, device)
@@ -662,7 +710,7 @@ def main():
     # ---- independent trajectories as a software pipeline (collective: every rank takes part).  Measured AFTER the line
     # above is complete, under a watchdog: whatever happens here (a second communicator that cannot be created, a hang), the
     # single-trajectory result is printed.
-    nch = args.chains if args.chains > 0 else (2 if (slab and world > 1) else 1)
+    nch = args.chains if args.chains > 0 else (2 if (full and slab and world > 1) else 1)
     if slab and nch > 1:
         import threading
 

@@ -60,9 +60,9 @@ def test_bench_gpus_launches_ranks_cpu(world):
 
 @pytest.mark.gpu
 def test_bench_gpus_2_gloo_shared_gpu(gpu):
-    """The whole `bench.py --gpus 2` line (slab-decomposed, strong scaling) with two ranks sharing cuda:0 over gloo: a
+    """The whole `bench.py --gpus 2 --full` line (slab-decomposed, strong scaling) with two ranks sharing cuda:0 over gloo: a
     rehearsal of the multi-GPU launch, never a measurement."""
-    r, line = _run_bench(["--gpus", "2", "--mesh", "64", "--steps", "3", "--warmup", "1", "--n-steps", "3", "--no-cpu-baseline"],
+    r, line = _run_bench(["--gpus", "2", "--mesh", "64", "--steps", "3", "--warmup", "1", "--n-steps", "3", "--no-cpu-baseline", "--full"],
                          env={"MCPM_BENCH_BACKEND": "gloo"})
     assert r.returncode == 0, r.stderr[-3000:]
     assert line["n_gpus"] == 2 and line["rccl_world"] == 2 and line["comm_backend"] == "gloo"

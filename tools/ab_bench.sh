@@ -8,7 +8,7 @@ mkdir -p gpurun_out/ab_$tag
 i=0
 for v in "${vals[@]}"; do
   f=gpurun_out/ab_$tag/${var}_${v}_$i.json
-  env $var=$v python bench.py --no-sub-record --no-cpu-baseline "$@" > $f 2> gpurun_out/ab_$tag/err_$i.log || { echo "bench failed"; tail -5 gpurun_out/ab_$tag/err_$i.log; exit 1; }
+  env $var=$v python bench.py --full --no-sub-record --no-cpu-baseline "$@" > $f 2> ${f%/*}/err_$i.log || { echo "bench failed"; tail -5 ${f%/*}/err_$i.log; exit 1; }
   python - "$f" "$var=$v" <<'PY'
 import json, sys
 d = json.loads([l for l in open(sys.argv[1]) if l.startswith("{")][-1])

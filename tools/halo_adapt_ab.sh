@@ -3,7 +3,7 @@
 OUT=${1:-gpurun_out/ha}; mkdir -p $OUT
 for n in ${MESHES:-512 256 128}; do for a in 0 1 0 1; do
   ST=50; [ $n = 512 ] && ST=20
-  MCPM_PAINT_ADAPT=$a timeout -k 10 300 python3 bench.py --mesh $n --steps $ST --warmup 5 --no-sub-record --no-cpu-baseline > $OUT/b_${n}_$a.json 2> $OUT/b_${n}_$a.err || exit 1
+  MCPM_PAINT_ADAPT=$a timeout -k 10 300 python3 bench.py --full --mesh $n --steps $ST --warmup 5 --no-sub-record --no-cpu-baseline > $OUT/b_${n}_$a.json 2> $OUT/b_${n}_$a.err || exit 1
   python3 - $OUT/b_${n}_$a.json $a <<'PY'
 import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])

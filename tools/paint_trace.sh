@@ -1,7 +1,7 @@
 #!/bin/bash
 # durations of the tiled-paint kernels, call by call, over one bench trajectory (rocprofv3 --kernel-trace)
 N=${1:-512}; O=${2:-gpurun_out/ptr}; mkdir -p $O; cd /tmp; export TMPDIR=/tmp; R=$GRAFT_REPO_ROOT
-timeout -k 10 300 rocprofv3 --kernel-trace --output-format csv -d $R/$O/tr -o t -- python3 $R/bench.py --mesh $N --steps 10 --warmup 0 --no-sub-record --no-cpu-baseline > $R/$O/run.log 2>&1 || exit 1
+timeout -k 10 300 rocprofv3 --kernel-trace --output-format csv -d $R/$O/tr -o t -- python3 $R/bench.py --full --mesh $N --steps 10 --warmup 0 --no-sub-record --no-cpu-baseline > $R/$O/run.log 2>&1 || exit 1
 python3 - $R/$O <<'PY'
 import csv, glob, sys
 f = glob.glob(sys.argv[1] + "/tr/**/*kernel_trace.csv", recursive=True)[0]

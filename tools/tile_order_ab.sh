@@ -3,7 +3,7 @@
 # stage times of the two tiled paints over the bench trajectory, alternating processes.   usage: tools/tile_order_ab.sh [mesh] [outdir]
 N=${1:-512}; OUT=${2:-gpurun_out/to}; mkdir -p $OUT
 for rep in ${REPS:-1 2}; do for o in ${ORDERS:-0 1}; do
-  MCPM_TILE_ORDER=$o timeout -k 10 300 python3 bench.py --mesh $N --steps 10 --warmup 3 --no-sub-record --no-cpu-baseline > $OUT/b_${N}_${o}_$rep.json 2> $OUT/b_${N}_${o}_$rep.err || exit 1
+  MCPM_TILE_ORDER=$o timeout -k 10 300 python3 bench.py --full --mesh $N --steps 10 --warmup 3 --no-sub-record --no-cpu-baseline > $OUT/b_${N}_${o}_$rep.json 2> $OUT/b_${N}_${o}_$rep.err || exit 1
   python3 - $OUT/b_${N}_${o}_$rep.json $o <<'PY'
 import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])
