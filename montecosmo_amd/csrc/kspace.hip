@@ -13,21 +13,40 @@
 
 #define TWO_PI 6.283185307179586f
 
+__device__ __forceinline__ int sfreq(int i, int n) { return (i < (n + 1) / 2) ? i : i - n; }  // n * fftfreq(n)[i]
 __device__ __forceinline__ float kfreq(int i, int n) {  // 2*pi*fftfreq(n)[i]
-    int s = (i < (n + 1) / 2) ? i : i - n;
-    return TWO_PI * (float)s / (float)n;
+    return TWO_PI * (float)sfreq(i, n) / (float)n;
+}
+// sin(pi t / n) with the argument reduced in integers to [-pi/2, pi/2]: sinf of a float k near +-pi loses the relative
+// accuracy of sin k (1.2e-5 next to the Nyquist mode of a 1024 axis), the reduced argument keeps it.
+__device__ __forceinline__ float sinpi_frac(int t, int n) {
+    t %= 2 * n;
+    if (t > n) t -= 2 * n;
+    if (t < -n) t += 2 * n;
+    if (2 * t > n) t = n - t;
+    if (2 * t < -n) t = -n - t;
+    return sinf(3.14159265358979f * (float)t / (float)n);
 }
 
+// The FD Laplacians of nbody.py:125-131, (cos k - 1) 2 and (cos 2k - 16 cos k + 15) / 6, in sine form: the cosine form
+// cancels at small k in float (5e-4 relative error at the fundamental mode of a 1024 axis, where 1/k^2 weighs most).
 template <int FD>
 __device__ __forceinline__ float lap_term(float k) {
-    if (FD == MCPM_FD_2) return (cosf(k) - 1.f) * 2.f;
-    if (FD == MCPM_FD_4) return (cosf(2.f * k) - 16.f * cosf(k) + 15.f) / 6.f;
+    if (FD == MCPM_FD_2) {
+        const float h = sinf(0.5f * k);
+        return -4.f * h * h;
+    }
+    if (FD == MCPM_FD_4) {
+        const float h = sinf(0.5f * k), s = sinf(k);
+        return (32.f * h * h - 2.f * s * s) / 6.f;
+    }
     return k * k;
 }
+// FD gradients of nbody.py:136-163 at k = 2 pi s / n: sin k and (8 sin k - sin 2k) / 6
 template <int FD>
-__device__ __forceinline__ float grad_term(float k) {
-    if (FD == MCPM_FD_2) return sinf(k);
-    if (FD == MCPM_FD_4) return (8.f * sinf(k) - sinf(2.f * k)) / 6.f;
+__device__ __forceinline__ float grad_term(float k, int s, int n) {
+    if (FD == MCPM_FD_2) return sinpi_frac(2 * s, n);
+    if (FD == MCPM_FD_4) return (8.f * sinpi_frac(2 * s, n) - sinpi_frac(4 * s, n)) / 6.f;
     return k;
 }
 __device__ __forceinline__ float sincf_pi(float k) {  // np.sinc(k / (2 pi)) = sin(k/2)/(k/2)
@@ -60,7 +79,8 @@ __device__ __forceinline__ Mode decode(const KArgs &a, uint32_t idx) {
     uint32_t r = idx / (uint32_t)g.nzh;
     m.iy = r % (uint32_t)g.ny;
     m.ix = r / (uint32_t)g.ny;
-    float kx = kfreq(m.ix, g.nx), ky = kfreq(m.iy, g.ny), kz = TWO_PI * (float)m.iz / (float)g.nz;
+    const int sx = sfreq(m.ix, g.nx), sy = sfreq(m.iy, g.ny);
+    float kx = TWO_PI * (float)sx / (float)g.nx, ky = TWO_PI * (float)sy / (float)g.ny, kz = TWO_PI * (float)m.iz / (float)g.nz;
     float kk = lap_term<LAP>(kx) + lap_term<LAP>(ky) + lap_term<LAP>(kz);
     float L = kk == 0.f ? 0.f : -1.f / kk;  // - safe_div(1, kk)
     if (a.kcut > 0.f) {
@@ -74,9 +94,9 @@ __device__ __forceinline__ Mode decode(const KArgs &a, uint32_t idx) {
         L /= d;
     }
     m.L = L * a.scale;
-    m.gk[0] = grad_term<GRAD>(kx);
-    m.gk[1] = grad_term<GRAD>(ky);
-    m.gk[2] = grad_term<GRAD>(kz);
+    m.gk[0] = grad_term<GRAD>(kx, sx, g.nx);
+    m.gk[1] = grad_term<GRAD>(ky, sy, g.ny);
+    m.gk[2] = grad_term<GRAD>(kz, m.iz, g.nz);
     m.nyq[0] = !(g.nx & 1) && m.ix == g.nx / 2;
     m.nyq[1] = !(g.ny & 1) && m.iy == g.ny / 2;
     m.nyq[2] = m.iz == g.nz / 2;

@@ -51,7 +51,8 @@ def test_force_meshes_match_oracle(nb, shape):
         assert rel_l2(got[c], want[c]) < 2e-6, c
 
 
-@pytest.mark.parametrize("shape", [(64, 64, 64), (128, 256, 64), (64, 128, 512), (48, 32, 16)])
+@pytest.mark.parametrize("shape", [(64, 64, 64), (128, 256, 64), (64, 128, 512), (1024, 64, 64), (64, 1024, 64), (64, 64, 1024),
+                                   (48, 32, 16)])
 def test_force_meshes_vjp_is_the_adjoint(nb, shape):
     rng = np.random.default_rng(1)
     fbar = rng.standard_normal((3,) + shape).astype(np.float32)

@@ -1,0 +1,576 @@
+"""The spectral operators on every FFT path against the float64 oracle.
+
+The library picks one of three implementations from the mesh shape and the kernel options, and the caller never sees
+which one ran ("Which path a spectral operator takes"):
+  A  every axis a power of two in 64..1024, default kernels: fused hand-written passes (xfused / xspec modes 0..5);
+  B  the same axes with FD orders 2 / 4, kcut or paint_deconv: hand-written plain passes (xplain) + the kspace.hip kernels;
+  C  any other axis: rocFFT + the kspace.hip kernels.
+Shapes with more than one axis length use three different lengths, so swapped axes cannot pass.  Inputs are a white
+half-spectrum (rfftn of standard-normal noise: every mode weighs the same, Nyquist planes and lines included) and a red one
+(synth.init_mesh: the weight sits at low k).  The oracle always gets the GPU's float32 / complex64 inputs cast up, so input
+rounding is not counted as error.  Measured errors are printed (`-s`) as `ERR <case> <value> gate <gate>`."""
+import ctypes as C
+import os
+
+import numpy as np
+import pytest
+
+pytestmark = pytest.mark.gpu
+
+from oracle import pm_oracle as o, background as obg  # noqa: E402  (checker only)
+
+INF = np.inf
+P1, P2, P3 = (64, 64, 64), (128, 64, 256), (64, 256, 128)
+P4, P5, P6 = (1024, 64, 64), (64, 1024, 64), (64, 64, 1024)
+G1, G2 = (48, 40, 24), (96, 64, 128)
+PATH_AB = [P1, P2, P3, P4, P5, P6]
+ALL = PATH_AB + [G1, G2]
+A_OBS = 0.7
+N_PTCL = 20000
+
+
+def sid(shape):
+    return "x".join(map(str, shape))
+
+
+def rel_l2(a, b):
+    a, b = np.asarray(a), np.asarray(b)
+    dt = np.complex128 if (np.iscomplexobj(a) or np.iscomplexobj(b)) else np.float64
+    a, b = a.astype(dt), b.astype(dt)
+    return float(np.linalg.norm(a - b) / max(np.linalg.norm(b), 1e-300))
+
+
+def per_mode(got, want, size=None):
+    """max |got - want| / |want| over the modes with |want| > 1e-3 rms(want): an error confined to a few modes (the
+    lowest k, the Nyquist planes) is not diluted by the rest of the spectrum as it is in a whole-field norm.
+    `size`: for an output that is a SUM of terms (the adjoint kernels, a prefilled accumulation) the error is measured
+    against sum_terms |term| instead of |want|.  Float32 cannot do better where the terms cancel: against |want| the
+    correct kernels measured up to 5.8e-5 at 64^3 (modes whose 3 or 6 random-phase terms nearly cancel), against the
+    terms' size at most 2.7e-6, while the FD Laplacian defect this file caught measured 5.5e-4 either way."""
+    got, want = np.asarray(got, np.complex128), np.asarray(want, np.complex128)
+    aw = np.abs(want) if size is None else np.asarray(size, np.float64)
+    m = aw > 1e-3 * np.sqrt(np.mean(aw ** 2))
+    return float(np.max(np.abs(got - want)[m] / aw[m]))
+
+
+def to_np(t):
+    return t.detach().cpu().numpy()
+
+
+def report(errs, name, value, gate):
+    print(f"ERR {name} {value:.3e} gate {gate:.0e}")
+    if not value <= gate:
+        errs.append(f"{name}: {value:.3e} > {gate:.0e}")
+
+
+@pytest.fixture(scope="module")
+def nb(gpu):
+    from montecosmo_amd import nbody
+    return nbody
+
+
+@pytest.fixture(scope="module", autouse=True)
+def oracle_threads():
+    prev = o.set_threads(min(len(os.sched_getaffinity(0)), 16))
+    yield
+    o.set_threads(prev)
+
+
+@pytest.fixture(scope="module")
+def cache():
+    """Inputs and oracle results shared by the cases of this module, keyed by (what, shape, input, ...)."""
+    return {}
+
+
+def memo(cache, key, fn):
+    if key not in cache:
+        cache[key] = fn()
+    return cache[key]
+
+
+def white(shape, seed=0):
+    return np.fft.rfftn(np.random.default_rng(seed).standard_normal(shape)).astype(np.complex64)
+
+
+def red(shape, seed=0):
+    from montecosmo_amd import synth
+    return synth.init_mesh(shape, seed=seed, rms_disp=1.0)
+
+
+def spectrum(cache, shape, kind):
+    return memo(cache, ("spec", shape, kind), lambda: white(shape, 11) if kind == "white" else red(shape, 12))
+
+
+def random_pos(shape, N, seed, spread=2.0):
+    """Positions over several box lengths; exact integers, half-integers and tiny negatives exercise floor /
+    round-half-even / wrap."""
+    rng = np.random.default_rng(seed)
+    n = np.asarray(shape, np.float64)
+    pos = (rng.uniform(-spread, spread, (N, 3)) * n).astype(np.float32)
+    pos[:64] = np.round(pos[:64])
+    pos[64:128] = np.round(pos[64:128]) + 0.5
+    pos[128:160] = -1e-7
+    return pos
+
+
+def particles(cache, shape):
+    return memo(cache, ("pos", shape), lambda: random_pos(shape, N_PTCL, 3))
+
+
+FD_OPTS = {"inf": dict(grad_fd=INF, lap_fd=INF), "fd22": dict(grad_fd=2, lap_fd=2), "fd44": dict(grad_fd=4, lap_fd=4),
+           "fd24_kcut2": dict(grad_fd=2, lap_fd=4, kcut=2.0)}
+
+
+# ------------------------------------------------------------------------------------------------ (a) pm_forces(pos, spec)
+@pytest.mark.parametrize("opts", list(FD_OPTS))
+@pytest.mark.parametrize("shape", ALL, ids=sid)
+def test_pm_forces_spectrum(nb, cache, shape, opts):
+    """Paths A (inf), B (FD, kcut; power-of-two shapes) and C: forces read at ~20k particles, NGP and CIC."""
+    kw = FD_OPTS[opts]
+    pos = particles(cache, shape)
+    p64 = pos.astype(np.float64)
+    kinds = ["white"] + (["red"] if shape in (P1, P4, P6) and opts in ("inf", "fd22") else [])
+    errs = []
+    for kind in kinds:
+        spec = spectrum(cache, shape, kind)
+        for ro in (1, 2):
+            got = to_np(nb.pm_forces(pos, spec, ro, **kw))
+            want = o.pm_forces(p64, spec.astype(np.complex128), ro, **kw)
+            report(errs, f"pm_forces[{sid(shape)}-{opts}-{kind}-ro{ro}]", rel_l2(got, want), 1e-5)
+    assert not errs, errs
+
+
+# ------------------------------------------------------------------------------------------------ (b) painted pm_forces
+PAINT_OPTS = [("deconv", 2, dict(paint_deconv=True)), ("fd24", 2, dict(grad_fd=2, lap_fd=4)), ("kcut2", 2, dict(kcut=2.0)),
+              ("deconv_fd42_kcut3", 2, dict(paint_deconv=True, grad_fd=4, lap_fd=2, kcut=3.0)),
+              ("ngp_deconv_fd24", 1, dict(paint_deconv=True, grad_fd=2, lap_fd=4))]
+
+
+@pytest.mark.parametrize("shape", [P1, P2, G2], ids=sid)
+def test_pm_forces_painted_options(nb, cache, shape):
+    """mesh = shape tuple with paint_deconv, FD orders and kcut: path B on power-of-two meshes, C on G2."""
+    pos = particles(cache, shape)
+    p64 = pos.astype(np.float64)
+    errs = []
+    for name, ro, kw in PAINT_OPTS:
+        got = to_np(nb.pm_forces(pos, shape, ro, **kw))
+        want = o.pm_forces(p64, shape, ro, **kw)
+        report(errs, f"pm_forces_painted[{sid(shape)}-{name}]", rel_l2(got, want), 1e-5)
+    assert not errs, errs
+
+
+# ------------------------------------------------------------------------------------------------ (c) pm_forces2
+@pytest.mark.parametrize("opts", ["inf", "fd22", "fd44"])
+@pytest.mark.parametrize("shape", ALL, ids=sid)
+def test_pm_forces2(nb, cache, shape, opts):
+    """2LPT source forces: xspec mode 3 + the fused Poisson solve (A), Hessian kernels + plain passes (B), rocFFT (C)."""
+    kw = FD_OPTS[opts]
+    pos = particles(cache, shape)
+    spec = spectrum(cache, shape, "white")
+    got = to_np(nb.pm_forces2(pos, spec, 2, **kw))
+    want = o.pm_forces2(pos.astype(np.float64), spec.astype(np.complex128), 2, **kw)
+    errs = []
+    report(errs, f"pm_forces2[{sid(shape)}-{opts}]", rel_l2(got, want), 1e-5)
+    assert not errs, errs
+
+
+# ------------------------------------------------------------------------------------------------ (d) pm_forces_vjp
+def real_pair_dot(a, b):
+    a, b = np.asarray(a, np.complex128), np.asarray(b, np.complex128)
+    return float(np.sum(a.real * b.real + a.imag * b.imag))
+
+
+@pytest.mark.parametrize("shape", ALL, ids=sid)
+def test_pm_forces_vjp(nb, cache, shape):
+    """Spectrum case (xspec mode 4 on A) and painted case (xfused mode 1 on A) against the oracle's VJP, and the
+    oracle-free identity <pm_forces(pos, ds), R> = <spec_bar, ds> (real-pair inner product over the half-spectrum) for a
+    Hermitian ds: it pins the cotangent convention (the multiplicity of the half-spectrum's modes) on its own.  The
+    identity's gate is relative to sqrt(sum (F R)^2), the natural scale of a sum of N random-sign terms."""
+    pos = particles(cache, shape)
+    p64 = pos.astype(np.float64)
+    rng = np.random.default_rng(50)
+    R = rng.standard_normal((N_PTCL, 3)).astype(np.float32)
+    R64 = R.astype(np.float64)
+    spec = spectrum(cache, shape, "white")
+    errs = []
+    pb, mb = nb.pm_forces_vjp(pos, spec, R)
+    pb_o, mb_o = o.pm_forces_vjp(p64, spec.astype(np.complex128), R64)
+    report(errs, f"pm_forces_vjp[{sid(shape)}-spec-pos_bar]", rel_l2(to_np(pb), pb_o), 2e-5)
+    report(errs, f"pm_forces_vjp[{sid(shape)}-spec-spec_bar]", rel_l2(to_np(mb), mb_o), 2e-5)
+    pb, none = nb.pm_forces_vjp(pos, shape, R)
+    pb_o, _ = o.pm_forces_vjp(p64, shape, R64)
+    assert none is None
+    report(errs, f"pm_forces_vjp[{sid(shape)}-painted-pos_bar]", rel_l2(to_np(pb), pb_o), 2e-5)
+    ds = white(shape, 51)
+    F = to_np(nb.pm_forces(pos, ds, 2)).astype(np.float64)
+    lhs, rhs = float(np.sum(F * R64)), real_pair_dot(to_np(mb), ds)
+    report(errs, f"pm_forces_dot[{sid(shape)}]", abs(lhs - rhs) / np.sqrt(np.sum((F * R64) ** 2)), 1e-5)
+    assert not errs, errs
+
+
+VJP_OPTS = [("deconv", dict(paint_deconv=True)), ("fd24", dict(grad_fd=2, lap_fd=4)),
+            ("deconv_fd44", dict(paint_deconv=True, grad_fd=4, lap_fd=4)), ("deconv_fd22", dict(paint_deconv=True, grad_fd=2, lap_fd=2))]
+
+
+@pytest.mark.parametrize("shape", [P1, P2, G2], ids=sid)
+def test_pm_forces_vjp_opts_abi(nb, cache, shape):
+    """mcpm_pm_forces_vjp_opts_f32 (painted, deconvolution + FD orders): R2C batch 3 + kspace_force_vjp + C2R (B, C)."""
+    import torch
+    pos = particles(cache, shape)
+    p64 = pos.astype(np.float64)
+    R = np.random.default_rng(52).standard_normal((N_PTCL, 3)).astype(np.float32)
+    plan = nb.get_plan(shape)
+    pt, rt = torch.from_numpy(pos).cuda(), torch.from_numpy(R).cuda()
+    errs = []
+    for name, kw in VJP_OPTS:
+        pb = torch.empty_like(pt)
+        plan.call("mcpm_pm_forces_vjp_opts_f32", C.c_void_p(pt.data_ptr()), N_PTCL, 0, 2, int(kw.get("paint_deconv", False)),
+                  nb._fd(kw.get("lap_fd", INF)), nb._fd(kw.get("grad_fd", INF)), C.c_void_p(rt.data_ptr()), C.c_void_p(pb.data_ptr()))
+        pb_o, _ = o.pm_forces_vjp(p64, shape, R.astype(np.float64), 2, **kw)
+        report(errs, f"pm_forces_vjp_opts[{sid(shape)}-{name}]", rel_l2(to_np(pb), pb_o), 2e-5)
+    assert not errs, errs
+
+
+# ------------------------------------------------------------------------------------------------ (e) lpt
+def cosmos():
+    from montecosmo_amd import bricks
+    return bricks.Planck18(), obg.Planck18()
+
+
+def light_cone_a(N, seed=4):
+    return 0.3 + 0.6 * np.random.default_rng(seed).uniform(size=(N, 1))
+
+
+def oracle_lpt(cos_o, F1, F2, a):
+    """o.lpt's growth combination (nbody.py:634-667) of the oracle's force arrays, so that both orders and both kinds of
+    `a` share one oracle force evaluation."""
+    dpos, vel = o.a2g(cos_o, a) * F1, F1
+    if F2 is not None:
+        dpos, vel = dpos - o.a2g2(cos_o, a) * F2, vel - o.a2dg2dg(cos_o, a) * F2
+    return dpos, vel
+
+
+LPT_CASES = ([(s, fd, k) for s in (P2, G1) for fd in ("inf", "fd22", "fd44") for k in ("white", "red")]
+             + [(P1, fd, k) for fd in ("inf", "fd22", "fd44") for k in ("white", "red")]
+             + [(s, "inf", k) for s in (P4, P5, P6) for k in ("white", "red")]
+             + [(P4, "fd44", "red"), (P5, "fd22", "white"), (P6, "fd22", "red")])
+
+
+@pytest.mark.parametrize("shape,opts,kind", LPT_CASES, ids=lambda v: sid(v) if isinstance(v, tuple) else v)
+def test_lpt_lattice(nb, shape, opts, kind):
+    """lpt on the regular lattice with read_order = 1 (mcpm_lpt_f32, the model's call): orders 1 and 2, scalar `a` and the
+    light cone (per-particle a in [0.3, 0.9])."""
+    cos_g, cos_o = cosmos()
+    kw = FD_OPTS[opts]
+    spec = white(shape, 21) if kind == "white" else red(shape, 22)
+    s64 = spec.astype(np.complex128)
+    pos = o.regular_pos(shape)
+    lat = nb.LatticePos.regular(shape)
+    F1 = o.pm_forces(pos, s64, 1, **kw)
+    F2 = o.pm_forces2(pos, s64, 1, **kw)
+    a_lc = light_cone_a(pos.shape[0])
+    errs = []
+    for order in (1, 2):
+        for aname, a in (("a_obs", A_OBS), ("cone", a_lc)):
+            dp, v = nb.lpt(cos_g, spec, lat, a, lpt_order=order, read_order=1, **kw)
+            dp_o, v_o = oracle_lpt(cos_o, F1, F2 if order == 2 else None, a)
+            tag = f"lpt[{sid(shape)}-{opts}-{kind}-o{order}-{aname}]"
+            report(errs, tag + "-dpos", rel_l2(to_np(dp), dp_o), 1e-5)
+            report(errs, tag + "-vel", rel_l2(to_np(v), v_o), 1e-5)
+    assert not errs, errs
+
+
+def test_lpt_config1(nb):
+    """BASELINE config 1 on its own: 64^3 mesh and particles, 2LPT, read_order = 1, at a = a_obs and on the light cone,
+    against o.lpt itself."""
+    cos_g, cos_o = cosmos()
+    spec = red(P1, 1)
+    pos = o.regular_pos(P1)
+    errs = []
+    for aname, a in (("a_obs", A_OBS), ("cone", light_cone_a(pos.shape[0], 5))):
+        dp, v = nb.lpt(cos_g, spec, nb.LatticePos.regular(P1), a, lpt_order=2, read_order=1)
+        dp_o, v_o = o.lpt(cos_o, spec.astype(np.complex128), pos, a, lpt_order=2, read_order=1)
+        report(errs, f"lpt_config1[{aname}]-dpos", rel_l2(to_np(dp), dp_o), 1e-5)
+        report(errs, f"lpt_config1[{aname}]-vel", rel_l2(to_np(v), v_o), 1e-5)
+    assert not errs, errs
+
+
+def test_lpt_particle_lattice_differs_from_mesh(nb):
+    """Fused lattice path with a particle lattice coarser than the mesh along x and finer along y (P2)."""
+    cos_g, cos_o = cosmos()
+    ptcl = (64, 128, 256)
+    spec = red(P2, 23)
+    pos = o.regular_pos(P2, ptcl)
+    lat = nb.LatticePos.regular(P2, ptcl)
+    errs = []
+    for aname, a in (("a_obs", A_OBS), ("cone", light_cone_a(pos.shape[0], 6))):
+        dp, v = nb.lpt(cos_g, spec, lat, a, lpt_order=2, read_order=1)
+        dp_o, v_o = o.lpt(cos_o, spec.astype(np.complex128), pos, a, lpt_order=2, read_order=1)
+        report(errs, f"lpt_ptcl_lattice[{aname}]-dpos", rel_l2(to_np(dp), dp_o), 1e-5)
+        report(errs, f"lpt_ptcl_lattice[{aname}]-vel", rel_l2(to_np(v), v_o), 1e-5)
+    assert not errs, errs
+
+
+def test_lpt_not_fused(nb):
+    """lpt off the fused path: read_order = 2 at displaced lattice positions (pm_forces + pm_forces2 on P2)."""
+    cos_g, cos_o = cosmos()
+    spec = red(P2, 24)
+    N = int(np.prod(P2))
+    disp = (0.3 * np.random.default_rng(7).standard_normal((N, 3))).astype(np.float32)
+    pos64 = o.regular_pos(P2) + disp.astype(np.float64)
+    errs = []
+    for order in (1, 2):
+        dp, v = nb.lpt(cos_g, spec, nb.LatticePos(disp, P2), A_OBS, lpt_order=order, read_order=2)
+        dp_o, v_o = o.lpt(cos_o, spec.astype(np.complex128), pos64, A_OBS, lpt_order=order, read_order=2)
+        report(errs, f"lpt_not_fused[o{order}]-dpos", rel_l2(to_np(dp), dp_o), 1e-5)
+        report(errs, f"lpt_not_fused[o{order}]-vel", rel_l2(to_np(v), v_o), 1e-5)
+    assert not errs, errs
+
+
+# ------------------------------------------------------------------------------------------------ (f) lpt_vjp
+LPT_VJP_CASES = ([(P1, o_, c) for o_ in (1, 2) for c in (False, True)] + [(G1, o_, c) for o_ in (1, 2) for c in (False, True)]
+                 + [(P2, 2, False), (P2, 1, True), (P4, 2, False), (P6, 2, True)])
+
+
+@pytest.mark.parametrize("shape,order,cone", LPT_VJP_CASES, ids=lambda v: sid(v) if isinstance(v, tuple) else str(v))
+def test_lpt_vjp(nb, shape, order, cone):
+    """lpt_vjp (xspec modes 4 / 5 on A): init_mesh_bar against the oracle; scalar cotangents as in
+    test_lpt_vjp_standalone, per-particle ones (light cone) as in test_lpt_light_cone."""
+    cos_g, cos_o = cosmos()
+    spec = red(shape, 31)
+    pos = o.regular_pos(shape)
+    N = pos.shape[0]
+    rng = np.random.default_rng(32)
+    a = light_cone_a(N, 33) if cone else A_OBS
+    xb, vb = rng.standard_normal((N, 3)), rng.standard_normal((N, 3))
+    xb32, vb32 = xb.astype(np.float32), vb.astype(np.float32)
+    mb_g, sb_g = nb.lpt_vjp(cos_g, spec, nb.LatticePos.regular(shape), a, xb32, vb32, lpt_order=order)
+    mb_o, _, sb_o = o.lpt_vjp(cos_o, spec.astype(np.complex128), pos, a, xb32.astype(np.float64), vb32.astype(np.float64),
+                              lpt_order=order, read_order=1)
+    errs = []
+    tag = f"lpt_vjp[{sid(shape)}-o{order}-{'cone' if cone else 'a_obs'}]"
+    report(errs, tag + "-init_mesh_bar", rel_l2(to_np(mb_g), mb_o), 2e-5)
+    keys = ("g", "g2", "dg2dg") if order == 2 else ("g",)
+    for k in keys:
+        if cone:
+            report(errs, f"{tag}-{k}_bar", rel_l2(to_np(sb_g[k]), sb_o[k]), 1e-5)
+        else:
+            assert np.isclose(sb_g[k], sb_o[k], rtol=1e-4, atol=1e-4 * abs(sb_o["g"])), (tag, k, sb_g[k], sb_o[k])
+    if order == 1 and not cone:
+        # oracle-free: lpt of order 1 is linear in the spectrum, <lpt(ds), (xb, vb)> = <init_mesh_bar, ds>
+        ds = white(shape, 34)
+        dp, v = nb.lpt(cos_g, ds, nb.LatticePos.regular(shape), a, lpt_order=1, read_order=1)
+        terms = np.concatenate([(to_np(dp) * xb32).ravel(), (to_np(v) * vb32).ravel()]).astype(np.float64)
+        lhs, rhs = float(np.sum(terms)), real_pair_dot(to_np(mb_g), ds)
+        report(errs, tag + "-dot", abs(lhs - rhs) / np.sqrt(np.sum(terms ** 2)), 1e-5)
+    assert not errs, errs
+
+
+LPT_VJP_FD = [(P1, "fd22"), (P2, "fd44"), (P6, "fd22")]
+
+
+@pytest.mark.parametrize("shape,opts", LPT_VJP_FD, ids=lambda v: sid(v) if isinstance(v, tuple) else v)
+def test_lpt_vjp_opts_abi(nb, shape, opts):
+    """mcpm_lpt_vjp_opts_f32 with FD kernels (path B: kspace_force_vjp / kspace_hessian_vjp + plain passes), order 2."""
+    import torch
+    cos_g, cos_o = cosmos()
+    kw = FD_OPTS[opts]
+    spec = red(shape, 35)
+    pos = o.regular_pos(shape)
+    N = pos.shape[0]
+    rng = np.random.default_rng(36)
+    xb, vb = rng.standard_normal((N, 3)).astype(np.float32), rng.standard_normal((N, 3)).astype(np.float32)
+    plan = nb.get_plan(shape)
+    st, xt, vt = torch.from_numpy(spec).cuda(), torch.from_numpy(xb).cuda(), torch.from_numpy(vb).cuda()
+    out = torch.empty_like(st)
+    sc = np.array([nb.a2g(cos_g, A_OBS), nb.a2g2(cos_g, A_OBS), nb.a2dg2dg(cos_g, A_OBS)], dtype=np.float64)
+    sb = np.zeros(3)
+    plan.call("mcpm_lpt_vjp_opts_f32", C.c_void_p(st.data_ptr()), 2, nb._dptr(sc), nb._fd(kw["lap_fd"]), nb._fd(kw["grad_fd"]),
+              C.c_void_p(xt.data_ptr()), C.c_void_p(vt.data_ptr()), C.c_void_p(out.data_ptr()), nb._dptr(sb))
+    mb_o, _, sb_o = o.lpt_vjp(cos_o, spec.astype(np.complex128), pos, A_OBS, xb.astype(np.float64), vb.astype(np.float64),
+                              lpt_order=2, read_order=1, **kw)
+    errs = []
+    report(errs, f"lpt_vjp_opts[{sid(shape)}-{opts}]-init_mesh_bar", rel_l2(to_np(out), mb_o), 2e-5)
+    for i, k in enumerate(("g", "g2", "dg2dg")):
+        assert np.isclose(sb[i], sb_o[k], rtol=1e-4, atol=1e-4 * abs(sb_o["g"])), (k, sb[i], sb_o[k])
+    assert not errs, errs
+
+
+# ------------------------------------------------------------------------------------------------ (g) kspace.hip ABI
+def hermitian_project(spec):
+    """What irfftn keeps of a half-spectrum: the Hermitian part of its kz = 0 and kz = nz/2 planes (nz even)."""
+    out = np.array(spec, np.complex128)
+    for iz in (0, -1):
+        plane = out[..., iz]
+        out[..., iz] = 0.5 * (plane + o.hermitian_symmetric(plane))
+    return out
+
+
+def kspace_factors(shape, lap, grad, kcut=INF, deconv=0):
+    """The oracle's kernels: L = invlaplace * gaussian / rectangular_hat^2 and the three gradient factors (i k_c)."""
+    kvec = o.rfftk(shape)
+    L = o.invlaplace_hat(kvec, lap) * o.gaussian_hat(kvec, kcut)
+    if deconv:
+        L = L / o.rectangular_hat(kvec, order=deconv) ** 2
+    return L, [o.gradient_hat(kvec, c, grad) for c in range(3)]
+
+
+def zweights(shape):
+    return o._zweights(shape)
+
+
+def irfftn(spec, shape):
+    import scipy.fft
+    return scipy.fft.irfftn(np.asarray(spec, np.complex128), s=shape, axes=(0, 1, 2), workers=min(len(os.sched_getaffinity(0)), 16))
+
+
+def noise_like(rng, shape, rms):
+    return ((rng.standard_normal(shape) + 1j * rng.standard_normal(shape)) * rms).astype(np.complex64)
+
+
+FDI = {INF: 0, 2: 2, 4: 4}
+FORCE_CASES = [(INF, INF, INF, 0), (2, 2, INF, 0), (4, 4, INF, 0), (4, 2, 2.0, 0), (2, 4, INF, 1), (INF, INF, 2.0, 2),
+               (2, INF, INF, 2), (INF, 4, 3.0, 1)]
+FORCE_VJP_FLAGS = [(0, 0, 0), (1, 0, 1), (0, 1, 0), (1, 0, 0), (0, 0, 1), (0, 1, 1), (1, 0, 1), (0, 1, 0)]
+HESS_CASES = [(INF, INF), (2, 2), (4, 4), (2, 4), (4, INF)]
+HESS_VJP_FLAGS = [(0, 0), (1, 1), (1, 0), (0, 1), (1, 1)]
+
+
+@pytest.mark.parametrize("shape", [P1, P4, P6, G1], ids=sid)
+def test_kspace_kernels_abi(nb, shape):
+    """mcpm_kspace_force_f32 / _vjp_f32 and mcpm_kspace_hessian_f32 / _vjp_f32 mode by mode against numpy products of
+    the oracle's kernels, over the FD orders (same and mixed), kcut, deconv_order, zweights, hermitian and accumulate
+    (prefilled with noise).  The forward kernels project onto what irfftn keeps: checked against the Hermitian projection
+    of the product, by irfftn of both, and by the Hermitian symmetry of the output's kz = 0 / Nyquist planes."""
+    import torch
+    plan = nb.get_plan(shape)
+    rng = np.random.default_rng(40)
+    Mh = int(np.prod(o.r2chshape(shape)))
+    cshape = o.r2chshape(shape)
+    scale = 0.37
+
+    def dev(x):
+        return torch.from_numpy(np.ascontiguousarray(x, np.complex64)).cuda()
+
+    def ptr(t):
+        return C.c_void_p(t.data_ptr())
+
+    def noise(b):
+        return np.stack([np.fft.rfftn(rng.standard_normal(shape)) for _ in range(b)]).astype(np.complex64)
+
+    zw = zweights(shape)
+    errs = []
+    x1 = noise(1)[0]
+    x1_t, x64 = dev(x1), x1.astype(np.complex128)
+    for i, (lap, grad, kcut, dec) in enumerate(FORCE_CASES):
+        tag = f"kspace_force[{sid(shape)}-lap{lap}-grad{grad}-kcut{kcut}-dec{dec}]"
+        L, gk = kspace_factors(shape, lap, grad, kcut, dec)
+        mult = [scale * (-gk[c]) * L for c in range(3)]
+        out = torch.empty((3,) + cshape, dtype=torch.complex64, device="cuda")
+        plan.call("mcpm_kspace_force_f32", ptr(x1_t), ptr(out), scale, FDI[lap], FDI[grad], 0.0 if kcut == INF else kcut, dec)
+        got = to_np(out)
+        for c in range(3):
+            raw = mult[c] * x64
+            want = hermitian_project(raw)
+            report(errs, f"{tag}-c{c}-per_mode", per_mode(got[c], want), 1e-5)
+            report(errs, f"{tag}-c{c}-max_abs", float(np.max(np.abs(got[c] - want)) / np.max(np.abs(want))), 1e-5)
+            if c == i % 3:
+                report(errs, f"{tag}-c{c}-irfftn", rel_l2(irfftn(got[c], shape), irfftn(raw, shape)), 2e-6)
+            for iz in (0, -1):
+                pl = got[c][..., iz].astype(np.complex128)
+                report(errs, f"{tag}-c{c}-hermitian_plane{iz}", float(np.max(np.abs(pl - o.hermitian_symmetric(pl)))
+                                                                      / max(np.max(np.abs(pl)), 1e-30)), 1e-6)
+        # adjoint
+        zwf, herm, acc = FORCE_VJP_FLAGS[i]
+        if herm:
+            y = noise(3)     # a C2R's input: Hermitian on the special planes
+        else:
+            y = noise_like(rng, (3,) + cshape, 1.0)
+        w = zw if zwf else 1.0
+        raw = sum(np.conj(mult[c]) * y[c].astype(np.complex128) for c in range(3)) * w
+        size = sum(np.abs(mult[c] * y[c]) for c in range(3)) * w
+        pre = noise_like(rng, cshape, np.sqrt(np.mean(np.abs(raw) ** 2)))   # prefill of the size of the result
+        y_t = dev(y)
+        out = dev(pre) if acc else torch.empty(cshape, dtype=torch.complex64, device="cuda")
+        plan.call("mcpm_kspace_force_vjp_f32", ptr(y_t), ptr(out), scale, FDI[lap], FDI[grad], 0.0 if kcut == INF else kcut, dec,
+                  zwf, herm, acc)
+        got = to_np(out).astype(np.complex128)
+        tagv = f"kspace_force_vjp[{sid(shape)}-lap{lap}-grad{grad}-kcut{kcut}-dec{dec}-zw{zwf}-herm{herm}-acc{acc}]"
+        accd = pre.astype(np.complex128) if acc else 0.0
+        if herm:
+            want = hermitian_project(raw) + accd
+            report(errs, tagv + "-irfftn", rel_l2(irfftn(got - accd, shape), irfftn(raw, shape)), 2e-6)
+            if not acc:
+                for iz in (0, -1):
+                    pl = got[..., iz]
+                    report(errs, f"{tagv}-hermitian_plane{iz}", float(np.max(np.abs(pl - o.hermitian_symmetric(pl)))
+                                                                       / max(np.max(np.abs(pl)), 1e-30)), 1e-6)
+        else:
+            want = raw + accd
+        report(errs, tagv + "-per_mode", per_mode(got, want, size + (np.abs(pre) if acc else 0.0)), 1e-5)
+    for i, (lap, grad) in enumerate(HESS_CASES):
+        tag = f"kspace_hessian[{sid(shape)}-lap{lap}-grad{grad}]"
+        L, gk = kspace_factors(shape, lap, grad)
+        mult = [scale * gk[a] * gk[b] * L for a in range(3) for b in range(a, 3)]
+        out = torch.empty((6,) + cshape, dtype=torch.complex64, device="cuda")
+        plan.call("mcpm_kspace_hessian_f32", ptr(x1_t), ptr(out), scale, FDI[lap], FDI[grad])
+        got = to_np(out)
+        for k in range(6):
+            raw = mult[k] * x64
+            want = hermitian_project(raw)
+            report(errs, f"{tag}-h{k}-per_mode", per_mode(got[k], want), 1e-5)
+            report(errs, f"{tag}-h{k}-max_abs", float(np.max(np.abs(got[k] - want)) / np.max(np.abs(want))), 1e-5)
+            if k == i or (i == 0 and k == 5):
+                report(errs, f"{tag}-h{k}-irfftn", rel_l2(irfftn(got[k], shape), irfftn(raw, shape)), 2e-6)
+        zwf, acc = HESS_VJP_FLAGS[i]
+        y = noise_like(rng, (6,) + cshape, 1.0)
+        w = zw if zwf else 1.0
+        raw = sum(np.conj(mult[k]) * y[k].astype(np.complex128) for k in range(6)) * w
+        size = sum(np.abs(mult[k] * y[k]) for k in range(6)) * w
+        pre = noise_like(rng, cshape, np.sqrt(np.mean(np.abs(raw) ** 2)))
+        y_t = dev(y)
+        out = dev(pre) if acc else torch.empty(cshape, dtype=torch.complex64, device="cuda")
+        plan.call("mcpm_kspace_hessian_vjp_f32", ptr(y_t), ptr(out), scale, FDI[lap], FDI[grad], zwf, acc)
+        got = to_np(out).astype(np.complex128)
+        want = raw + (pre.astype(np.complex128) if acc else 0.0)
+        report(errs, f"kspace_hessian_vjp[{sid(shape)}-lap{lap}-grad{grad}-zw{zwf}-acc{acc}]-per_mode",
+               per_mode(got, want, size + (np.abs(pre) if acc else 0.0)), 1e-5)
+        del y, y_t, out
+    assert not errs, errs
+
+
+# ------------------------------------------------------------------------------------------------ (h) R2C / C2R batches
+@pytest.mark.parametrize("shape", [P2, P4, P5, P6, G1], ids=sid)
+def test_fft_batches_abi(nb, shape):
+    """mcpm_fft_r2c / mcpm_fft_c2r at batch 1, 3 and 6 (xplain_kernel + batched y / z passes, or rocFFT) against numpy;
+    the C2R gets a NON-Hermitian half-spectrum, which it must project as numpy's irfftn does."""
+    import torch
+    import scipy.fft
+    plan = nb.get_plan(shape)
+    cshape = o.r2chshape(shape)
+    M = int(np.prod(shape))
+    rng = np.random.default_rng(60)
+    w = min(len(os.sched_getaffinity(0)), 16)
+    errs = []
+    for b in (1, 3, 6):
+        x = rng.standard_normal((b,) + shape).astype(np.float32)
+        xt = torch.from_numpy(x).cuda()
+        st = torch.empty((b,) + cshape, dtype=torch.complex64, device="cuda")
+        plan.call("mcpm_fft_r2c", C.c_void_p(xt.data_ptr()), C.c_void_p(st.data_ptr()), b)
+        got = to_np(st)
+        want = scipy.fft.rfftn(x.astype(np.float64), axes=(1, 2, 3), workers=w)
+        report(errs, f"fft_r2c[{sid(shape)}-b{b}]", rel_l2(got, want), 2e-6)
+        for j in range(b):
+            report(errs, f"fft_r2c[{sid(shape)}-b{b}-member{j}]", rel_l2(got[j], want[j]), 2e-6)
+        del xt, st, got, want
+        Z = (rng.standard_normal((b,) + cshape) + 1j * rng.standard_normal((b,) + cshape)).astype(np.complex64)
+        zt = torch.from_numpy(Z).cuda()
+        yt = torch.empty((b,) + shape, dtype=torch.float32, device="cuda")
+        plan.call("mcpm_fft_c2r", C.c_void_p(zt.data_ptr()), C.c_void_p(yt.data_ptr()), b)
+        got = to_np(yt)
+        want = M * scipy.fft.irfftn(Z.astype(np.complex128), s=shape, axes=(1, 2, 3), workers=w)
+        report(errs, f"fft_c2r[{sid(shape)}-b{b}]", rel_l2(got, want), 2e-6)
+        for j in range(b):
+            report(errs, f"fft_c2r[{sid(shape)}-b{b}-member{j}]", rel_l2(got[j], want[j]), 2e-6)
+        del zt, yt, got, want
+    assert not errs, errs
