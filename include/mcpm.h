@@ -67,7 +67,7 @@ int mcpm_plan_slab_oob(mcpm_plan *plan, int64_t *count);
 int mcpm_plan_destroy(mcpm_plan *plan);
 const char *mcpm_last_error(const mcpm_plan *plan); /* plan may be NULL: last error of a failed create */
 /* ABI revision string; the Python loader (montecosmo_amd/_lib.py) refuses a library that reports another one. */
-#define MCPM_ABI_VERSION "mcpm 0.6 (gfx950)"
+#define MCPM_ABI_VERSION "mcpm 0.7 (gfx950)"
 const char *mcpm_version(void);
 /* Tiled CIC paints (montecosmo_amd/csrc/paint_tiled.hip).  A tile's window is a box of lattice points per axis -- chosen on the device
    for every input and every tile from the displacement field around it, or (16 + 2 halo + 1)^3 around the tile's bulk displacement when a
@@ -535,6 +535,26 @@ int mcpm_chreshape_c64(void *stream, const float *in, int in_nx, int in_ny, int 
                        int out_nz);
 int mcpm_chreshape_vjp_c64(void *stream, const float *out_bar, int out_nx, int out_ny, int out_nz, float *in_bar, int in_nx,
                            int in_ny, int in_nz);
+
+/* Binned power spectra (montecosmo/metrics.py:_spectrum, spectrum.hip): one pass over one or two complex64 half-spectra
+   [batch][nx][ny][nz/2+1] (nz even; batch rows `stride0` / `stride1` complex elements apart, 0 = the same spectrum for every
+   row; spec1 NULL = auto spectrum of spec0 only).  Host float64 inputs: ktab = per-axis |k| components [nx | ny | nz/2+1] in the
+   caller's units (rfftk(shape, box_size)); deconv0 / deconv1 = per-axis factors 1/sinc(k_cell/2pi)^order in the same layout, or
+   NULL; edges[n_edges] strictly increasing (MCPM_E_ARG otherwise), 2 <= n_edges <= MCPM_SPECTRUM_MAX_EDGES; los[3] the unit line
+   of sight (zeros: mu = 0); ells[n_ells] multipoles in 0..8, 1 <= n_ells <= 9.  A mode falls in bin i (0-based) when
+   edges[i] <= |k| < edges[i+1] (np.digitize, right=False, bins 1..n_edges-1); |k|^2 = (kx^2 + ky^2) + kz^2 unfused, correctly
+   rounded sqrt.  `out` (device, OVERWRITTEN): float64 [batch][n_acc][n_edges-1] bin sums with the Hermitian weight w (1 on the
+   kz = 0 and kz = nz/2 planes, else 2): acc 0 = sum w, 1 = sum w |k|, then per multipole j with c = w (2l+1) L_l(mu):
+   one input:  2 + j = sum c |d0|^2;
+   two inputs: 2 + 4j = sum c |d0|^2, 3 + 4j = sum c |d1|^2, 4 + 4j = sum c Re(d0 conj d1), 5 + 4j = sum c Im(d0 conj d1).
+   Bitwise reproducible; a batch row equals the single call.  `work` (device, work_bytes >= mcpm_spectrum_workspace(...)) is the
+   caller's; the call synchronises `stream` once after uploading the tables.  No plan: `stream` is a hipStream_t. */
+#define MCPM_SPECTRUM_MAX_EDGES 4096
+int mcpm_spectrum_workspace(int nx, int ny, int nz, int n_edges, int n_ells, int two_inputs, int batch, int64_t *bytes);
+int mcpm_spectrum_bins_c64(void *stream, int nx, int ny, int nz, const float *spec0, int64_t stride0, const float *spec1,
+                           int64_t stride1, int batch, const double *ktab, const double *deconv0, const double *deconv1,
+                           const double *edges, int n_edges, const double *los, const int *ells, int n_ells, void *work,
+                           int64_t work_bytes, double *out);
 
 /* RK4 on atab = logspace(log10_amin, 0, steps); writes seven host arrays of length `steps`. */
 int mcpm_growth_table(double Omega_m, double Omega_de, double Omega_k, double w0, double wa,

@@ -19,7 +19,7 @@ from __future__ import annotations
 import numpy as np
 import torch
 
-from . import nbody, bricks
+from . import nbody, bricks, metrics
 from .utils import scale_shape, r2chshape, chreshape, chreshape_vjp
 
 
@@ -64,6 +64,16 @@ class FieldLevelForward:
                 "curved_sky", "evolution", "nbody_a_start", "nbody_n_steps", "lpt_order", "paint_order", "paint_deconv",
                 "interlace_order", "lin_kpow")
         return {k: getattr(self, k) for k in keys}
+
+    # ---- metrics (model.py:1370-1379) ----------------------------------------------------------------------
+    def spectrum(self, mesh0, mesh1=None, ells: int | list = 0, kedges: int | float | list = None, include_corners=True):
+        """metrics.spectrum with the model's box_size and box_center."""
+        return metrics.spectrum(mesh0, mesh1=mesh1, box_size=self.box_size, box_center=self.box_center, ells=ells, kedges=kedges,
+                                include_corners=include_corners)
+
+    def powtranscoh(self, mesh0, mesh1, kedges: int | float | list = None, include_corners=True):
+        """(k, pow1, (pow1 / pow0)^.5, pow01 / (pow0 pow1)^.5) with the model's box_size; a batched mesh1 gives batched outputs."""
+        return metrics.powtranscoh(mesh0, mesh1, box_size=self.box_size, kedges=kedges, include_corners=include_corners)
 
     # ---- pieces ------------------------------------------------------------------------------------------
     def _kphys(self, shape):
