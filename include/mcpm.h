@@ -67,7 +67,7 @@ int mcpm_plan_slab_oob(mcpm_plan *plan, int64_t *count);
 int mcpm_plan_destroy(mcpm_plan *plan);
 const char *mcpm_last_error(const mcpm_plan *plan); /* plan may be NULL: last error of a failed create */
 /* ABI revision string; the Python loader (montecosmo_amd/_lib.py) refuses a library that reports another one. */
-#define MCPM_ABI_VERSION "mcpm 0.7 (gfx950)"
+#define MCPM_ABI_VERSION "mcpm 0.8 (gfx950)"
 const char *mcpm_version(void);
 /* Tiled CIC paints (montecosmo_amd/csrc/paint_tiled.hip).  A tile's window is a box of lattice points per axis -- chosen on the device
    for every input and every tile from the displacement field around it, or (16 + 2 halo + 1)^3 around the tile's bulk displacement when a
@@ -126,6 +126,11 @@ int mcpm_paint_f32(mcpm_plan *plan, const float *pos, int64_t n, int pos_mode, c
    three-component read w.r.t. its meshes).  weights3 is float32 [N][3]; the three meshes are contiguous. */
 int mcpm_paint3_f32(mcpm_plan *plan, const float *pos, int64_t n, int pos_mode, const float *weights3, int order,
                     float *meshes3, int accumulate);
+/* The same with every weight taken as wscale * weights3[p][c] (one float32 product): bit for bit the meshes that
+   mcpm_paint3_f32 gives for the scaled array formed in memory, without forming it (the tile kernels fold wscale into
+   their fixed-point scale).  What a chained reverse sweep paints: beta (v_bar + tau x_bar) from the carried sum. */
+int mcpm_paint3_scaled_f32(mcpm_plan *plan, const float *pos, int64_t n, int pos_mode, const float *weights3, float wscale,
+                           int order, float *meshes3, int accumulate);
 /* read (nbody.py:398-427) of `ncomp` contiguous meshes at once: out[p*ncomp + c]. */
 int mcpm_read_f32(mcpm_plan *plan, const float *pos, int64_t n, int pos_mode, const float *meshes,
                   int ncomp, int order, float *out);
@@ -356,9 +361,20 @@ int mcpm_bullfrog_step_vjp_from_f32(mcpm_plan *plan, const float *pos_in, const 
                                     const float *vel_bar_src, float *pos_bar, float *vel_bar, double *alpha_bar, double *beta_bar,
                                     double dtau_ddg, double *dg_bar);
 /* Optional chaining of consecutive adjoint steps: call this before the adjoint of step i with beta and tau of step
-   i-1; the particle kernel then also writes step i-1's force cotangent beta'(v_bar + tau' x_bar), and the next
-   mcpm_bullfrog_step_vjp_f32 call skips its own pass over the cotangents IF it is given the same pos_bar / vel_bar
-   pointers and exactly these scalars.  Only valid when the caller does not modify the cotangents in between. */
+   i-1 (beta', tau').  The next step's force cotangent beta' (v_bar + tau' x_bar) then needs no pass of its own:
+     - mcpm_bullfrog_step_vjp_f32 / _from_f32 (hinted) leave  v_bar + tau' pos_bar  in vel_bar, NOT v_bar; pos_bar is the
+       true cotangent throughout.  The next mcpm_bullfrog_step_vjp*_f32 call, IF it is given these pos_bar / vel_bar
+       pointers as its incoming cotangents and exactly these scalars, paints beta' times that sum and feeds it to its
+       particle kernel as it is: the arithmetic of the chain that keeps the force cotangent in memory, bit for bit, with
+       one (N, 3) array less written per step.  The last call of a chain (not hinted) leaves the true v_bar in vel_bar.
+     - Any other adjoint-step call on the plan (other pointers or scalars, mcpm_step_adjoint_particles*_f32, and
+       mcpm_plan_chained_fb, with which a composed step begins) first turns
+       the pending sum back, vel_bar -= tau' pos_bar, on the pointers of the hinted call -- which therefore have to stay
+       allocated until the plan's next adjoint-step call -- and proceeds unchained: never an error and never a wrong
+       gradient, but this repair is exact only to rounding (one ulp of max(|v_bar|, |tau' pos_bar|) per element).
+     - mcpm_step_adjoint_particles*_f32 (hinted) keep v_bar in vel_bar and write the force cotangent to plan memory
+       (mcpm_plan_chained_fb).
+   Only valid when the caller does not modify the cotangents in between; reading vel_bar in between shows the sum. */
 int mcpm_plan_hint_next_adjoint(mcpm_plan *plan, double beta_next, double tau_next);
 /* After a hinted mcpm_step_adjoint_particles_f32: *fb = plan-owned F_bar = beta (v_bar + tau x_bar) (Np x 3 floats) of the
    next adjoint step if (beta, tau, pos_bar, vel_bar) are the hinted ones, else NULL (then the caller forms it itself with

@@ -120,6 +120,13 @@ __device__ __forceinline__ void absmax_commit(float a, float b, float c, unsigne
     }
 }
 
+// nt: bit 0 streaming loads, bit 1 streaming stores; the two mode bits of a chained reverse sweep (wave-uniform):
+//   MCPM_ADJ_CARRIED_IN: the array at vb_src holds u = v_bar + tau x_bar (left by the previous call's carry-out), so vt = u as it is;
+//   MCPM_ADJ_CARRY_OUT:  vb receives u' = v_bar_new + tau_next x_bar_new instead of v_bar_new, and no fb_next is written: the next
+//                        call's paint takes its weights as beta_next u' and its particle kernel reads vt = u'.
+// Both sums are ONE fma, written out, so that the carried and the materialised sweep round alike (u' here, vt in the next call).
+#define MCPM_ADJ_CARRIED_IN 4
+#define MCPM_ADJ_CARRY_OUT 8
 template <int ORDER, bool IL>
 __global__ __launch_bounds__(256) void step_adjoint_kernel(Geom g, const float *__restrict__ x, const float *__restrict__ v,
                                                            const float *xb_src, const float *vb_src, float *xb, float *vb,
@@ -144,7 +151,8 @@ __global__ __launch_bounds__(256) void step_adjoint_kernel(Geom g, const float *
         float f[3];
         locate<MCPM_POS_LATTICE, ORDER>(g, pi, d, c, f);
         Stencil<ORDER> s(g, c);
-        const P3 vt = {vbi.x + tau * xbi.x, vbi.y + tau * xbi.y, vbi.z + tau * xbi.z};
+        P3 vt = vbi;
+        if (!(nt & MCPM_ADJ_CARRIED_IN)) vt = P3{__builtin_fmaf(tau, xbi.x, vbi.x), __builtin_fmaf(tau, xbi.y, vbi.y), __builtin_fmaf(tau, xbi.z, vbi.z)};
         const float Fb[3] = {beta * vt.x, beta * vt.y, beta * vt.z};
         float F[3], G[3][3];
         interp3<ORDER, true, IL>(fm, M, s, f, F, G);
@@ -167,19 +175,20 @@ __global__ __launch_bounds__(256) void step_adjoint_kernel(Geom g, const float *
             const float vnx = alpha * vi.x + beta * F[0], vny = alpha * vi.y + beta * F[1], vnz = alpha * vi.z + beta * F[2];
             rc = dtau_ddg * (xin.x * vnx + xin.y * vny + xin.z * vnz);
         }
-        const P3 vnew = {alpha * vt.x, alpha * vt.y, alpha * vt.z};
+        P3 vnew = {alpha * vt.x, alpha * vt.y, alpha * vt.z};
+        if (fb_next || (nt & MCPM_ADJ_CARRY_OUT)) {  // force cotangent of the PREVIOUS step, F_bar = beta' u', u' = v_bar + tau' x_bar
+            const P3 u = {__builtin_fmaf(tau_next, xbi.x, vnew.x), __builtin_fmaf(tau_next, xbi.y, vnew.y), __builtin_fmaf(tau_next, xbi.z, vnew.z)};
+            fbn = P3{beta_next * u.x, beta_next * u.y, beta_next * u.z};      // in registers: its maximum scales the fixed-point paint
+            if (nt & MCPM_ADJ_CARRY_OUT) vnew = u;                              // handed on in v_bar's place; F_bar is not stored
+            else if (nt & 2) store3_nt(fb_next, pi.i, fbn.x, fbn.y, fbn.z);
+            else store3(fb_next, pi.i, fbn);
+        }
         if (nt & 2) {
             store3_nt(xb, pi.i, xbi.x, xbi.y, xbi.z);
             store3_nt(vb, pi.i, vnew.x, vnew.y, vnew.z);
         } else {
             store3(xb, pi.i, xbi);
             store3(vb, pi.i, vnew);
-        }
-        if (fb_next) {  // force cotangent of the PREVIOUS step, F_bar = beta' (v_bar + tau' x_bar)
-            fbn = P3{beta_next * (vnew.x + tau_next * xbi.x), beta_next * (vnew.y + tau_next * xbi.y),
-                     beta_next * (vnew.z + tau_next * xbi.z)};
-            if (nt & 2) store3_nt(fb_next, pi.i, fbn.x, fbn.y, fbn.z);
-            else store3(fb_next, pi.i, fbn);
         }
     }
     block_add3_max(ra, rb, rc, part, gridDim.x, fbn.x, fbn.y, fbn.z, fb_max);
@@ -196,7 +205,9 @@ __global__ void axpby_kernel(const float *__restrict__ x, const float *__restric
                              float *__restrict__ out, unsigned *__restrict__ out_max) {
     unsigned r = 0u;      // max |out| as bits: a NaN / Inf stays the maximum
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-        const float o = a * x[i] + b * y[i];
+        // one explicit form: left to the compiler, the unrolled pairs of this loop became fma(a, x, b y) and its remainder
+        // a x + b y with both products rounded, so the result depended on how many elements a thread was given (on the grid)
+        const float o = __builtin_fmaf(a, x[i], b * y[i]);
         out[i] = o;
         r = max(r, __float_as_uint(o) & 0x7fffffffu);
     }
@@ -248,6 +259,7 @@ static int axpby(mcpm_plan *p, const float *x, const float *y, int64_t n, float 
         if (!p->fx_clean) MCPM_HIP(p, hipMemsetAsync(p->fx_wmax, 0, sizeof(unsigned) * MCPM_FX_SLOTS * MCPM_FX_STRIDE, p->stream));
         p->fx_clean = 0;
         p->fx_src = out;
+        p->fx_scale = 1.f;
     }
     axpby_kernel<<<nb, 256, 0, p->stream>>>(x, y, n, a, b, out, with_max ? p->fx_wmax : nullptr);
     MCPM_LAUNCH_CHECK(p, "axpby_kernel");
@@ -370,7 +382,8 @@ static int lpt_vjp_device(mcpm_plan *p, const float *init_mesh, int lpt_order, c
 static int step_adjoint_particles(mcpm_plan *p, const float *pos_in, const float *vel_in, const float *force_meshes, int layout,
                                   const float *rho_bar, double alpha, double beta, double tau, int paint_order, float *pos_bar,
                                   float *vel_bar, double *alpha_bar, double *beta_bar, double dtau_ddg, double *dg_bar,
-                                  const float *pos_bar_src, const float *vel_bar_src);
+                                  const float *pos_bar_src, const float *vel_bar_src, int mode);
+static int carry_undo(mcpm_plan *p);
 // force-mesh layout of the steppers' checkpoints: 1 = interleaved [cell][3] (hand-written Poisson solve), 0 = three meshes
 static inline int step_layout(const mcpm_plan *p) { return mcpm_fftpm_supported(p) ? 1 : 0; }
 
@@ -551,18 +564,26 @@ int mcpm_bullfrog_step_vjp_from_f32(mcpm_plan *p, const float *pos_in, const flo
     MCPM_REQUIRE(p, paint_order >= 1 && paint_order <= 4, MCPM_E_ORDER, "mcpm_bullfrog_step_vjp_f32: paint_order must be 1..4");
     MCPM_TRY(ensure_pscratch(p));
     const int64_t N = p->Np;
-    float *Fb = ps_arr(p, 2);
     const float b = (float)beta, t = (float)tau;
-    // force cotangent F_bar = beta (v_bar + tau x_bar), scattered onto three meshes (adjoint of read); already written
-    // by the previous call's particle kernel when the caller chained the steps (mcpm_plan_hint_next_adjoint)
-    if (!(p->fb_valid && p->fb_beta == b && p->fb_tau == t && p->fb_xb == pos_bar_src && p->fb_vb == vel_bar_src))
+    // force cotangent F_bar = beta (v_bar + tau x_bar), scattered onto three meshes (adjoint of read).  When the caller chained
+    // the steps (mcpm_plan_hint_next_adjoint) the previous call's particle kernel left u = v_bar + tau x_bar where v_bar would
+    // be: the paint takes its weights as beta u (no F_bar array at all) and the particle kernel reads vt = u as it is.
+    const bool carried = p->carry_valid && p->carry_beta == b && p->carry_tau == t && p->carry_xb == pos_bar_src && p->carry_vb == vel_bar_src;
+    if (carried) {
+        p->carry_valid = 0;
+        MCPM_TRY(mcpm_paint3_scaled(p, pos_in, N, MCPM_POS_LATTICE, vel_bar_src, b, paint_order, p->fmesh, 0));
+    } else {
+        MCPM_TRY(carry_undo(p));      // a chain that this call does not continue: its vel_bar is made v_bar again first
+        float *Fb = ps_arr(p, 2);
         MCPM_TRY(axpby(p, vel_bar_src, pos_bar_src, 3 * N, b, b * t, Fb, true));
+        MCPM_TRY(mcpm_paint3_scaled(p, pos_in, N, MCPM_POS_LATTICE, Fb, 1.f, paint_order, p->fmesh, 0));
+    }
     p->fb_valid = 0;
-    MCPM_TRY(mcpm_paint3_f32(p, pos_in, N, MCPM_POS_LATTICE, Fb, paint_order, p->fmesh, 0));
     // adjoint of 3 C2R + k-space + R2C: rho_bar = C2R( (1/M) sum_c conj(m_c) R2C(f_bar_c) )
     MCPM_TRY(mcpm_force_meshes_vjp_f32(p, p->fmesh, p->rho));
     return step_adjoint_particles(p, pos_in, vel_in, force_meshes, step_layout(p), p->rho, alpha, beta, tau, paint_order, pos_bar,
-                                  vel_bar, alpha_bar, beta_bar, dtau_ddg, dg_bar, pos_bar_src, vel_bar_src);
+                                  vel_bar, alpha_bar, beta_bar, dtau_ddg, dg_bar, pos_bar_src, vel_bar_src,
+                                  MCPM_ADJ_CARRY_OUT | (carried ? MCPM_ADJ_CARRIED_IN : 0));
 }
 
 int mcpm_bullfrog_step_vjp_f32(mcpm_plan *p, const float *pos_in, const float *vel_in, const float *force_meshes,
@@ -586,6 +607,7 @@ int mcpm_axpby_f32(mcpm_plan *p, const float *x, const float *y, int64_t n, floa
 int mcpm_plan_chained_fb(mcpm_plan *p, double beta, double tau, const float *pos_bar, const float *vel_bar, float **fb) {
     if (!p || !fb) return MCPM_E_ARG;
     *fb = nullptr;
+    MCPM_TRY(carry_undo(p));      // a composed step begins here: it must see the true v_bar before it forms F_bar itself
     if (p->fb_valid && p->fb_beta == (float)beta && p->fb_tau == (float)tau && p->fb_xb == pos_bar && p->fb_vb == vel_bar && p->pscratch)
         *fb = ps_arr(p, 2);
     p->fb_valid = 0;
@@ -597,7 +619,7 @@ int mcpm_step_adjoint_particles_f32(mcpm_plan *p, const float *pos_in, const flo
                                     float *pos_bar, float *vel_bar, double *alpha_bar, double *beta_bar, double dtau_ddg,
                                     double *dg_bar) {
     return step_adjoint_particles(p, pos_in, vel_in, force_meshes, 0, rho_bar, alpha, beta, tau, paint_order, pos_bar, vel_bar,
-                                  alpha_bar, beta_bar, dtau_ddg, dg_bar, nullptr, nullptr);
+                                  alpha_bar, beta_bar, dtau_ddg, dg_bar, nullptr, nullptr, 0);
 }
 
 }  // extern "C"
@@ -609,46 +631,74 @@ extern "C" int mcpm_step_adjoint_particles_il_f32(mcpm_plan *p, const float *pos
                                                   float *pos_bar, float *vel_bar, double *alpha_bar, double *beta_bar, double dtau_ddg,
                                                   double *dg_bar) {
     return step_adjoint_particles(p, pos_in, vel_in, force_mesh_il, 1, rho_bar, alpha, beta, tau, paint_order, pos_bar, vel_bar,
-                                  alpha_bar, beta_bar, dtau_ddg, dg_bar, nullptr, nullptr);
+                                  alpha_bar, beta_bar, dtau_ddg, dg_bar, nullptr, nullptr, 0);
 }
 
-// pos_bar_src / vel_bar_src: where the incoming cotangents are read (NULL: pos_bar / vel_bar, in place)
+// A pending carry (vel_bar holds v_bar + tau_next pos_bar: see the kernel) that the call at hand does not continue is turned
+// back into the true cotangent, v_bar = u - tau_next x_bar: exact only to rounding (one ulp of max(|u|, |tau_next x_bar|)).
+static int carry_undo(mcpm_plan *p) {
+    if (!p->carry_valid) return MCPM_OK;
+    p->carry_valid = 0;
+    if (p->fx_src == p->carry_vb) p->fx_src = nullptr;      // the maximum left for the paint of that array is beta_next u's
+    float *vb = (float *)p->carry_vb;
+    return axpby(p, (const float *)p->carry_xb, vb, 3 * p->Np, -p->carry_tau, 1.f, vb);      // fma(-tau', x_bar, u)
+}
+
+// pos_bar_src / vel_bar_src: where the incoming cotangents are read (NULL: pos_bar / vel_bar, in place).
+// mode: MCPM_ADJ_CARRY_OUT = a pending hint makes this call hand on u' in vel_bar (the composite drivers: they also do the next
+// step's paint); without it a pending hint makes the kernel write F_bar' to plan scratch (mcpm_plan_chained_fb: callers that compose
+// the step themselves).  MCPM_ADJ_CARRIED_IN: vel_bar_src holds u (the driver has matched the pending carry).
 static int step_adjoint_particles(mcpm_plan *p, const float *pos_in, const float *vel_in, const float *force_meshes, int layout,
                                   const float *rho_bar, double alpha, double beta, double tau, int paint_order, float *pos_bar,
                                   float *vel_bar, double *alpha_bar, double *beta_bar, double dtau_ddg, double *dg_bar,
-                                  const float *pos_bar_src, const float *vel_bar_src) {
+                                  const float *pos_bar_src, const float *vel_bar_src, int mode) {
     if (!p) return MCPM_E_ARG;
     if (!pos_bar_src) pos_bar_src = pos_bar;
     if (!vel_bar_src) vel_bar_src = vel_bar;
     MCPM_REQUIRE(p, pos_in && vel_in && force_meshes && rho_bar && pos_bar && vel_bar, MCPM_E_ARG,
                  "mcpm_step_adjoint_particles_f32: null buffer");
     MCPM_REQUIRE(p, paint_order >= 1 && paint_order <= 4, MCPM_E_ORDER, "mcpm_step_adjoint_particles_f32: paint_order must be 1..4");
+    if (!(mode & MCPM_ADJ_CARRIED_IN)) MCPM_TRY(carry_undo(p));
     const int64_t N = p->Np, M = p->M;
     const float a = (float)alpha, b = (float)beta, t = (float)tau;
     dim3 grid, block;
     lattice_launch(p->g, grid, block);
-    // algorithmic bytes: x, v, x_bar, v_bar in (48 N), x_bar, v_bar out (24 N), three force meshes + rho_bar gathered once (16 M); in a
-    // chained reverse sweep the kernel also WRITES the next step's force cotangent (12 N: the axpby pass it replaces)
-    StageTimer st_(p, ST_STEPADJ, 72.0 * N + 16.0 * M + (p->hint_set ? 12.0 * N : 0.0));
+    const bool hinted = p->hint_set != 0, carry_out = hinted && (mode & MCPM_ADJ_CARRY_OUT);
+    // algorithmic bytes: x, v, x_bar, v_bar in (48 N), x_bar, v_bar out (24 N), three force meshes + rho_bar gathered once (16 M).  In a
+    // chained reverse sweep the next step's force cotangent costs nothing more when it is carried (u' goes out where v_bar would);
+    // materialised (mcpm_plan_chained_fb) the kernel also WRITES it (12 N: the axpby pass it replaces)
+    StageTimer st_(p, ST_STEPADJ, 72.0 * N + 16.0 * M + (hinted && !carry_out ? 12.0 * N : 0.0));
     float *fb_next = nullptr;
-    if (p->hint_set) {
-        MCPM_TRY(ensure_pscratch(p));
-        fb_next = ps_arr(p, 2);
-        p->fb_valid = 1;
-        p->fb_beta = p->hint_beta;
-        p->fb_tau = p->hint_tau;
-        p->fb_xb = pos_bar;
-        p->fb_vb = vel_bar;
+    if (hinted) {
         p->hint_set = 0;
-        if (p->paint3_variant == 4) {   // the fixed-point paint of fb_next needs max|fb_next| (slots zero after a tiled paint3)
+        const float *fx_arr;
+        if (carry_out) {
+            p->carry_valid = 1;
+            p->carry_beta = p->hint_beta;
+            p->carry_tau = p->hint_tau;
+            p->carry_xb = pos_bar;
+            p->carry_vb = vel_bar;
+            fx_arr = vel_bar;
+        } else {
+            MCPM_TRY(ensure_pscratch(p));
+            fb_next = ps_arr(p, 2);
+            p->fb_valid = 1;
+            p->fb_beta = p->hint_beta;
+            p->fb_tau = p->hint_tau;
+            p->fb_xb = pos_bar;
+            p->fb_vb = vel_bar;
+            fx_arr = fb_next;
+        }
+        if (p->paint3_variant == 4) {   // the fixed-point paint of F_bar' needs max|F_bar'| (slots zero after a tiled paint3)
             if (!p->fx_clean) MCPM_HIP(p, hipMemsetAsync(p->fx_wmax, 0, sizeof(unsigned) * MCPM_FX_SLOTS * MCPM_FX_STRIDE, p->stream));
             p->fx_clean = 0;
-            p->fx_src = fb_next;
+            p->fx_src = fx_arr;      // max|wscale w| of a paint of `fx_arr` with this wscale is in fx_wmax
+            p->fx_scale = carry_out ? p->hint_beta : 1.f;
         }
     }
-    unsigned *fb_max = (fb_next && p->paint3_variant == 4) ? p->fx_wmax : nullptr;
+    unsigned *fb_max = (hinted && p->paint3_variant == 4) ? p->fx_wmax : nullptr;
     static const int ntp_env = [] { const char *e = getenv("MCPM_NT_PART"); return e ? atoi(e) : 3; }();     // streaming loads / stores: 2.80 -> 2.62 ms at 512^3
-    const int ntp = N < ((int64_t)1 << 23) ? 0 : ntp_env;      // not for problems that live in the caches
+    const int ntp = (N < ((int64_t)1 << 23) ? 0 : (ntp_env & 3)) | (mode & MCPM_ADJ_CARRIED_IN) | (carry_out ? MCPM_ADJ_CARRY_OUT : 0);      // (streaming: not for problems that live in the caches)
     double *P, *Q;      // this launch's per-workgroup partials of (alpha_bar, beta_bar, dg_bar)
     unsigned *ticket, R;
     MCPM_TRY(mcpm_det_scratch(p, 3, grid.x, &P, &Q, &ticket, &R));
@@ -800,9 +850,10 @@ int mcpm_plan_probe_particle_pitch(mcpm_plan *p, float *flat, int64_t flat_float
             (void)hipMemsetAsync(p->pscratch, 0, sizeof(float) * 3 * pitch, p->stream);
             for (int rep = 0; rep < 4 && rc == MCPM_OK; ++rep) {      // the first call warms up
                 if (rep == 1) (void)hipEventRecord(e0, p->stream);
-                p->hint_set = 1, p->hint_beta = 0.f, p->hint_tau = 0.f;      // as inside a reverse sweep: the kernel also writes F_bar
+                // as inside a reverse sweep: cotangents carried in and carried out (six particle streams, no F_bar array)
+                p->hint_set = 1, p->hint_beta = 0.f, p->hint_tau = 0.f, p->carry_valid = 0;
                 rc = step_adjoint_particles(p, flat, flat + pitch, p->fmesh, step_layout(p), p->rho, 1.0, 0.0, 0.0, 2, ps_arr(p, 0), ps_arr(p, 1),
-                                            nullptr, nullptr, 1.0, nullptr, nullptr, nullptr);
+                                            nullptr, nullptr, 1.0, nullptr, nullptr, nullptr, MCPM_ADJ_CARRIED_IN | MCPM_ADJ_CARRY_OUT);
             }
             if (rc != MCPM_OK) break;
             (void)hipEventRecord(e1, p->stream);
@@ -814,6 +865,8 @@ int mcpm_plan_probe_particle_pitch(mcpm_plan *p, float *flat, int64_t flat_float
         (void)hipEventDestroy(e0);
         (void)hipEventDestroy(e1);
         p->fb_valid = 0;
+        p->carry_valid = 0;      // (the probe's arrays are scratch: nothing to turn back)
+        p->hint_set = 0;
         p->fx_src = nullptr;
         p->ppitch = keep;
         if (rc != MCPM_OK) return rc;
@@ -867,7 +920,7 @@ int mcpm_nbody_bf_vjp_f32(mcpm_plan *p, const float *init_mesh, int n_steps, con
     auto state_x = [&](int i) { return ckpt + (int64_t)(2 * i) * pitch; };
     auto state_v = [&](int i) { return ckpt + (int64_t)(2 * i + 1) * pitch; };
     auto force_m = [&](int i) { return ckpt + (int64_t)n_steps * 2 * mcpm_pitch_max(p) + (int64_t)i * 3 * M; };
-    MCPM_HIP(p, hipMemsetAsync(p->reduce, 0, sizeof(double) * (2 * n_steps + 4 + 256), p->stream));
+    MCPM_HIP(p, hipMemsetAsync(p->reduce, 0, sizeof(double) * (2 * n_steps + 4), p->stream));
     p->fb_valid = 0;
     for (int i = n_steps - 1; i >= 0; --i) {
         if (i > 0) MCPM_TRY(mcpm_plan_hint_next_adjoint(p, beta[i - 1], dg));

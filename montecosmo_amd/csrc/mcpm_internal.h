@@ -85,15 +85,22 @@ struct mcpm_plan {
     unsigned *fx_wmax;  // fixed-point paint: bits of max|w|, maximum over MCPM_FX_SLOTS slots (device)
     int *fx_redo;       // fixed-point paint: [0] = number of flagged tiles, then their indices (device)
     int fx_tiles;       // capacity of fx_redo
-    const float *fx_src; // weights whose max|w| a producer kernel already left in fx_wmax (else NULL)
+    const float *fx_src; // weights whose max|fx_scale w| a producer kernel already left in fx_wmax (else NULL): a three-component paint of
+                         // this array with wscale == fx_scale skips its absmax pass
+    float fx_scale;      // 1 for a materialised F_bar (axpby, the adjoint kernel's fb_next); beta_next for the carried u' array
     int fx_clean;        // fx_wmax is all zero (the last three-component paint's epilogue cleared it): producers skip their memset
     long long *gx_acc;  // generic (order-independent) paint: int64 fixed-point accumulator mesh, all-zero between calls; allocated on first use
     unsigned *gx_wmax;  // generic paint: bits of max|w| (MCPM_FX_SLOTS slots)
-    // chaining of adjoint steps (mcpm_plan_hint_next_adjoint): the adjoint particle kernel of step i also writes the
-    // force cotangent F_bar of step i-1, saving one pass over the cotangents
-    int hint_set, fb_valid;
-    float hint_beta, hint_tau, fb_beta, fb_tau;
-    const void *fb_xb, *fb_vb;
+    // chaining of adjoint steps (mcpm_plan_hint_next_adjoint): hint_* = (beta, tau) of step i-1, pending until the adjoint particle
+    // kernel of step i consumes them.  Two forms (composite.hip, step_adjoint_particles):
+    //   carry_* (the composite drivers, mcpm_bullfrog_step_vjp*_f32): the kernel left u' = v_bar + tau' x_bar in the caller's
+    //     vel_bar array (carry_vb; carry_xb = its pos_bar) -- no F_bar array exists; the next call's paint scales u' by beta'.
+    //     Pending until that call matches it (same pointers, same scalars as float) or any other adjoint-step call turns it back.
+    //   fb_* (mcpm_step_adjoint_particles*_f32 + mcpm_plan_chained_fb: callers that compose the step, slabs): the kernel also
+    //     wrote F_bar' = beta' u' to plan scratch and vel_bar is the true v_bar.
+    int hint_set, fb_valid, carry_valid;
+    float hint_beta, hint_tau, fb_beta, fb_tau, carry_beta, carry_tau;
+    const void *fb_xb, *fb_vb, *carry_xb, *carry_vb;
     // x-slab decomposition (mcpm_plan_create_slab): this rank owns global planes [rank*nxl, (rank+1)*nxl)
     int nranks, rank, ghost, nx_global, nxl;
     unsigned *dmax; // caller's MCPM_FX_SLOTS x MCPM_FX_STRIDE slots: kick_drift leaves max |d_x| (as float bits) there; NULL = off
@@ -194,7 +201,10 @@ int mcpm_fftpm_spec_meshes_vjp(mcpm_plan *p, const float *meshes_bar, float *spe
 
 // tiled CIC paints (paint_tiled.hip); false: geometry not tileable, the caller takes the generic path
 bool mcpm_paint_tiled(mcpm_plan *p, const float *pos, const float *w, int64_t wstride, float wscalar, float *mesh, int accumulate);
-bool mcpm_paint3_tiled(mcpm_plan *p, const float *pos, const float *weights3, float *meshes3, int accumulate);
+// every consumer of the weights sees wscale * weights3 (one f32 product, as if the scaled array had been formed in memory)
+bool mcpm_paint3_tiled(mcpm_plan *p, const float *pos, const float *weights3, float wscale, float *meshes3, int accumulate);
+int mcpm_paint3_scaled(mcpm_plan *p, const float *pos, int64_t n, int mode, const float *weights3, float wscale, int order, float *meshes3,
+                       int accumulate);
 
 // adjoint of the NGP lattice read on a lattice != mesh: order-independent fixed-point sums (particles.hip)
 int mcpm_lattice_scatter_fx(mcpm_plan *p, const float *xb, const float *vb, float a, float b, float *meshes3);

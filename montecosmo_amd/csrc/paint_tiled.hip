@@ -719,7 +719,7 @@ __device__ __forceinline__ void paint_bucket_body(const Geom &g, const float *__
 // window misses the particle -- the same predicate as the coverage duty, re-evaluated over all particles.
 template <int NC>
 __device__ __forceinline__ void paint_leftover_body(const Geom &g, const float *__restrict__ disp, const float *__restrict__ w,
-                                                    int64_t wstride, float wscalar, float *__restrict__ mesh, int64_t M,
+                                                    int64_t wstride, float wscalar, float wmul, float *__restrict__ mesh, int64_t M,
                                                     const TileLists &L, const int bid, const int nblk) {
     const int nw = min(L.cnts[C_WILD], L.listcap);
     if (bid == 0 && threadIdx.x == 0) L.cnts[C_LAST] = L.cnts[C_WILD] + L.cnts[C_PAIRS];
@@ -735,7 +735,7 @@ __device__ __forceinline__ void paint_leftover_body(const Geom &g, const float *
         const P3 d = load3(disp, gi);
         float wt[3];
 #pragma unroll
-        for (int c = 0; c < NC; ++c) wt[c] = w ? w[(int64_t)gi * wstride + c] : wscalar;
+        for (int c = 0; c < NC; ++c) wt[c] = w ? wmul * w[(int64_t)gi * wstride + c] : wscalar;
         if (!(fabsf(d.x) < 3.0e4f && fabsf(d.y) < 3.0e4f && fabsf(d.z) < 3.0e4f)) {
             // non-finite position, or beyond the int16 index range of the reference (nbody.py:369): no cell can be named;
             // the first cell of every component is made non-finite so that the caller sees it
@@ -778,7 +778,7 @@ __device__ __forceinline__ void paint_leftover_body(const Geom &g, const float *
                              if (L.bcnt[tidx] <= L.cap) return;      // that tile's bucket was deposited by the bucket kernel
                              const int x0 = (tidx / (ntz * nty)) * MCPM_TILE, y0 = ((tidx / ntz) % nty) * MCPM_TILE, z0 = (tidx % ntz) * MCPM_TILE;
                              float wt[3];
-                             for (int c = 0; c < NC; ++c) wt[c] = w ? w[gi * wstride + c] : wscalar;
+                             for (int c = 0; c < NC; ++c) wt[c] = w ? wmul * w[gi * wstride + c] : wscalar;
                              for (int a = 0; a < 2; ++a)
                                  for (int b = 0; b < 2; ++b)
                                      for (int e = 0; e < 2; ++e) {
@@ -804,7 +804,7 @@ __global__ __launch_bounds__(256) void paint_epilogue_kernel(Geom g, const float
     __shared__ u64 tile[MCPM_TILE * MCPM_TILE * MCPM_TILE];
     if ((int)blockIdx.x < nbk) paint_bucket_body<WMODE>(g, disp, w, wstride, wscalar, mesh, L, wmax_bits, tile, (int)blockIdx.x, nbk);
     else {
-        paint_leftover_body<1>(g, disp, w, wstride, wscalar, mesh, M, L, (int)blockIdx.x - nbk, (int)gridDim.x - nbk);
+        paint_leftover_body<1>(g, disp, w, wstride, wscalar, 1.f, mesh, M, L, (int)blockIdx.x - nbk, (int)gridDim.x - nbk);
     }
 }
 
@@ -823,11 +823,12 @@ __global__ __launch_bounds__(256) void paint_epilogue_kernel(Geom g, const float
 // < 2^17 deposits per cell).  A tile holding a cell with bound >= 2^19 is not written: it is appended to the redo list and
 // painted by the f64 kernel.  Non-finite or tiny (< 2^-97) max|w| sends every tile there.  Rounding: half a unit per deposit
 // = max|w| 2^-25, so the mesh differs from the exact sums by ~1e-8 max|w| per cell.
-__global__ __launch_bounds__(256) void absmax_kernel(const float *__restrict__ w, int64_t stride, int64_t n, unsigned *__restrict__ out) {
+// (scale: the maximum is that of |scale w|, the weights as a scaled three-component paint deposits them)
+__global__ __launch_bounds__(256) void absmax_kernel(const float *__restrict__ w, int64_t stride, int64_t n, float scale, unsigned *__restrict__ out) {
     float m = 0.f;
     unsigned bad = 0;
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
-        const unsigned b = __float_as_uint(w[i * stride]) & 0x7fffffffu;
+        const unsigned b = __float_as_uint(scale * w[i * stride]) & 0x7fffffffu;
         bad |= b >= 0x7f800000u;
         m = fmaxf(m, __uint_as_float(b));
     }
@@ -841,7 +842,7 @@ __global__ __launch_bounds__(256) void absmax_kernel(const float *__restrict__ w
 // over the tiles listed in redo ([0] = count, then indices).  F64: accumulators are doubles (96 KB) instead of packed fields.
 // One tile of the three-component paint (redo_tile < 0: the tile of this block; else the given tile, for the f64 repaint).
 template <bool F64, int THREADS, int U, int FAST>
-__device__ __forceinline__ void paint3_tile_body(const Geom &g, const float *__restrict__ disp, const float *__restrict__ w3,
+__device__ __forceinline__ void paint3_tile_body(const Geom &g, const float *__restrict__ disp, const float *__restrict__ w3, const float wscale,
                                                  float *__restrict__ mesh, int64_t M, int accumulate, const TileLists &L,
                                                  const unsigned *__restrict__ wmax_bits, int *__restrict__ redo_out, int redo_tile, int duty,
                                                  u64 *tile, int &flagged, int *sh27, int *sus) {
@@ -879,8 +880,15 @@ __device__ __forceinline__ void paint3_tile_body(const Geom &g, const float *__r
             deposit = false;
             if (threadIdx.x == 0) redo_out[1 + atomicAdd(redo_out, 1)] = tidx;
         } else {
-            S = __uint_as_float((278u - be) << 23);      // 2^(24-e)
-            Sinv = __uint_as_float((be - 24u) << 23);    // 2^(e-24)
+            // The weight scale rides in the power-of-two scale: w (wscale S) is (wscale w) S bit for bit (S only shifts the exponent)
+            // unless a product is subnormal, and a deposit that small rounds to 0 either way: nothing is added to the visit loop.
+            // 2^e is the maximum of |wscale w| (wmax_bits), so the integer sums and Sinv are those of the scaled weights.
+            S = wscale * __uint_as_float((278u - be) << 23);      // wscale 2^(24-e)
+            Sinv = __uint_as_float((be - 24u) << 23);             // 2^(e-24)
+            if (!(fabsf(S) >= 1.17549435e-38f && fabsf(S) <= 3.40282347e38f)) {      // wscale S left the normal range: f64 tiles
+                deposit = false;
+                if (threadIdx.x == 0) redo_out[1 + atomicAdd(redo_out, 1)] = tidx;
+            }
         }
     }
     if (threadIdx.x == 0) {
@@ -907,6 +915,7 @@ __device__ __forceinline__ void paint3_tile_body(const Geom &g, const float *__r
                 if (FAST == 1 || gis[u] >= 0) {
                     d[u] = load3w<FAST>(disp, gis[u]);
                     wt[u] = load3w<FAST>(w3, gis[u]);
+                    if (F64) wt[u] = P3{wscale * wt[u].x, wscale * wt[u].y, wscale * wt[u].z};      // (fixed point: folded into S)
                 }
             }
             wi.next();
@@ -1058,7 +1067,7 @@ __device__ __forceinline__ void paint3_tile_body(const Geom &g, const float *__r
 // workgroups that return at once cost 30 us per adjoint step at 512^3).
 // (four waves per SIMD = two 512-thread workgroups per CU: with three candidate bodies the allocator would take 133 registers)
 template <bool F64, int THREADS, int U, int FAST = 0>
-__global__ __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(4))) void paint3_tile_kernel(Geom g, const float *__restrict__ disp, const float *__restrict__ w3,
+__global__ __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(4))) void paint3_tile_kernel(Geom g, const float *__restrict__ disp, const float *__restrict__ w3, float wscale,
                                                               float *__restrict__ mesh, int64_t M, int accumulate, TileLists L,
                                                               const unsigned *__restrict__ wmax_bits, int *__restrict__ redo_out,
                                                               const int *__restrict__ redo_in, int duty) {
@@ -1068,14 +1077,14 @@ __global__ __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(4))) vo
     __shared__ int sh27[27];
     __shared__ int sus[MCPM_SUS + 2];
     if (!redo_in) {
-        paint3_tile_body<F64, THREADS, U, FAST>(g, disp, w3, mesh, M, accumulate, L, wmax_bits, redo_out, -1, duty, tile, flagged, sh27, sus);
+        paint3_tile_body<F64, THREADS, U, FAST>(g, disp, w3, wscale, mesh, M, accumulate, L, wmax_bits, redo_out, -1, duty, tile, flagged, sh27, sus);
         return;
     }
     if (!F64) return;      // only the f64 instance repaints (the fixed-point one would carry three more window-walk bodies, and their
                            // scalar-register pressure, for a branch it never takes)
     const int n = redo_in[0];
     for (int k = blockIdx.x; k < n; k += gridDim.x) {
-        paint3_tile_body<F64, THREADS, U, FAST>(g, disp, w3, mesh, M, accumulate, L, wmax_bits, redo_out, redo_in[1 + k], duty, tile, flagged, sh27, sus);
+        paint3_tile_body<F64, THREADS, U, FAST>(g, disp, w3, wscale, mesh, M, accumulate, L, wmax_bits, redo_out, redo_in[1 + k], duty, tile, flagged, sh27, sus);
         __syncthreads();
     }
 }
@@ -1084,18 +1093,18 @@ __global__ __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(4))) vo
 // time is latency): two such workgroups per CU need eight waves per SIMD, i.e. at most 64 VGPRs (the 512-thread instance takes 75).
 template <int FAST>
 __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(8, 8))) void paint3_tile_wide_kernel(Geom g, const float *__restrict__ disp,
-                                                              const float *__restrict__ w3, float *__restrict__ mesh, int64_t M, int accumulate,
+                                                              const float *__restrict__ w3, float wscale, float *__restrict__ mesh, int64_t M, int accumulate,
                                                               TileLists L, const unsigned *__restrict__ wmax_bits, int *__restrict__ redo_out, int duty) {
     constexpr int NT = MCPM_TILE * MCPM_TILE * (MCPM_TILE + 2);      // z-padded
     __shared__ u64 tile[2 * NT];
     __shared__ int flagged;
     __shared__ int sh27[27];
     __shared__ int sus[MCPM_SUS + 2];
-    paint3_tile_body<false, 1024, 2, FAST>(g, disp, w3, mesh, M, accumulate, L, wmax_bits, redo_out, -1, duty, tile, flagged, sh27, sus);
+    paint3_tile_body<false, 1024, 2, FAST>(g, disp, w3, wscale, mesh, M, accumulate, L, wmax_bits, redo_out, -1, duty, tile, flagged, sh27, sus);
 }
 
 // buckets of the three-component paint: int64 fixed point with the max|w| 2^-28 scale, doubles when the weights are non-finite
-__device__ __forceinline__ void paint3_bucket_body(const Geom &g, const float *__restrict__ disp, const float *__restrict__ w3,
+__device__ __forceinline__ void paint3_bucket_body(const Geom &g, const float *__restrict__ disp, const float *__restrict__ w3, const float wscale,
                                                    float *__restrict__ mesh, int64_t M, const TileLists &L,
                                                    const unsigned *__restrict__ wmax_bits, u64 *tile, const int bid, const int nblk) {
     constexpr int B = MCPM_TILE, NT = B * B * B;
@@ -1119,7 +1128,8 @@ __device__ __forceinline__ void paint3_bucket_body(const Geom &g, const float *_
             const P3 d = load3(disp, gi);
             int cx, cy, cz;
             if (!bucket_cell(g, gi, d, x0, y0, z0, cx, cy, cz)) continue;
-            const P3 wt = load3(w3, gi);
+            P3 wt = load3(w3, gi);
+            wt = P3{wscale * wt.x, wscale * wt.y, wscale * wt.z};
             const float tx1 = d.x - floorf(d.x), ty1 = d.y - floorf(d.y), tz1 = d.z - floorf(d.z);
             const float kx[2] = {1.f - tx1, tx1}, ky[2] = {1.f - ty1, ty1}, kz[2] = {1.f - tz1, tz1};
             const float s = F64 ? 1.f : sc.S;
@@ -1161,15 +1171,15 @@ __device__ __forceinline__ void paint3_bucket_body(const Geom &g, const float *_
 // Epilogue of the three-component paint, one launch: buckets | leftovers (see paint_epilogue_kernel).  The last block to
 // finish also clears the max|w| slots: they are zero between paints, so the kernel that produces the next weights (the
 // adjoint particle kernel, axpby) commits its maximum without a memset launch in front of it.
-__global__ __launch_bounds__(256) void paint3_epilogue_kernel(Geom g, const float *__restrict__ disp, const float *__restrict__ w3,
+__global__ __launch_bounds__(256) void paint3_epilogue_kernel(Geom g, const float *__restrict__ disp, const float *__restrict__ w3, float wscale,
                                                               float *__restrict__ mesh, int64_t M, TileLists L,
                                                               unsigned *__restrict__ wmax_bits, int nbk, unsigned *__restrict__ done) {
     __shared__ u64 tile[3 * MCPM_TILE * MCPM_TILE * MCPM_TILE];
     __shared__ int last;
-    if ((int)blockIdx.x < nbk) paint3_bucket_body(g, disp, w3, mesh, M, L, wmax_bits, tile, (int)blockIdx.x, nbk);
+    if ((int)blockIdx.x < nbk) paint3_bucket_body(g, disp, w3, wscale, mesh, M, L, wmax_bits, tile, (int)blockIdx.x, nbk);
     else {
         const int bid = (int)blockIdx.x - nbk, nblk = (int)gridDim.x - nbk;
-        paint_leftover_body<3>(g, disp, w3, 3, 0.f, mesh, M, L, bid, nblk);
+        paint_leftover_body<3>(g, disp, w3, 3, 0.f, wscale, mesh, M, L, bid, nblk);
     }
     // The bucket blocks that found work are the only readers of the max|w| slots in this launch (tile_scale at their top): the
     // last of THEM clears the slots (every block counting on one address cost 30 us: 1088 serialised atomics); with no reader
@@ -1275,7 +1285,7 @@ bool mcpm_paint_tiled(mcpm_plan *p, const float *pos, const float *w, int64_t ws
     const unsigned nlo = 64u;
     if (w) {
         (void)hipMemsetAsync(p->gx_wmax, 0, sizeof(unsigned) * MCPM_FX_SLOTS * MCPM_FX_STRIDE, p->stream);
-        absmax_kernel<<<2048, 256, 0, p->stream>>>(w, wstride, p->Np, p->gx_wmax);
+        absmax_kernel<<<2048, 256, 0, p->stream>>>(w, wstride, p->Np, 1.f, p->gx_wmax);
         // fixed point, and doubles for non-finite weights: the instantiation the weights do not call for returns at once
 #define CALLW(FAST_)                                                                                                                  \
     {                                                                                                                                 \
@@ -1300,7 +1310,7 @@ bool mcpm_paint_tiled(mcpm_plan *p, const float *pos, const float *w, int64_t ws
 }
 
 // Tiled three-component paint; returns false if the caller must paint the components one by one.
-bool mcpm_paint3_tiled(mcpm_plan *p, const float *pos, const float *weights3, float *meshes3, int accumulate) {
+bool mcpm_paint3_tiled(mcpm_plan *p, const float *pos, const float *weights3, float wscale, float *meshes3, int accumulate) {
     if (!tiled_geometry_ok(p, meshes3) || ((p->M * 4) & 15) || p->paint3_variant < 0) return false;
     const Geom &g = p->g;
     const unsigned nb = (unsigned)((g.nx / MCPM_TILE) * (g.ny / MCPM_TILE) * (g.nz / MCPM_TILE));
@@ -1309,24 +1319,24 @@ bool mcpm_paint3_tiled(mcpm_plan *p, const float *pos, const float *weights3, fl
     const TileLists L = tile_lists(p);
     const int fast = tiled_fast(p);
     const unsigned nbk = nb <= 4096u ? (nb < 256u ? nb : 256u) : 1024u;   // see mcpm_paint_tiled
-    if (p->fx_src != weights3) {   // max|w| not left behind by the kernel that produced the weights
+    if (p->fx_src != weights3 || p->fx_scale != wscale) {   // max|wscale w| not left behind by the kernel that produced the weights
         if (!p->fx_clean) (void)hipMemsetAsync(p->fx_wmax, 0, sizeof(unsigned) * MCPM_FX_SLOTS * MCPM_FX_STRIDE, p->stream);
-        absmax_kernel<<<2048, 256, 0, p->stream>>>(weights3, 1, 3 * p->Np, p->fx_wmax);
+        absmax_kernel<<<2048, 256, 0, p->stream>>>(weights3, 1, 3 * p->Np, wscale, p->fx_wmax);
     }
     p->fx_src = nullptr;
     if (p->paint3_variant == 4) {   // fixed-point tiles; the tiles they flag (and every tile if max|w| is unusable) in f64
-        if (fast == 1 && nb <= wide_max_tiles()) paint3_tile_wide_kernel<1><<<nb, 1024, 0, p->stream>>>(g, pos, weights3, meshes3, p->M, accumulate, L, p->fx_wmax, p->fx_redo, 1);
-        else if (fast == 1) paint3_tile_kernel<false, 512, 4, 1><<<nb, 512, 0, p->stream>>>(g, pos, weights3, meshes3, p->M, accumulate, L, p->fx_wmax, p->fx_redo, nullptr, 1);
-        else if (fast == 2) paint3_tile_kernel<false, 512, 4, 2><<<nb, 512, 0, p->stream>>>(g, pos, weights3, meshes3, p->M, accumulate, L, p->fx_wmax, p->fx_redo, nullptr, 1);
-        else paint3_tile_kernel<false, 512, 4><<<nb, 512, 0, p->stream>>>(g, pos, weights3, meshes3, p->M, accumulate, L, p->fx_wmax, p->fx_redo, nullptr, 1);
-        paint3_tile_kernel<true, 1024, 4><<<nb < 256u ? nb : 256u, 1024, 0, p->stream>>>(g, pos, weights3, meshes3, p->M, accumulate, L, p->fx_wmax, nullptr, p->fx_redo, 0);
+        if (fast == 1 && nb <= wide_max_tiles()) paint3_tile_wide_kernel<1><<<nb, 1024, 0, p->stream>>>(g, pos, weights3, wscale, meshes3, p->M, accumulate, L, p->fx_wmax, p->fx_redo, 1);
+        else if (fast == 1) paint3_tile_kernel<false, 512, 4, 1><<<nb, 512, 0, p->stream>>>(g, pos, weights3, wscale, meshes3, p->M, accumulate, L, p->fx_wmax, p->fx_redo, nullptr, 1);
+        else if (fast == 2) paint3_tile_kernel<false, 512, 4, 2><<<nb, 512, 0, p->stream>>>(g, pos, weights3, wscale, meshes3, p->M, accumulate, L, p->fx_wmax, p->fx_redo, nullptr, 1);
+        else paint3_tile_kernel<false, 512, 4><<<nb, 512, 0, p->stream>>>(g, pos, weights3, wscale, meshes3, p->M, accumulate, L, p->fx_wmax, p->fx_redo, nullptr, 1);
+        paint3_tile_kernel<true, 1024, 4><<<nb < 256u ? nb : 256u, 1024, 0, p->stream>>>(g, pos, weights3, wscale, meshes3, p->M, accumulate, L, p->fx_wmax, nullptr, p->fx_redo, 0);
     } else {   // f64 tiles everywhere (A/B and tests)
-        paint3_tile_kernel<true, 1024, 4><<<nb, 1024, 0, p->stream>>>(g, pos, weights3, meshes3, p->M, accumulate, L, p->fx_wmax, nullptr, nullptr, 1);
+        paint3_tile_kernel<true, 1024, 4><<<nb, 1024, 0, p->stream>>>(g, pos, weights3, wscale, meshes3, p->M, accumulate, L, p->fx_wmax, nullptr, nullptr, 1);
     }
     coverage_duty_kernel<<<1024, 256, 0, p->stream>>>(g, pos, L);
     const unsigned nlo = 64u;     // see mcpm_paint_tiled
     // buckets | leftovers in one launch; its last block leaves the max|w| slots zero for the next producer
-    paint3_epilogue_kernel<<<nbk + nlo, 256, 0, p->stream>>>(g, pos, weights3, meshes3, p->M, L, p->fx_wmax, (int)nbk,
+    paint3_epilogue_kernel<<<nbk + nlo, 256, 0, p->stream>>>(g, pos, weights3, wscale, meshes3, p->M, L, p->fx_wmax, (int)nbk,
                                                              (unsigned *)(p->outlier_count + 7));
     p->fx_clean = 1;
     return true;

@@ -59,12 +59,12 @@ __device__ __forceinline__ FxgScale fxg_scale(const unsigned *__restrict__ wmax_
     return r;
 }
 
-__global__ __launch_bounds__(256) void absmax_strided_kernel(const float *__restrict__ w, int64_t stride, int64_t n,
+__global__ __launch_bounds__(256) void absmax_strided_kernel(const float *__restrict__ w, int64_t stride, int64_t n, float wmul,
                                                              unsigned *__restrict__ out) {
     float m = 0.f;
     unsigned bad = 0;
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
-        const unsigned b = __float_as_uint(w[i * stride]) & 0x7fffffffu;
+        const unsigned b = __float_as_uint(wmul * w[i * stride]) & 0x7fffffffu;
         bad |= b >= 0x7f800000u;
         m = fmaxf(m, __uint_as_float(b));
     }
@@ -80,7 +80,7 @@ __global__ __launch_bounds__(64) void fxg_set_unit_kernel(unsigned *__restrict__
 
 template <int MODE, int ORDER>
 __global__ __launch_bounds__(256) void paint_atomic_kernel(Geom g, const float *__restrict__ pos, int64_t n,
-                                                           const float *__restrict__ w, int64_t wstride,
+                                                           const float *__restrict__ w, int64_t wstride, float wmul,
                                                            float *__restrict__ mesh, unsigned long long *__restrict__ acc,
                                                            const unsigned *__restrict__ wmax_bits, int q, int *__restrict__ oob) {
     const FxgScale sc = fxg_scale(wmax_bits, q);
@@ -92,7 +92,7 @@ __global__ __launch_bounds__(256) void paint_atomic_kernel(Geom g, const float *
     float f[3];
     locate<MODE, ORDER>(g, pi, d, c, f);
     if (g.xslab && (c[0] < 0 || c[0] > g.nx - ORDER)) atomicAdd(oob, 1);  // beyond the ghost planes: clamped + counted
-    const float wt = w ? w[pi.i * wstride] : 1.f;   // unweighted: the scalar weight is applied by the flush
+    const float wt = w ? wmul * w[pi.i * wstride] : 1.f;   // unweighted: the scalar weight is applied by the flush
     Stencil<ORDER> s(g, c);
     auto deposit = [&](int64_t cell, float v) {
         if (sc.flt) atomicAdd(mesh + cell, v);
@@ -514,13 +514,16 @@ int mcpm_cell_index(mcpm_plan *p, const float *pos, int64_t n, int mode, int ord
     return MCPM_OK;
 }
 
-int mcpm_paint_f32(mcpm_plan *p, const float *pos, int64_t n, int mode, const float *weights, int64_t wstride,
-                   float wscalar, int order, float *mesh, int accumulate) {
+// wmul: every deposit takes wmul * weights[p] (one f32 product) as its weight; 1 = the public paint.  A scaled paint keeps to the
+// generic kernels (it is the fallback of the scaled three-component paint on meshes the tile kernels do not take).
+static int paint_weighted(mcpm_plan *p, const float *pos, int64_t n, int mode, const float *weights, int64_t wstride,
+                          float wscalar, float wmul, int order, float *mesh, int accumulate) {
     MCPM_TRY(check_particles(p, pos, n, mode, order, "mcpm_paint_f32"));
     MCPM_REQUIRE(p, mesh != nullptr, MCPM_E_ARG, "mcpm_paint_f32: null mesh");
     if (weights && wstride < 1) return mcpm_fail(p, MCPM_E_ARG, "mcpm_paint_f32: wstride must be >= 1");
     StageTimer st_(p, ST_PAINT, (weights ? 16.0 : 12.0) * n + (accumulate ? 8.0 : 4.0) * p->M);
-    if (mode == MCPM_POS_LATTICE && order == 2 && n > 0 && mcpm_paint_tiled(p, pos, weights, wstride, wscalar, mesh, accumulate)) {
+    if (mode == MCPM_POS_LATTICE && order == 2 && n > 0 && (!weights || wmul == 1.f) &&
+        mcpm_paint_tiled(p, pos, weights, wstride, wscalar, mesh, accumulate)) {
         MCPM_LAUNCH_CHECK(p, "paint_tile_kernel");
         return MCPM_OK;
     }
@@ -529,14 +532,14 @@ int mcpm_paint_f32(mcpm_plan *p, const float *pos, int64_t n, int mode, const fl
     MCPM_TRY(fxg_prepare(p));
     if (weights) {
         MCPM_HIP(p, hipMemsetAsync(p->gx_wmax, 0, sizeof(unsigned) * MCPM_FX_SLOTS * MCPM_FX_STRIDE, p->stream));
-        absmax_strided_kernel<<<2048, 256, 0, p->stream>>>(weights, wstride, n, p->gx_wmax);
+        absmax_strided_kernel<<<2048, 256, 0, p->stream>>>(weights, wstride, n, wmul, p->gx_wmax);
     } else {
         fxg_set_unit_kernel<<<1, MCPM_FX_SLOTS, 0, p->stream>>>(p->gx_wmax);
     }
     const int q = fxg_q(n * order * order * order);
     dim3 grid, block;
     if (mode == MCPM_POS_LATTICE) lattice_launch(p->g, grid, block); else flat_launch(n, grid, block);
-#define CALL(MO, OR) paint_atomic_kernel<MO, OR><<<grid, block, 0, p->stream>>>(p->g, pos, n, weights, wstride, mesh, (unsigned long long *)p->gx_acc, p->gx_wmax, q, p->outlier_count + 2)
+#define CALL(MO, OR) paint_atomic_kernel<MO, OR><<<grid, block, 0, p->stream>>>(p->g, pos, n, weights, wstride, wmul, mesh, (unsigned long long *)p->gx_acc, p->gx_wmax, q, p->outlier_count + 2)
     DISPATCH_MODE_ORDER(mode, order, CALL);
 #undef CALL
     paint_fxg_flush_kernel<<<2048, 256, 0, p->stream>>>(p->gx_acc, mesh, p->M, p->gx_wmax, q, weights ? 1.f : wscalar, (((uintptr_t)mesh) & 7) ? 0 : 1);
@@ -544,19 +547,19 @@ int mcpm_paint_f32(mcpm_plan *p, const float *pos, int64_t n, int mode, const fl
     return MCPM_OK;
 }
 
+int mcpm_paint_f32(mcpm_plan *p, const float *pos, int64_t n, int mode, const float *weights, int64_t wstride,
+                   float wscalar, int order, float *mesh, int accumulate) {
+    return paint_weighted(p, pos, n, mode, weights, wstride, wscalar, 1.f, order, mesh, accumulate);
+}
+
 int mcpm_paint3_f32(mcpm_plan *p, const float *pos, int64_t n, int mode, const float *weights3, int order, float *meshes3,
                     int accumulate) {
-    MCPM_TRY(check_particles(p, pos, n, mode, order, "mcpm_paint3_f32"));
-    MCPM_REQUIRE(p, weights3 && meshes3, MCPM_E_ARG, "mcpm_paint3_f32: null buffer");
-    if (mode == MCPM_POS_LATTICE && order == 2 && n > 0) {
-        StageTimer st_(p, ST_PAINT3, 24.0 * n + (accumulate ? 24.0 : 12.0) * p->M);
-        if (mcpm_paint3_tiled(p, pos, weights3, meshes3, accumulate)) {
-            MCPM_LAUNCH_CHECK(p, "paint3_tile_kernel");
-            return MCPM_OK;
-        }
-    }
-    for (int c = 0; c < 3; ++c) MCPM_TRY(mcpm_paint_f32(p, pos, n, mode, weights3 + c, 3, 0.f, order, meshes3 + c * p->M, accumulate));
-    return MCPM_OK;
+    return mcpm_paint3_scaled(p, pos, n, mode, weights3, 1.f, order, meshes3, accumulate);
+}
+
+int mcpm_paint3_scaled_f32(mcpm_plan *p, const float *pos, int64_t n, int mode, const float *weights3, float wscale, int order,
+                           float *meshes3, int accumulate) {
+    return mcpm_paint3_scaled(p, pos, n, mode, weights3, wscale, order, meshes3, accumulate);
 }
 
 int mcpm_read_f32(mcpm_plan *p, const float *pos, int64_t n, int mode, const float *meshes, int ncomp, int order,
@@ -631,7 +634,7 @@ int mcpm_paint_kb_f32(mcpm_plan *p, const float *pos, int64_t n, int mode, const
     MCPM_TRY(fxg_prepare(p));
     if (weights) {
         MCPM_HIP(p, hipMemsetAsync(p->gx_wmax, 0, sizeof(unsigned) * MCPM_FX_SLOTS * MCPM_FX_STRIDE, p->stream));
-        absmax_strided_kernel<<<2048, 256, 0, p->stream>>>(weights, wstride, n, p->gx_wmax);
+        absmax_strided_kernel<<<2048, 256, 0, p->stream>>>(weights, wstride, n, 1.f, p->gx_wmax);
     } else {
         fxg_set_unit_kernel<<<1, MCPM_FX_SLOTS, 0, p->stream>>>(p->gx_wmax);
     }
@@ -803,3 +806,21 @@ int mcpm_kick_drift_layout(mcpm_plan *p, const float *pos_in, const float *vel_i
     return MCPM_OK;
 }
 
+
+// mcpm_paint3_f32 with every weight multiplied by wscale on the way in (mcpm_internal.h): the tiled kernels fold it into their
+// fixed-point scale; the per-component fallback multiplies at the load
+int mcpm_paint3_scaled(mcpm_plan *p, const float *pos, int64_t n, int mode, const float *weights3, float wscale, int order, float *meshes3,
+                       int accumulate) {
+    MCPM_TRY(check_particles(p, pos, n, mode, order, "mcpm_paint3_f32"));
+    MCPM_REQUIRE(p, weights3 && meshes3, MCPM_E_ARG, "mcpm_paint3_f32: null buffer");
+    if (mode == MCPM_POS_LATTICE && order == 2 && n > 0) {
+        StageTimer st_(p, ST_PAINT3, 24.0 * n + (accumulate ? 24.0 : 12.0) * p->M);
+        if (mcpm_paint3_tiled(p, pos, weights3, wscale, meshes3, accumulate)) {
+            MCPM_LAUNCH_CHECK(p, "paint3_tile_kernel");
+            return MCPM_OK;
+        }
+    }
+    if (p->fx_src == weights3) p->fx_src = nullptr;
+    for (int c = 0; c < 3; ++c) MCPM_TRY(paint_weighted(p, pos, n, mode, weights3 + c, 3, 0.f, wscale, order, meshes3 + c * p->M, accumulate));
+    return MCPM_OK;
+}

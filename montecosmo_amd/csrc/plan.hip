@@ -124,6 +124,8 @@ static int plan_create_impl(int nx, int ny, int nz, int px, int py, int pz, int 
     p->paint3_variant = 4;   // fixed-point tiles (particles.hip); 2 = f64 tiles
     p->hint_set = 0;
     p->fb_valid = 0;
+    p->carry_valid = 0;
+    p->fx_scale = 1.f;
     if (const char *e = getenv("MCPM_PAINT3_VARIANT")) p->paint3_variant = atoi(e);
     p->rho = p->spec = p->fmesh = p->spec1 = p->fft_pad = nullptr;
     p->outliers = p->outlier_count = nullptr;
