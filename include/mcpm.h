@@ -502,6 +502,42 @@ int mcpm_power_mult_f32(mcpm_plan *plan, const float *in, float kphys_x, float k
    :862-884 for per-particle scale factors on the light cone).  Tables float64 on the DEVICE, xp ascending. */
 int mcpm_interp_f32(mcpm_plan *plan, const float *x, int64_t n, const double *xp, const double *fp, int ntab, float scale,
                     float *out);
+/* Local primordial non-Gaussianity of the initial field (montecosmo/bricks.py:129-141, add_png):
+     phi = irfftn(safe_div(lin_mesh, t(|k|))),  phi <- phi + fNL (phi^2 - <phi^2>),  out = t(|k|) rfftn(phi)
+   with t the phi -> delta transfer function, linearly interpolated inside the kernels from the DEVICE float64 table (ks
+   ascending, trans; zero outside it) at |k| in h/Mpc (kphys = mesh_shape / box_size).  lin_mesh, out: plain half-spectra;
+   phi (M floats): receives the GAUSSIAN potential, or provides it when phi_given != 0 (then lin_mesh is not read);
+   mean_out (device double, may be NULL) receives <phi^2>, a fixed-order float64 sum: repeat calls are bitwise equal. */
+int mcpm_png_add_f32(mcpm_plan *plan, const float *lin_mesh, float kphys_x, float kphys_y, float kphys_z, const double *ks,
+                     const double *trans, int ntab, float fNL, int phi_given, float *phi, float *out, double *mean_out);
+/* VJP of mcpm_png_add_f32.  lin_mesh, out, phi, mean: the forward call's input and outputs; out_bar: cotangent of out (real-pair
+   convention) -> lin_mesh_bar (real-pair convention, irfftn multiplicity weights), fNL_bar (device double) and trans_bar
+   (device float64 [ntab], OVERWRITTEN): the cotangent of the table entries, from the divide and the multiply, each mode
+   scattered to its two bracketing nodes with the interpolation weights and summed order-independently (ntab <= 2048).
+   phi_bar, lap_phi_bar (real meshes, either may be NULL): cotangents of the Gaussian phi and of lap phi = irfftn(-k^2 lin / t) from
+   their other readers (the bias weights); they join before the single divide by t, so the whole adjoint is three transforms.
+   out_bar NULL (then out, phi, mean may be NULL and phi_bar is required): only phi_bar / lap_phi_bar are pulled back to lin_mesh
+   and the table -- the adjoint of mcpm_png_phi_f32 -- in one or two R2C; fNL_bar = 0. */
+int mcpm_png_add_vjp_f32(mcpm_plan *plan, const float *lin_mesh, const float *out, const float *phi, const double *mean,
+                         float kphys_x, float kphys_y, float kphys_z, const double *ks, const double *trans, int ntab, float fNL,
+                         const float *out_bar, const float *phi_bar, const float *lap_phi_bar, float *lin_mesh_bar, double *fNL_bar,
+                         double *trans_bar);
+/* phi = irfftn(safe_div(lin_mesh, t)) and lap_phi = irfftn(-k^2 safe_div(lin_mesh, t)), k in h/Mpc (bricks.py:415, :439). */
+int mcpm_png_phi_f32(mcpm_plan *plan, const float *lin_mesh, float kphys_x, float kphys_y, float kphys_z, const double *ks,
+                     const double *trans, int ntab, float *phi, float *lap_phi);
+/* out = scale * safe_div(in, t(|k|)) on the half-spectrum: the PNG term of the Kaiser boost (bricks.py:181-183); self-adjoint. */
+int mcpm_png_div_f32(mcpm_plan *plan, const float *in, float kphys_x, float kphys_y, float kphys_z, const double *ks,
+                     const double *trans, int ntab, float scale, float *out);
+/* The five PNG terms of the Lagrangian bias weights (bricks.py:413-441), ADDED to `weights` (the output of mcpm_bias_weights_f32 on
+   the same reads): dr, s2r raw reads of delta and s^2, ph, lp reads of phi and lap phi, png5 = {fNL_bp, fNL_bpd, fNL_bpd2, fNL_bps2,
+   fNL_bn2p} (host).  <d^2> and <ph d> are fixed-order float64 sums; moments_out (device, 2 doubles, may be NULL) receives them. */
+int mcpm_png_weights_f32(mcpm_plan *plan, int64_t n, const float *dr, const float *s2r, const float *ph, const float *lp,
+                         const float *growth, float growth_scalar, const float *png5, float *weights, double *moments_out);
+/* VJP: drb, s2rb, growth_bar (may be NULL) are ADDED to, phb and lpb written; scalars_out (device, 10 doubles) = cotangents of
+   png5, <ph d>_bar, <d^2>_bar, the summed growth cotangent, <d^2>, <ph d>. */
+int mcpm_png_weights_vjp_f32(mcpm_plan *plan, int64_t n, const float *dr, const float *s2r, const float *ph, const float *lp,
+                             const float *growth, float growth_scalar, const float *png5, const float *weights_bar, float *drb,
+                             float *s2rb, float *phb, float *lpb, float *growth_bar, double *scalars_out);
 /* Light-cone LPT (montecosmo/nbody.py:652-666 with a of shape (N,1)): per-particle growth (gtab (n,3) = a2g, a2g2, a2dg2dg at
    a_i) applied to the first / second order forces at the particles: dpos = g F1 - g2 F2, vel = F1 - dg2dg F2 (F2 NULL for
    lpt_order 1).  F2 and F1 are what mcpm_lpt_f32 returns as (dpos, vel) for (g, g2, dg2dg) = (0, -1, 0).  The VJP works in

@@ -65,6 +65,15 @@ SIGNATURES = {
                                             C.POINTER(C.c_float), _f32p, _f32p, _f32p, _f32p, _f32p, _f32p, _f32p, _f32p, C.c_void_p]),
     "mcpm_power_mult_f32": (C.c_int, [C.c_void_p, _f32p, C.c_float, C.c_float, C.c_float, C.c_double, C.c_void_p, C.c_void_p, C.c_int, _f32p]),
     "mcpm_interp_f32": (C.c_int, [C.c_void_p, _f32p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int, C.c_float, _f32p]),
+    "mcpm_png_add_f32": (C.c_int, [C.c_void_p, _f32p, C.c_float, C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.c_int, C.c_float, C.c_int, _f32p,
+                                   _f32p, C.c_void_p]),
+    "mcpm_png_add_vjp_f32": (C.c_int, [C.c_void_p, _f32p, _f32p, _f32p, C.c_void_p, C.c_float, C.c_float, C.c_float, C.c_void_p, C.c_void_p,
+                                       C.c_int, C.c_float, _f32p, _f32p, _f32p, _f32p, C.c_void_p, C.c_void_p]),
+    "mcpm_png_phi_f32": (C.c_int, [C.c_void_p, _f32p, C.c_float, C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.c_int, _f32p, _f32p]),
+    "mcpm_png_div_f32": (C.c_int, [C.c_void_p, _f32p, C.c_float, C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.c_int, C.c_float, _f32p]),
+    "mcpm_png_weights_f32": (C.c_int, [C.c_void_p, C.c_int64, _f32p, _f32p, _f32p, _f32p, _f32p, C.c_float, C.POINTER(C.c_float), _f32p, C.c_void_p]),
+    "mcpm_png_weights_vjp_f32": (C.c_int, [C.c_void_p, C.c_int64, _f32p, _f32p, _f32p, _f32p, _f32p, C.c_float, C.POINTER(C.c_float), _f32p,
+                                           _f32p, _f32p, _f32p, _f32p, _f32p, C.c_void_p]),
     "mcpm_lpt_combine_f32": (C.c_int, [C.c_void_p, _f32p, _f32p, _f32p, C.c_int64, _f32p, _f32p]),
     "mcpm_lpt_combine_vjp_f32": (C.c_int, [C.c_void_p, _f32p, _f32p, _f32p, C.c_int64, _f32p, _f32p, _f32p]),
     "mcpm_observe_pos_f32": (C.c_int, [C.c_void_p, _f32p, _f32p, _f32p, C.c_int64, C.c_int, C.POINTER(C.c_float), C.c_int,

@@ -1,6 +1,10 @@
 """The pieces of montecosmo/bricks.py the PM path touches: cosmology presets (bricks.py:16-47) as a
 duck-typed object (the path reads Omega_m, Omega_de, Omega_k, w0, wa and uses `_workspace`, nbody.py:699)
-and the initial particle lattice (bricks.py:593-603)."""
+and the initial particle lattice (bricks.py:593-603).
+
+Primordial non-Gaussianity (png_type 'fNL' / 'bias'): the transfer table, `add_png`, the five PNG terms of `lagrangian_bias` and
+the `fNL_bias` reparametrisation, each with its VJP.  Out of scope: Eulerian bias, the stochastic term s_ep * phi of the likelihood
+(model.py:894) and PNG on the light-cone and curved-sky forms of the Kaiser model."""
 import os
 
 import numpy as np
@@ -46,7 +50,7 @@ def regular_pos(mesh_shape, ptcl_shape=None):
 
 
 # ------------------------------------------------------------------------------------------------
-# Lagrangian bias expansion (bricks.py:327-443), png_type = None
+# Lagrangian bias expansion (bricks.py:327-443)
 BIAS_KEYS = ("b1", "b2", "bs2", "b3", "bds2", "bs3", "bn2", "bnpar")
 
 
@@ -58,14 +62,17 @@ class BiasCtx:
 def lagrangian_bias(cosmo, pos, a, box_size, lin_mesh, bias, png=None, png_type=None, kpow=None, read_order: int = 2,
                     return_ctx=False):
     """Lagrangian bias expansion weights (bricks.py:327-443): returns (weights (N,), dvel (N,3), phi) like the
-    reference (phi = 0. without primordial non-Gaussianity, the only case built).  `a`: scalar or (N,1) scale
-    factor(s); `pos`: the Lagrangian positions in cell units ((N,3) array or LatticePos); `bias`: dict with the keys
-    BIAS_KEYS (missing keys = 0).  HIP: mcpm_bias_fields_f32 -> mcpm_read_f32 x5 -> mcpm_bias_weights_f32."""
+    reference.  `a`: scalar or (N,1) scale factor(s); `pos`: the Lagrangian positions in cell units ((N,3) array or
+    LatticePos); `bias`: dict with the keys BIAS_KEYS (missing keys = 0).  HIP: mcpm_bias_fields_f32 -> mcpm_read_f32 x5 ->
+    mcpm_bias_weights_f32.
+    png_type None: phi = 0.  Otherwise `png` holds the products 'fNL_bp', 'fNL_bpd' (what `fNL_bias` returns), 'fNL_bpd2',
+    'fNL_bps2', 'fNL_bn2p' (missing = 0); phi = irfftn(lin / t) and lap phi are formed (mcpm_png_phi_f32, two transforms), read
+    at the particles and the five terms of bricks.py:413-441 added (mcpm_png_weights_f32); phi comes back as a device mesh."""
     import ctypes as C
     import torch
     from . import nbody
-    if png_type is not None:
-        raise NotImplementedError("primordial non-Gaussianity terms are not built")
+    if png_type not in (None, "fNL", "bias"):
+        raise ValueError(f"png_type must be None, 'fNL' or 'bias', got {png_type!r}")
     spec = nbody._c64(lin_mesh)
     shape = nbody.ch2rshape(spec.shape)
     plan, p, n, mode = nbody._pos_args(pos, shape)
@@ -102,17 +109,39 @@ def lagrangian_bias(cosmo, pos, a, box_size, lin_mesh, bias, png=None, png_type=
     dvel = torch.empty((n, 3), dtype=torch.float32, device=dev)
     plan.call("mcpm_bias_weights_f32", n, nbody._ptr(reads[0]), nbody._ptr(reads[1]), nbody._ptr(reads[2]), nbody._ptr(reads[3]),
               nbody._ptr(gr), gcs, nbody._ptr(gp), gs, b8, nbody._ptr(w), nbody._ptr(dvel), None)
+    phi, pctx = 0., None
+    if png_type is not None:
+        png = png or {}
+        tab, nt = png_table_dev(cosmo, kpow, dev)
+        pl = torch.empty((2,) + tuple(shape), dtype=torch.float32, device=dev)      # phi, lap phi
+        plan.call("mcpm_png_phi_f32", nbody._ptr(spec), kphys[0], kphys[1], kphys[2], nbody._ptr(tab), tab.data_ptr() + 8 * nt, nt,
+                  nbody._ptr(pl[0]), nbody._ptr(pl[1]))
+        if ident:
+            pr = pl.reshape(2, n)
+        else:
+            pr = torch.empty((2, n), dtype=torch.float32, device=dev)
+            for c in range(2):
+                plan.call("mcpm_read_f32", nbody._ptr(p), n, mode, nbody._ptr(pl[c]), 1, int(read_order), nbody._ptr(pr[c]))
+        b5 = (C.c_float * 5)(*[float(png.get(k, 0.0)) for k in PNG_KEYS[1:]])
+        plan.call("mcpm_png_weights_f32", n, nbody._ptr(reads[0]), nbody._ptr(reads[1]), nbody._ptr(pr[0]), nbody._ptr(pr[1]), nbody._ptr(gp),
+                  gs, b5, nbody._ptr(w), None)
+        phi, pctx = pl[0], BiasCtx(tab=tab, nt=nt, pr=pr, b5=b5)
     if return_ctx:
         ctx = BiasCtx(plan=plan, spec=spec, shape=shape, p=p, n=n, mode=mode, kphys=kphys, reads=reads, gr=gr, gp=gp, gs=gs,
-                      g_shape=g_shape, b8=b8, read_order=int(read_order), gcs=gcs, hess6=hess6)
-        return (w, dvel, 0.), ctx
-    return w, dvel, 0.
+                      g_shape=g_shape, b8=b8, read_order=int(read_order), gcs=gcs, hess6=hess6, png=pctx)
+        return (w, dvel, phi), ctx
+    return w, dvel, phi
 
 
-def lagrangian_bias_vjp(ctx, weights_bar, dvel_bar):
+def lagrangian_bias_vjp(ctx, weights_bar, dvel_bar, defer_phi=False):
     """VJP of lagrangian_bias w.r.t. (lin_mesh, bias, growth factor(s) a2g(a)): returns (lin_mesh_bar [complex64,
     real-pair convention], bias_bar dict, growths_bar [shape of a2g(a)]).  Positions are the fixed Lagrangian
-    lattice of the model (model.py:738), so no position cotangent is formed."""
+    lattice of the model (model.py:738), so no position cotangent is formed.
+    With png_type set three more outputs follow: png_bar (dict: cotangents of the five PNG coefficients), lin_mesh_bar and
+    growths_bar then INCLUDE the PNG terms' share, and trans_bar (float64 numpy, per table node).  <phi delta> is a mean over
+    particles: its cotangent is a fixed-order float64 sum handed back to every particle (mcpm_png_weights_vjp_f32).
+    `defer_phi`: the sixth output is instead the pair of real meshes (phi_bar, lap_phi_bar) and lin_mesh_bar leaves their share
+    out -- the caller hands them to `add_png_vjp`, where they meet add_png's own phi cotangent before the single divide by t."""
     import torch
     from . import nbody
     plan, n, dev = ctx.plan, ctx.n, ctx.spec.device
@@ -130,6 +159,17 @@ def lagrangian_bias_vjp(ctx, weights_bar, dvel_bar):
     plan.call("mcpm_bias_weights_vjp_f32", n, nbody._ptr(r[0]), nbody._ptr(r[1]), nbody._ptr(r[2]), nbody._ptr(r[3]), nbody._ptr(ctx.gr),
               ctx.gcs, nbody._ptr(ctx.gp), ctx.gs, ctx.b8, nbody._ptr(wb), nbody._ptr(vb), nbody._ptr(rb[0]), nbody._ptr(rb[1]),
               nbody._ptr(rb[2]), nbody._ptr(rb[3]), nbody._ptr(grb), nbody._ptr(gbar), nbody._ptr(scal))
+    pc = getattr(ctx, "png", None)
+    if pc is not None:
+        plb = torch.empty((2,) + tuple(ctx.shape), dtype=torch.float32, device=dev)      # cotangents of the phi, lap phi meshes
+        prb = plb.reshape(2, n) if ctx.gcs else torch.empty((2, n), dtype=torch.float32, device=dev)
+        pscal = torch.zeros(10, dtype=torch.float64, device=dev)
+        plan.call("mcpm_png_weights_vjp_f32", n, nbody._ptr(r[0]), nbody._ptr(r[1]), nbody._ptr(pc.pr[0]), nbody._ptr(pc.pr[1]), nbody._ptr(ctx.gp),
+                  ctx.gs, pc.b5, nbody._ptr(wb), nbody._ptr(rb[0]), nbody._ptr(rb[1]), nbody._ptr(prb[0]), nbody._ptr(prb[1]), nbody._ptr(gbar),
+                  nbody._ptr(pscal))
+        if not ctx.gcs:
+            for c in range(2):
+                plan.call("mcpm_paint_f32", nbody._ptr(ctx.p), n, ctx.mode, nbody._ptr(prb[c]), 1, 0.0, ctx.read_order, nbody._ptr(plb[c]), 0)
     if not ctx.gcs:
         for c in range(4):       # adjoint of a read w.r.t. its mesh = a weighted paint
             plan.call("mcpm_paint_f32", nbody._ptr(ctx.p), n, ctx.mode, nbody._ptr(rb[c]), 1, 0.0, ctx.read_order, nbody._ptr(fb[c]), 0)
@@ -142,8 +182,180 @@ def lagrangian_bias_vjp(ctx, weights_bar, dvel_bar):
     s = scal.cpu().numpy()
     bias_bar = {k: float(s[i]) for i, k in enumerate(BIAS_KEYS)}
     # per-particle growth cotangents stay on the device; a scalar one comes back as a float64 array of the shape of a2g(a)
-    growths_bar = gbar.reshape(ctx.g_shape) if gbar is not None else np.asarray(s[8]).reshape(ctx.g_shape)
-    return out, bias_bar, growths_bar
+    if pc is None:
+        growths_bar = gbar.reshape(ctx.g_shape) if gbar is not None else np.asarray(s[8]).reshape(ctx.g_shape)
+        return out, bias_bar, growths_bar
+    ps = pscal.cpu().numpy()
+    growths_bar = gbar.reshape(ctx.g_shape) if gbar is not None else np.asarray(s[8] + ps[7]).reshape(ctx.g_shape)
+    png_bar = {k: float(ps[i]) for i, k in enumerate(PNG_KEYS[1:])}
+    if defer_phi:
+        return out, bias_bar, growths_bar, png_bar, None, (plb[0], plb[1])
+    lb, trans_bar = png_phi_vjp(plan, ctx.spec, ctx.kphys, pc.tab, pc.nt, plb[0], plb[1])
+    return out + lb, bias_bar, growths_bar, png_bar, trans_bar, None
+
+
+# ------------------------------------------------------------------------------------------------
+# Local primordial non-Gaussianity: transfer table, add_png (bricks.py:108-141), bias reparametrisation (bricks.py:466-508)
+RH = 2997.92458      # c / (100 km/s/Mpc) in Mpc/h (jax_cosmo.constants.rh)
+PNG_KEYS = ("fNL", "fNL_bp", "fNL_bpd", "fNL_bpd2", "fNL_bps2", "fNL_bn2p")
+
+
+def trans_phi2delta_table(cosmo, a=1., kpow=None):
+    """The 256-point table (ks [h/Mpc], trans) behind `trans_phi2delta_interp` (bricks.py:108-127): the transfer function from
+    the primordial potential to the linear density at scale factor `a`,
+        trans = 2 rh^2 k^2 T(k) D(a) / D_md / (3 Omega_m),  T = sqrt(P_lin / k^n_s) normalised to 1 at ks[0],
+    with D_md = a2g(a_md) / a_md at z = 10.  P_lin is `kpow` (a (ks, pows) tabulation) or the Eisenstein & Hu table of
+    `power.lin_power_table`; its amplitude cancels in T, so the table does not depend on sigma8.  The look-up is linear and 0
+    outside the table (mcpm_png_add_f32 does it on the device).  Host float64."""
+    from . import nbody, power
+    ks, pows = power.lin_power_table(cosmo) if kpow is None else kpow
+    ks, pows = np.asarray(ks, dtype=np.float64), np.asarray(pows, dtype=np.float64)
+    pow_large = ks ** cosmo.n_s
+    lin_trans = (pows / pow_large / (pows[0] / pow_large[0])) ** .5
+    a_md = 1. / (1. + 10.)
+    growth_md = float(nbody.a2g(cosmo, a_md)) / a_md
+    trans = 2. * RH ** 2 * ks ** 2 * lin_trans * (nbody.a2g(cosmo, a) / growth_md) / (3. * cosmo.Omega_m)
+    return ks, trans
+
+
+_PNG_TABLES = {}
+
+
+def png_table_dev(cosmo, kpow, device):
+    """(device float64 tensor [ks, trans], n): the table of `trans_phi2delta_table` at a = 1, built once per cosmology and power
+    source and kept on the device (a handful of entries: a sampler revisits the same cosmology for every call of one gradient)."""
+    import torch
+    key = (float(cosmo.Omega_c), float(cosmo.Omega_b), float(cosmo.h), float(cosmo.n_s), float(cosmo.Omega_k), float(cosmo.w0),
+           float(cosmo.wa), None if kpow is None else id(kpow[0]), str(device))
+    hit = _PNG_TABLES.get(key)
+    if hit is None or (kpow is not None and hit[2] is not kpow[0]):
+        if len(_PNG_TABLES) > 8:
+            _PNG_TABLES.clear()
+        ks, trans = trans_phi2delta_table(cosmo, kpow=kpow)
+        hit = _PNG_TABLES[key] = (torch.from_numpy(np.concatenate([ks, trans])).to(device), len(ks), None if kpow is None else kpow[0])
+    return hit[0], hit[1]
+
+
+class PngCtx:
+    def __init__(self, **kw):
+        self.__dict__.update(kw)
+
+
+def add_png(cosmo, fNL, lin_mesh, box_size, kpow=None, return_ctx=False, phi=None):
+    """Add local primordial non-Gaussianity to the linear field (bricks.py:129-141):
+        phi = irfftn(safe_div(lin_mesh, t(|k|))),  phi <- phi + fNL (phi^2 - <phi^2>),  returns t(|k|) rfftn(phi)
+    with t = trans_phi2delta_table(cosmo, kpow=kpow) looked up inside the kernels.  `phi`: the Gaussian potential if the caller
+    already holds it (the third return value of `lagrangian_bias` on the same mesh), which saves the divide and one transform.
+    HIP: mcpm_png_add_f32 (png_div_kernel -> C2R -> png_moment_kernel + fold -> png_quad_kernel -> R2C -> png_mult_kernel);
+    <phi^2> is a fixed-order float64 sum, so repeat calls are bitwise equal."""
+    import torch
+    from . import nbody
+    spec = nbody._c64(lin_mesh)
+    shape = nbody.ch2rshape(spec.shape)
+    plan, dev = nbody.get_plan(shape), spec.device
+    kphys = [float(s) / float(b) for s, b in zip(shape, box_size)]
+    tab, nt = png_table_dev(cosmo, kpow, dev)
+    phi_t = nbody._f32(phi, shape) if phi is not None else torch.empty(tuple(shape), dtype=torch.float32, device=dev)
+    out = torch.empty(tuple(spec.shape), dtype=torch.complex64, device=dev)
+    mean = torch.empty(1, dtype=torch.float64, device=dev)
+    plan.call("mcpm_png_add_f32", nbody._ptr(spec), kphys[0], kphys[1], kphys[2], nbody._ptr(tab), tab.data_ptr() + 8 * nt, nt, float(fNL),
+              int(phi is not None), nbody._ptr(phi_t), nbody._ptr(out), nbody._ptr(mean))
+    if return_ctx:
+        return out, PngCtx(plan=plan, spec=spec, out=out, phi=phi_t, mean=mean, kphys=kphys, tab=tab, nt=nt, fNL=float(fNL))
+    return out
+
+
+def png_phi_vjp(plan, spec, kphys, tab, nt, phi_bar, lap_phi_bar=None):
+    """Adjoint of (phi, lap phi) = irfftn((1, -k^2) safe_div(lin_mesh, t)) alone: real-mesh cotangents -> (lin_mesh_bar [complex64,
+    real-pair convention], trans_bar [float64 numpy]).  HIP: mcpm_png_add_vjp_f32 without a cotangent of add_png's output."""
+    import torch
+    from . import nbody
+    lin_bar = torch.empty(tuple(spec.shape), dtype=torch.complex64, device=spec.device)
+    scal = torch.empty(1 + nt, dtype=torch.float64, device=spec.device)
+    plan.call("mcpm_png_add_vjp_f32", nbody._ptr(spec), None, None, None, kphys[0], kphys[1], kphys[2], nbody._ptr(tab), tab.data_ptr() + 8 * nt, nt,
+              0.0, None, nbody._ptr(nbody._f32(phi_bar)), nbody._ptr(None if lap_phi_bar is None else nbody._f32(lap_phi_bar)),
+              nbody._ptr(lin_bar), nbody._ptr(scal), scal.data_ptr() + 8)
+    return lin_bar, scal[1:].cpu().numpy()
+
+
+def add_png_vjp(ctx, out_bar, phi_bar=None, lap_phi_bar=None, sync=True):
+    """VJP of add_png w.r.t. (lin_mesh, fNL, the table entries of t): cotangent of the output (complex, real-pair convention) ->
+    (lin_mesh_bar [complex64, real-pair convention], fNL_bar [float], trans_bar [float64 numpy, one entry per table node]).
+    trans_bar collects both uses of t (the divide and the multiply); contract it with d trans / d theta for a cosmological
+    parameter.  `phi_bar`, `lap_phi_bar`: real-mesh cotangents of the Gaussian phi and of lap phi from their other readers (the
+    bias weights, `lagrangian_bias_vjp(..., defer_phi=True)`); they are folded in before the divide by t.  `sync=False` returns the
+    last two outputs as one device float64 tensor [fNL_bar, trans_bar...] instead of blocking on a copy to the host.
+    HIP: mcpm_png_add_vjp_f32; every sum is order-independent, so repeat calls are bitwise equal."""
+    import torch
+    from . import nbody
+    dev = ctx.spec.device
+    ob = nbody._c64(out_bar, tuple(ctx.spec.shape))
+    lin_bar = torch.empty(tuple(ctx.spec.shape), dtype=torch.complex64, device=dev)
+    scal = torch.empty(1 + ctx.nt, dtype=torch.float64, device=dev)
+    ctx.plan.call("mcpm_png_add_vjp_f32", nbody._ptr(ctx.spec), nbody._ptr(ctx.out), nbody._ptr(ctx.phi), nbody._ptr(ctx.mean), ctx.kphys[0],
+                  ctx.kphys[1], ctx.kphys[2], nbody._ptr(ctx.tab), ctx.tab.data_ptr() + 8 * ctx.nt, ctx.nt, ctx.fNL, nbody._ptr(ob),
+                  nbody._ptr(None if phi_bar is None else nbody._f32(phi_bar)), nbody._ptr(None if lap_phi_bar is None else nbody._f32(lap_phi_bar)),
+                  nbody._ptr(lin_bar), nbody._ptr(scal), scal.data_ptr() + 8)
+    if not sync:
+        return lin_bar, scal
+    s = scal.cpu().numpy()
+    return lin_bar, float(s[0]), s[1:].copy()
+
+
+def bpd_L2E(bpd, bp):
+    """bricks.py:466-467"""
+    return bpd + bp / 2
+
+
+def bpd_E2L(bpd, bp):
+    """bricks.py:469-470"""
+    return bpd - bp / 2
+
+
+def b_phi(b1, p=1., delta_c=1.686):
+    """Primordial scale-dependent bias parameter, 2 delta_c (b1 + 1 - p) for the Lagrangian b1 (bricks.py:472-481)."""
+    return 2 * delta_c * (b1 + 1 - p)
+
+
+def b_phi_delta(b1, b2, delta_c=1.686):
+    """Primordial-density scale-dependent bias parameter, 2 (delta_c b2 - b1) (bricks.py:483-491)."""
+    return 2 * (delta_c * b2 - b1)
+
+
+def fNL_bias(png, bias, p=1., png_type=None):
+    """The reparametrisation of bricks.py:493-508: a copy of `png` whose 'fNL_bp', 'fNL_bpd' are the products the bias expansion
+    uses -- fNL b_phi(b1, p), fNL b_phi_delta(b1, b2) for png_type 'fNL'; fNL * fNL_bp, fNL * fNL_bpd for 'bias'; unchanged for
+    None.  Missing keys count as 0."""
+    png = {k: png.get(k, 0.) for k in PNG_KEYS} | {k: v for k, v in png.items() if k not in PNG_KEYS}
+    fNL, b1, b2 = png["fNL"], bias.get("b1", 0.), bias.get("b2", 0.)
+    if png_type == "fNL":
+        png["fNL_bp"], png["fNL_bpd"] = fNL * b_phi(b1, p), fNL * b_phi_delta(b1, b2)
+    elif png_type == "bias":
+        png["fNL_bp"], png["fNL_bpd"] = fNL * png["fNL_bp"], fNL * png["fNL_bpd"]
+    elif png_type is not None:
+        raise ValueError(f"png_type must be None, 'fNL' or 'bias', got {png_type!r}")
+    return png
+
+
+def fNL_bias_vjp(png, bias, png_bar, p=1., png_type=None, delta_c=1.686):
+    """VJP of fNL_bias: `png_bar` holds the cotangents of the RETURNED dict (missing keys = 0) -> (cotangents of the input png
+    dict, cotangents of bias {'b1', 'b2'}).  'fNL': the cotangents of fNL_bp, fNL_bpd chain to fNL, b1, b2; 'bias': to fNL and
+    the input fNL_bp, fNL_bpd.  The other entries pass through."""
+    out = {k: float(png_bar.get(k, 0.)) for k in PNG_KEYS}
+    bp_bar, bpd_bar = out["fNL_bp"], out["fNL_bpd"]
+    fNL, b1, b2 = png.get("fNL", 0.), bias.get("b1", 0.), bias.get("b2", 0.)
+    bias_bar = {"b1": 0., "b2": 0.}
+    if png_type == "fNL":
+        out["fNL"] += bp_bar * b_phi(b1, p, delta_c) + bpd_bar * b_phi_delta(b1, b2, delta_c)
+        bias_bar["b1"] = fNL * (2 * delta_c * bp_bar - 2 * bpd_bar)
+        bias_bar["b2"] = fNL * 2 * delta_c * bpd_bar
+        out["fNL_bp"] = out["fNL_bpd"] = 0.
+    elif png_type == "bias":
+        out["fNL"] += bp_bar * png.get("fNL_bp", 0.) + bpd_bar * png.get("fNL_bpd", 0.)
+        out["fNL_bp"], out["fNL_bpd"] = fNL * bp_bar, fNL * bpd_bar
+    elif png_type is not None:
+        raise ValueError(f"png_type must be None, 'fNL' or 'bias', got {png_type!r}")
+    return out, bias_bar
 
 
 # ------------------------------------------------------------------------------------------------

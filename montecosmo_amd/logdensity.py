@@ -140,7 +140,10 @@ class FieldLevelLogDensity:
     count_obs: observed count mesh, real, fwd.final_shape
     latents  : name -> dict(loc, scale, loc_fid, scale_fid) for every SAMPLED scalar base parameter (unbounded Normal)
     fixed    : name -> value for the base parameters that are not sampled; between them `latents` and `fixed` must
-               provide Omega_m, sigma8, the eight bias parameters, ngbars, s_e, s_ed, s_e2
+               provide Omega_m, sigma8, the eight bias parameters, ngbars, s_e, s_ed, s_e2.  The six PNG parameters
+               (bricks.PNG_KEYS: fNL, fNL_bp, fNL_bpd, fNL_bpd2, fNL_bps2, fNL_bn2p) may appear in either; a missing one is
+               fixed at 0.  They reach the model only when `fwd.png_type` is set.  The stochastic term s_ep * phi of the
+               reference's likelihood (model.py:894) is not built.
     make_cosmo(base) -> cosmology object (default: Planck18 with Omega_c = Omega_m - Omega_b and sigma8)
     """
 
@@ -384,9 +387,10 @@ class FieldLevelLogDensity:
         white = (nbody.rfftn(w) if self.precond == "real" else rg2cgh(w)) * self.transfer
         cosmo = self.make_cosmo(base)
         bias = {k: base[k] for k in bricks.BIAS_KEYS}
+        png = {k: float(base.get(k, 0.0)) for k in bricks.PNG_KEYS} if fwd.png_type is not None else None
         # Omega_m sampled: the forward model makes the two evaluations of the growth-table Jacobian as soon as it has queued its kernels
         fwd.cosmo_fd_params = ("Omega_m",) if "Omega_m" in self.latents else None
-        gxy, ctx = fwd.evolve(cosmo, bias, white, return_ctx=True)
+        gxy, ctx = fwd.evolve(cosmo, bias, white, return_ctx=True) if png is None else fwd.evolve(cosmo, bias, white, png=png, return_ctx=True)
         # likelihood (model.py:852-866, :893-908): per-cell count multiplier from the shells' mean densities
         rcounts = np.atleast_1d(np.asarray(base["ngbars"], dtype=np.float64)) * fwd.cell_length ** 3
         rc_ext = torch.from_numpy(np.append(rcounts, 1.0).astype(np.float32)).to(gxy.device)
@@ -459,7 +463,9 @@ class FieldLevelLogDensity:
         grad["white_mesh_"] = wbar - (w if self.scale is None else w / self.scale ** 2)
         if ngb_bar is not None:
             grad["ngbars_"] = ngb_prior_grad + ngb_bar * ngb_dbase
-        base_bar = dict(g["bias"])
+        base_bar = {k: 0.0 for k in bricks.PNG_KEYS}      # (without png_type the model does not read them)
+        base_bar.update(g.get("png", {}))
+        base_bar.update(g["bias"])
         base_bar.update(stoch_bar)
         base_bar["sigma8"] = g["sigma8"]
         if "Omega_m" in self.latents:

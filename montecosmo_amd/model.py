@@ -1,9 +1,11 @@
 """`FieldLevelModel.evolve` (montecosmo/model.py:686-838) on the HIP path, with its hand-written reverse sweep.
 
 Built branch: bias_type 'lagrangian', evolution 'lpt' (scalar a_obs or light cone), 'nbody' (scalar a_obs, as the
-reference asserts) or 'kaiser' (flat sky, scalar a_obs: bricks.py:170-198), png_type None, ap_auto None, kernel_type 'rectangular', linear power from a table (`lin_kpow`,
+reference asserts) or 'kaiser' (flat sky, scalar a_obs: bricks.py:170-198), png_type None, 'fNL' or 'bias' (local primordial
+non-Gaussianity: `evolve(..., png={'fNL': ..., ...})`, model.py:688, :751-758), ap_auto None, kernel_type 'rectangular', linear power from a table (`lin_kpow`,
 bricks.py:75-77) or, with lin_kpow = None, from the Eisenstein-Hu fit of the current cosmology (bricks.py:72-74; power.py).
-Priors, likelihood and samplers: logdensity.py, samplers.py.
+Priors, likelihood and samplers: logdensity.py, samplers.py.  Not built: Eulerian bias, the stochastic term s_ep * phi of the
+likelihood (model.py:894), PNG on the light-cone / curved-sky Kaiser forms.
 
     fwd = FieldLevelForward(final_shape=(64, 64, 64), cell_length=20., box_center=(0, 0, 2000.), evolution='nbody',
                             a_obs=0.7, lin_kpow=(ks, pows))
@@ -11,7 +13,8 @@ Priors, likelihood and samplers: logdensity.py, samplers.py.
     grads = fwd.evolve_vjp(ctx, gxy_mesh_bar)      # {'white_mesh': ..., 'bias': {...}, 'sigma8': ..., 'growth': ...}
 
 Chain (every arrow is a HIP kernel sequence of libmcpm.so, each with its VJP):
-white_mesh -white2lin-> init_mesh -chreshape-> evol mesh -lagrangian_bias-> (weights, dvel); -lpt | nbody_bf-> (pos, vel)
+white_mesh -white2lin-> init_mesh -chreshape-> evol mesh -lagrangian_bias-> (weights, dvel, phi); [-add_png(phi)-> -chreshape to
+init_shape and back->] -lpt | nbody_bf-> (pos, vel)
 -observe_pos (los, rsd)-> pos on init_shape -nufft(weights, paint_shape)-> spectrum -chreshape-> -irfftn-> gxy_mesh.
 """
 from __future__ import annotations
@@ -32,12 +35,15 @@ class FieldLevelForward:
     def __init__(self, final_shape=(64, 64, 64), cell_length=20., box_center=(0., 0., 0.), box_rotvec=(0., 0., 0.),
                  evolution='lpt', nbody_a_start=0., nbody_n_steps=10, lpt_order=2, paint_order=2, paint_deconv=True,
                  init_oversamp=3 / 2, evol_oversamp=7 / 4, ptcl_oversamp=7 / 4, paint_oversamp=7 / 4, interlace_order=2,
-                 a_obs=None, curved_sky=True, lin_kpow=None):
+                 a_obs=None, curved_sky=True, lin_kpow=None, png_type=None):
         if evolution not in ('kaiser', 'lpt', 'nbody'):
             raise ValueError("evolution must be 'kaiser', 'lpt' or 'nbody'")
         if evolution == 'kaiser' and (curved_sky or a_obs is None):
             raise NotImplementedError("the Kaiser model is built for the flat sky at fixed a_obs (bricks.py:194-198); "
                                       "its curved-sky / light-cone forms (bricks.py:200-231) are not")
+        if png_type not in (None, 'fNL', 'bias'):
+            raise ValueError("png_type must be None, 'fNL' or 'bias'")
+        self.png_type = png_type
         self.final_shape = tuple(int(s) for s in final_shape)
         self.cell_length = float(cell_length)
         self.box_center = np.asarray(box_center, dtype=np.float64)
@@ -132,14 +138,25 @@ class FieldLevelForward:
             self._mu2 = torch.from_numpy(np.ascontiguousarray(mu2, dtype=np.float32)).to(device)
         return self._mu2
 
-    def _kaiser(self, cosmo, bias, white, evol_k, return_ctx):
+    def _png_div(self, spec, cosmo, scale):
+        """scale * safe_div(spec, t(|k|)) on the evolution mesh, t from `lin_kpow` as the reference's Kaiser model takes it."""
+        tab, nt = bricks.png_table_dev(cosmo, self.lin_kpow, spec.device)
+        out, kp = torch.empty_like(spec), self._kphys(self.evol_shape)
+        nbody.get_plan(self.evol_shape).call("mcpm_png_div_f32", nbody._ptr(spec), kp[0], kp[1], kp[2], nbody._ptr(tab), tab.data_ptr() + 8 * nt, nt,
+                                             float(scale), nbody._ptr(out))
+        return out
+
+    def _kaiser(self, cosmo, bias, white, evol_k, return_ctx, png=None):
         D, f = float(nbody.a2g(cosmo, self.a_obs)), float(nbody.a2f(cosmo, self.a_obs))
         mu2 = self._mu2_mesh(evol_k.device)
         boost = D * ((1.0 + float(bias["b1"])) + f * mu2)                 # b1E = 1 + b1 (bricks.py:454)
-        gxy = nbody.irfftn(evol_k * boost) + 1.0
+        gxy_k = evol_k * boost
+        if png is not None:      # boost += safe_div(fNL_bp, t) (bricks.py:181-183)
+            gxy_k = gxy_k + self._png_div(evol_k, cosmo, png["fNL_bp"])
+        gxy = nbody.irfftn(gxy_k) + 1.0
         cosmo._workspace = {}
         if return_ctx:
-            return gxy, EvolveCtx(cosmo=cosmo, white=white, evol_k=evol_k, kaiser=(D, f, float(bias["b1"]), boost))
+            return gxy, EvolveCtx(cosmo=cosmo, white=white, evol_k=evol_k, kaiser=(D, f, float(bias["b1"]), boost), png=png, bias=bias)
         return gxy
 
     def _kaiser_vjp(self, ctx, gxy_bar):
@@ -151,35 +168,64 @@ class FieldLevelForward:
         prod = kb.conj() * ctx.evol_k
         c0 = float(prod.real.double().sum())                              # d/d(D b1E)
         c1 = float((prod.real * self._mu2_mesh(kb.device)).double().sum())    # d/d(D f)
-        init_b = chreshape_vjp(kb * boost, r2chshape(self.init_shape))
-        white_b = self._power_mult(init_b, cosmo)
-        s8b = float((init_b.conj() * self._power_mult(ctx.white, cosmo, sigma8=1.0)).real.sum().item())
+        evol_b, extra = kb * boost, {}
         bias_bar = {k: 0.0 for k in bricks.BIAS_KEYS}
         bias_bar["b1"] = D * c0
+        if getattr(ctx, "png", None) is not None:
+            # the PNG term is fNL_bp phi in real space, phi = irfftn(evol_k / t): phi_bar = fNL_bp gxy_bar, pulled back to evol_k and the table
+            bp_bar = float((kb.conj() * self._png_div(ctx.evol_k, cosmo, 1.0)).real.double().sum())
+            tab, nt = bricks.png_table_dev(cosmo, self.lin_kpow, kb.device)
+            lb, trans_bar = bricks.png_phi_vjp(nbody.get_plan(self.evol_shape), ctx.evol_k, self._kphys(self.evol_shape), tab, nt,
+                                               gb * float(ctx.png["fNL_bp"]))
+            evol_b = evol_b + lb
+            png_bar, bb = bricks.fNL_bias_vjp(ctx.png_in, ctx.bias, {"fNL_bp": bp_bar}, p=1., png_type=self.png_type)
+            bias_bar["b1"] += bb["b1"]
+            bias_bar["b2"] += bb["b2"]
+            extra = {"png": png_bar, "trans_bar": trans_bar}
+        init_b = chreshape_vjp(evol_b, r2chshape(self.init_shape))
+        white_b = self._power_mult(init_b, cosmo)
+        s8b = float((init_b.conj() * self._power_mult(ctx.white, cosmo, sigma8=1.0)).real.sum().item())
         return {"white_mesh": white_b, "bias": bias_bar, "sigma8": s8b, "init_bar": init_b,
-                "kaiser": {"g": (1.0 + b1) * c0 + f * c1, "f": D * c1}}
+                "kaiser": {"g": (1.0 + b1) * c0 + f * c1, "f": D * c1}, **extra}
 
     # ---- forward -----------------------------------------------------------------------------------------
-    def evolve(self, cosmo, bias, white_mesh, return_ctx=False):
+    def evolve(self, cosmo, bias, white_mesh, png=None, return_ctx=False):
         """cosmo: duck-typed cosmology (Omega_m, Omega_de, Omega_k, w0, wa, sigma8, _workspace); bias: dict of the
         Lagrangian bias parameters; white_mesh: complex half-spectrum of shape r2chshape(init_shape) (what
-        samp2base_mesh returns).  Returns gxy_mesh (paint_shape, float32 device tensor) = 1 + delta_obs."""
+        samp2base_mesh returns); png: dict with the keys bricks.PNG_KEYS (missing = 0), read only when the model's png_type is
+        set.  Returns gxy_mesh (paint_shape, float32 device tensor) = 1 + delta_obs.
+        With png_type (model.py:688, :751-758): fNL_bias -> bias weights from the GAUSSIAN evolution mesh -> add_png on it (phi is
+        handed over from the bias step: three extra transforms in all) -> chreshape to init_shape and back, which cuts the modes
+        phi^2 filled above the initial Nyquist -> lpt / nbody.  As in the reference, the transfer table of these two steps is the
+        Eisenstein-Hu one (model.py:751, :757 pass no kpow); the Kaiser model's follows `lin_kpow` (model.py:695)."""
         white = nbody._c64(white_mesh, r2chshape(self.init_shape))
         init_k = self._power_mult(white, cosmo)
         evol_k = chreshape(init_k, r2chshape(self.evol_shape))
+        png_in = png
+        png = bricks.fNL_bias(png or {}, bias, p=1., png_type=self.png_type) if self.png_type is not None else None
         if self.evolution == 'kaiser':      # gxy_mesh lives on the evolution mesh (model.py:690-696: no oversampling needed)
-            return self._kaiser(cosmo, bias, white, evol_k, return_ctx)
+            res = self._kaiser(cosmo, bias, white, evol_k, return_ctx, png=png)
+            if return_ctx:
+                res[1].png_in = png_in or {}
+            return res
         pos0 = getattr(self, "_pos0", None)      # the undisplaced lattice: built once (201 MB of zeros per call at 256^3 otherwise); never written to
         if pos0 is None:
             pos0 = self._pos0 = nbody.LatticePos.regular(self.evol_shape, self.ptcl_shape)
         a = self._scale_factors(cosmo)
-        (w, dvel, _), bctx = bricks.lagrangian_bias(cosmo, pos0, a, self.box_size, evol_k, bias, read_order=1, return_ctx=True)
+        lin_k, actx = evol_k, None
+        if png is None:
+            (w, dvel, _), bctx = bricks.lagrangian_bias(cosmo, pos0, a, self.box_size, evol_k, bias, read_order=1, return_ctx=True)
+        else:
+            (w, dvel, phi), bctx = bricks.lagrangian_bias(cosmo, pos0, a, self.box_size, evol_k, bias, png=png, png_type=self.png_type,
+                                                          read_order=1, return_ctx=True)
+            lin_k, actx = bricks.add_png(cosmo, png["fNL"], evol_k, self.box_size, return_ctx=True, phi=phi)
+            lin_k = chreshape(chreshape(lin_k, r2chshape(self.init_shape)), r2chshape(self.evol_shape))      # model.py:758
         cosmo._workspace = {}                                                        # model.py:762, :769
         if self.evolution == 'lpt':
-            (dpos, vel), lctx = nbody.lpt(cosmo, evol_k, pos0, a, lpt_order=self.lpt_order, read_order=1, return_ctx=True)
+            (dpos, vel), lctx = nbody.lpt(cosmo, lin_k, pos0, a, lpt_order=self.lpt_order, read_order=1, return_ctx=True)
             pos, nctx = pos0 + dpos, lctx      # (the LPT context rides in the N-body context's slot)
         else:
-            (pos, vel), nctx = nbody.nbody_bf(cosmo, evol_k, pos0, a0=self.nbody_a_start, a1=a, n_steps=self.nbody_n_steps,
+            (pos, vel), nctx = nbody.nbody_bf(cosmo, lin_k, pos0, a0=self.nbody_a_start, a1=a, n_steps=self.nbody_n_steps,
                                               paint_order=self.paint_order, lpt_order=self.lpt_order, return_ctx=True,
                                               lattice_out=True)
             vel = vel.reshape(-1, 3)
@@ -194,14 +240,16 @@ class FieldLevelForward:
         gxy = nbody.irfftn(gxy_k)
         if return_ctx:
             return gxy, EvolveCtx(cosmo=cosmo, white=white, evol_k=evol_k, pos0=pos0, a=a, bctx=bctx, nctx=nctx, octx=octx,
-                                  pos_c=pos_c, w=w, jac=jac, scalar_fd=fd)
+                                  pos_c=pos_c, w=w, jac=jac, scalar_fd=fd, lin_k=lin_k, actx=actx, png=png, png_in=png_in or {}, bias=bias)
         return gxy
 
     # ---- reverse sweep -----------------------------------------------------------------------------------
     def evolve_vjp(self, ctx, gxy_bar):
         """Cotangent of gxy_mesh (real, paint_shape) -> {'white_mesh': complex64 cotangent (real-pair convention),
         'bias': dict, 'sigma8': float, 'growth': cotangents of the growth scalars (see nbody.lpt_vjp / nbody_bf_vjp),
-        'bias_growth': cotangent(s) of a2g(a) through the bias weights, 'gf': cotangent of a2g(a_obs) a2f(a_obs) through rsd}."""
+        'bias_growth': cotangent(s) of a2g(a) through the bias weights, 'gf': cotangent of a2g(a_obs) a2f(a_obs) through rsd}.
+        With png_type also 'png': cotangents of the six entries of the `png` dict given to evolve (the fNL_bias reparametrisation
+        chained back, its b1 / b2 share added to 'bias'), and 'trans_bar': cotangent of the transfer table's entries (cosmo_vjp)."""
         if self.evolution == 'kaiser':
             return self._kaiser_vjp(ctx, gxy_bar)
         cosmo = ctx.cosmo
@@ -214,18 +262,30 @@ class FieldLevelForward:
         pb, wb = nbody.nufft_vjp(ctx.pos_c, self.init_shape, ctx.w, kb, self.paint_order, self.interlace_order, self.paint_deconv,
                                  paint_shape=self.paint_shape)
         xb, vb, dvb, gfb = bricks.observe_pos_vjp(ctx.octx, pb)
-        mesh_b, bias_bar, bg_bar = bricks.lagrangian_bias_vjp(ctx.bctx, wb, dvb)
+        extra = {}
+        if ctx.actx is None:
+            mesh_b, bias_bar, bg_bar = bricks.lagrangian_bias_vjp(ctx.bctx, wb, dvb)
+        else:
+            mesh_b, bias_bar, bg_bar, png_bar, _, (phb, lpb) = bricks.lagrangian_bias_vjp(ctx.bctx, wb, dvb, defer_phi=True)
         if self.evolution == 'lpt':
-            mb, growth = nbody.lpt_vjp(cosmo, ctx.evol_k, ctx.pos0, ctx.a, xb, vb, lpt_order=self.lpt_order, ctx=ctx.nctx)
+            mb, growth = nbody.lpt_vjp(cosmo, ctx.lin_k, ctx.pos0, ctx.a, xb, vb, lpt_order=self.lpt_order, ctx=ctx.nctx)
         else:
             mb, growth = nbody.nbody_bf_vjp(ctx.nctx, xb, vb)
+        if ctx.actx is not None:
+            # three transforms: the cotangents of phi (bias weights and add_png) and of lap phi meet in k-space before the one divide by t
+            ob = chreshape_vjp(chreshape_vjp(mb, r2chshape(self.init_shape)), r2chshape(self.evol_shape))
+            mb, png_bar["fNL"], trans_bar = bricks.add_png_vjp(ctx.actx, ob, phi_bar=phb, lap_phi_bar=lpb)
+            png_bar, bb = bricks.fNL_bias_vjp(ctx.png_in, ctx.bias, png_bar, p=1., png_type=self.png_type)
+            bias_bar["b1"] += bb["b1"]
+            bias_bar["b2"] += bb["b2"]
+            extra = {"png": png_bar, "trans_bar": trans_bar}
         mesh_b = mesh_b + mb
         init_b = chreshape_vjp(mesh_b, r2chshape(self.init_shape))
         white_b = self._power_mult(init_b, cosmo)
         # d/d sigma8: init_mesh is linear in sigma8
         s8b = float((init_b.conj() * self._power_mult(ctx.white, cosmo, sigma8=1.0)).real.sum().item())
         return {"white_mesh": white_b, "bias": bias_bar, "sigma8": s8b, "growth": growth, "bias_growth": bg_bar, "gf": gfb,
-                "init_bar": init_b, "obs_bar": pb if self.a_obs is None else None}
+                "init_bar": init_b, "obs_bar": pb if self.a_obs is None else None, **extra}
 
     def cosmo_vjp(self, ctx, grads, params=("Omega_m",), rel_eps=1e-5):
         """Chains the growth cotangents of `evolve_vjp` to cosmological parameters (fixed a_obs): besides sigma8 and the
@@ -267,11 +327,26 @@ class FieldLevelForward:
                 vals.append(cached[len(vals)] if cached is not None else scalars(c))
                 if self.lin_kpow is None:      # the Eisenstein-Hu shape moves with the cosmology: init_mesh = white sqrt(P)
                     inits.append(self._power_mult(ctx.white, c))
-            out[name] = float(np.dot(bars, (vals[0] - vals[1]) / (2 * h)))
+            out[name] = float(np.dot(bars, (vals[0] - vals[1]) / (2 * h))) + self._trans_term(cosmo, grads, attr, base, h)
             if inits:
                 out[name] += float((grads["init_bar"].conj() * (inits[0] - inits[1])).real.sum().item()) / (2 * h)
         cosmo._workspace = {}
         return out
+
+    def _trans_term(self, cosmo, grads, attr, base, h):
+        """<trans_bar, d trans / d theta> for the phi -> delta transfer table (png_type set), the table Jacobian by the same host
+        central difference as the growth tables.  (sigma8 cancels in the table, so its derivative has no such term.)"""
+        import copy
+        if grads.get("trans_bar") is None:
+            return 0.0
+        kpow = self.lin_kpow if self.evolution == 'kaiser' else None
+        tr = []
+        for sgn in (+1, -1):
+            c = copy.copy(cosmo)
+            c._workspace = {}
+            setattr(c, attr, base + sgn * h)
+            tr.append(bricks.trans_phi2delta_table(c, kpow=kpow)[1])
+        return float(np.dot(grads["trans_bar"], (tr[0] - tr[1]) / (2 * h)))
 
     def _cosmo_scalars(self, c):
         """The host float64 scalars through which a cosmology enters `evolve` at fixed a_obs (see cosmo_vjp)."""
@@ -364,6 +439,7 @@ class FieldLevelForward:
                 if self.lin_kpow is None:
                     inits.append(self._power_mult(ctx.white, c))
             out[name] = float(sum(np.dot(bars[k], (tabs[0][k] - tabs[1][k]) / (2 * h)) for k in self._LC_TABLES))
+            out[name] += self._trans_term(cosmo, grads, attr, base, h)
             if inits:
                 out[name] += float((grads["init_bar"].conj() * (inits[0] - inits[1])).real.sum().item()) / (2 * h)
         return out

@@ -25,7 +25,7 @@ import numpy as np
 
 MANDATORY = ("cell_length", "box_center", "box_rotvec", "init_oversamp", "paint_oversamp", "cosmo_fid", "count_mesh")
 OPTIONAL = ("selec_mesh", "mask_mesh", "n_tracers", "n_randoms", "a_obs", "curved_sky", "paint_order", "interlace_order",
-            "paint_deconv", "kernel_type", "cell_budget", "padding", "lin_kpow", "white_mesh", "white_fake")
+            "paint_deconv", "kernel_type", "cell_budget", "padding", "lin_kpow", "white_mesh", "white_fake", "png_type")
 
 
 def _flatten(d, prefix=""):
@@ -121,6 +121,8 @@ def model_arguments(reg, **overrides):
     for k in ("a_obs", "curved_sky", "paint_order", "interlace_order", "paint_deconv"):
         if k in reg:
             fwd[k] = reg[k]
+    if reg.get("png_type") not in (None, "None"):      # 'fNL' or 'bias' (model.py:84); absent or None: no primordial non-Gaussianity
+        fwd["png_type"] = str(reg["png_type"])
     if reg.get("kernel_type", "rectangular") != "rectangular":
         raise NotImplementedError("FieldLevelForward paints with kernel_type='rectangular' (nbody.paint itself takes 'kaiser_bessel')")
     if reg.get("lin_kpow") is not None:
