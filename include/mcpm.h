@@ -67,7 +67,7 @@ int mcpm_plan_slab_oob(mcpm_plan *plan, int64_t *count);
 int mcpm_plan_destroy(mcpm_plan *plan);
 const char *mcpm_last_error(const mcpm_plan *plan); /* plan may be NULL: last error of a failed create */
 /* ABI revision string; the Python loader (montecosmo_amd/_lib.py) refuses a library that reports another one. */
-#define MCPM_ABI_VERSION "mcpm 0.8 (gfx950)"
+#define MCPM_ABI_VERSION "mcpm 0.9 (gfx950)"
 const char *mcpm_version(void);
 /* Tiled CIC paints (montecosmo_amd/csrc/paint_tiled.hip).  A tile's window is a box of lattice points per axis -- chosen on the device
    for every input and every tile from the displacement field around it, or (16 + 2 halo + 1)^3 around the tile's bulk displacement when a
@@ -546,8 +546,8 @@ int mcpm_lpt_combine_f32(mcpm_plan *plan, const float *F1, const float *F2, cons
 int mcpm_lpt_combine_vjp_f32(mcpm_plan *plan, const float *F1, const float *F2, const float *gtab, int64_t n, float *xb, float *vb,
                              float *gtab_bar);
 
-/* Evolved particles -> redshift-space positions on the paint mesh (montecosmo/model.py:780-797 without Alcock-Paczynski;
-   bricks.py:628-662 cell <-> physical maps, :750-768 line of sight and scale factor, :791-803 rsd), one fused pass.
+/* Evolved particles -> redshift-space positions on the paint mesh (montecosmo/model.py:780-797; the Alcock-Paczynski step of
+   :787-794 is in the *_ap_* variants below; bricks.py:628-662 cell <-> physical maps, :750-768 line of sight and scale factor, :791-803 rsd), one fused pass.
    The plan's mesh is the evolution mesh.  geom (host, 19 floats) = box_rot matrix R[9] (row major, apply(x) = R x),
    box_size[3], box_center[3], paint_shape[3], g(a_obs) f(a_obs).  flags: bit 0 = curved sky, bit 1 = light cone; on the
    light cone `tables` (DEVICE float64) = chi ascending [nchi], a(chi) [nchi], a [ngrow], g [ngrow], f [ngrow].
@@ -560,6 +560,34 @@ int mcpm_observe_pos_f32(mcpm_plan *plan, const float *pos, const float *vel, co
 int mcpm_observe_pos_vjp_f32(mcpm_plan *plan, const float *pos, const float *vel, const float *dvel, int64_t n, int pos_mode,
                              const float *geom, int flags, const double *tables, int nchi, int ngrow, const float *out_bar,
                              float *pos_bar, float *vel_bar, float *dvel_bar, double *gf_bar);
+/* The same pass with the Alcock-Paczynski remapping (model.py:787-794; bricks.py:795-814 ap_auto, :848-857 ap_param, :708-732) between
+   the RSD step and phys2cell_pos, at no extra pass over the particles.  With P' the physical redshift-space position:
+   MCPM_AP_AUTO:  P'' = alpha P', alpha = safe_div(rho, r'), rho = a2chi(cosmo_fid, chi2a(cosmo, r')), r' = |P'| (curved sky) or
+                  |P' . l_flat| (flat sky; all three components are scaled).  Two clamped linear look-ups in ap_tables (DEVICE float64) =
+                  chi ascending [nap], a(chi) [nap] of the SAMPLED cosmology, then a ascending [nfid], chi_fid(a) [nfid] of the FIDUCIAL
+                  one.  On the light cone the first pair must be the chi, a(chi) of `tables` (nap = nchi).  alpha_iso / alpha_ap unused.
+   MCPM_AP_PARAM: curved sky P'' = alpha_iso P'; flat sky the components along / across l_flat are scaled by alpha_par = alpha_iso
+                  alpha_ap^(2/3) and alpha_perp = alpha_iso alpha_ap^(-1/3) (alpha_ap > 0).  ap_tables unused (NULL, 0, 0).
+   MCPM_AP_NONE:  the functions above, bit for bit (they are this case).
+   The small displacement P'' - P' is formed on its own (auto: (rho - r') / r' in float64 from the tables) and added to the output,
+   which keeps the displacement-from-lattice encoding.  The VJP adds the path through r' to pos_bar / vel_bar / dvel_bar and returns
+   alpha_bar (device double[2]: cotangents of alpha_iso, alpha_ap; fixed-order sums; 0 for MCPM_AP_AUTO, alpha_ap_bar = 0 on a curved
+   sky).  The tables VJP adds the cotangent of the chi NODES of chi2a(cosmo, r') (the fiducial table is constant) to chi_bar; with
+   MCPM_AP_AUTO it also runs WITHOUT the light-cone bit, and table_bar is then chi_bar[nap] alone. */
+#define MCPM_AP_NONE 0
+#define MCPM_AP_AUTO 1
+#define MCPM_AP_PARAM 2
+int mcpm_observe_pos_ap_f32(mcpm_plan *plan, const float *pos, const float *vel, const float *dvel, int64_t n, int pos_mode,
+                            const float *geom, int flags, const double *tables, int nchi, int ngrow, int ap_mode, double alpha_iso,
+                            double alpha_ap, const double *ap_tables, int nap, int nfid, float *out);
+int mcpm_observe_pos_ap_vjp_f32(mcpm_plan *plan, const float *pos, const float *vel, const float *dvel, int64_t n, int pos_mode,
+                                const float *geom, int flags, const double *tables, int nchi, int ngrow, int ap_mode, double alpha_iso,
+                                double alpha_ap, const double *ap_tables, int nap, int nfid, const float *out_bar, float *pos_bar,
+                                float *vel_bar, float *dvel_bar, double *gf_bar, double *alpha_bar);
+int mcpm_observe_pos_ap_tables_vjp_f32(mcpm_plan *plan, const float *pos, const float *vel, const float *dvel, int64_t n, int pos_mode,
+                                       const float *geom, int flags, const double *tables, int nchi, int ngrow, int ap_mode,
+                                       double alpha_iso, double alpha_ap, const double *ap_tables, int nap, int nfid,
+                                       const float *out_bar, double *table_bar);
 /* Light cone (a_obs = None, the reference's default: model.py:62): how the cosmology enters the per-particle look-ups.
    The scale factor of a particle is chi2a(distance) and its growth quantities are table look-ups at that scale factor
    (model.py:740-742 -> bricks.py:750-768 los_scalefactor_pos -> nbody.py:862-884 chi2a, :748-808 a2g ...; again at the evolved

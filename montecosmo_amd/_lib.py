@@ -13,6 +13,7 @@ LIB_PATH = os.environ.get("MCPM_LIB") or os.path.join(_HERE, "libmcpm.so")      
 
 OK = 0
 POS_ABSOLUTE, POS_LATTICE = 0, 1
+AP_NONE, AP_AUTO, AP_PARAM = 0, 1, 2
 FD_INF, FD_2, FD_4 = 0, 2, 4
 
 _f32p = C.c_void_p  # device pointers travel as integers
@@ -83,6 +84,14 @@ SIGNATURES = {
     "mcpm_lightcone_tables_vjp_f32": (C.c_int, [C.c_void_p, _f32p, C.c_int64, C.c_void_p, C.c_int, C.c_int, _f32p, _f32p, _f32p, C.c_void_p]),
     "mcpm_observe_pos_tables_vjp_f32": (C.c_int, [C.c_void_p, _f32p, _f32p, _f32p, C.c_int64, C.c_int, C.POINTER(C.c_float), C.c_int,
                                                   C.c_void_p, C.c_int, C.c_int, _f32p, C.c_void_p]),
+    "mcpm_observe_pos_ap_f32": (C.c_int, [C.c_void_p, _f32p, _f32p, _f32p, C.c_int64, C.c_int, C.POINTER(C.c_float), C.c_int,
+                                          C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, C.c_void_p, C.c_int, C.c_int, _f32p]),
+    "mcpm_observe_pos_ap_vjp_f32": (C.c_int, [C.c_void_p, _f32p, _f32p, _f32p, C.c_int64, C.c_int, C.POINTER(C.c_float), C.c_int,
+                                              C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, C.c_void_p, C.c_int, C.c_int,
+                                              _f32p, _f32p, _f32p, _f32p, C.c_void_p, C.c_void_p]),
+    "mcpm_observe_pos_ap_tables_vjp_f32": (C.c_int, [C.c_void_p, _f32p, _f32p, _f32p, C.c_int64, C.c_int, C.POINTER(C.c_float), C.c_int,
+                                                     C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, C.c_void_p, C.c_int,
+                                                     C.c_int, _f32p, C.c_void_p]),
     "mcpm_rg2cgh_f32": (C.c_int, [C.c_void_p, _f32p, C.c_int, C.c_int, C.c_int, _f32p]),
     "mcpm_rg2cgh_vjp_f32": (C.c_int, [C.c_void_p, _f32p, C.c_int, C.c_int, C.c_int, _f32p]),
     "mcpm_cgh2rg_f32": (C.c_int, [C.c_void_p, _f32p, C.c_int, C.c_int, C.c_int, _f32p]),
@@ -154,7 +163,7 @@ SIGNATURES = {
 }
 
 
-ABI_VERSION = "mcpm 0.8 (gfx950)"   # must equal mcpm_version() of the loaded library (include/mcpm.h MCPM_ABI_VERSION)
+ABI_VERSION = "mcpm 0.9 (gfx950)"   # must equal mcpm_version() of the loaded library (include/mcpm.h MCPM_ABI_VERSION)
 
 
 def _load():

@@ -3,7 +3,8 @@ duck-typed object (the path reads Omega_m, Omega_de, Omega_k, w0, wa and uses `_
 and the initial particle lattice (bricks.py:593-603).
 
 Primordial non-Gaussianity (png_type 'fNL' / 'bias'): the transfer table, `add_png`, the five PNG terms of `lagrangian_bias` and
-the `fNL_bias` reparametrisation, each with its VJP.  Out of scope: Eulerian bias, the stochastic term s_ep * phi of the likelihood
+the `fNL_bias` reparametrisation, each with its VJP.  Alcock-Paczynski: `scale_pos`, `parperp2isoap`, `isoap2parperp` on the host and
+the `ap_auto` / `ap_param` remapping inside `observe_pos` (bricks.py:708-732, :795-857).  Out of scope: Eulerian bias, the stochastic term s_ep * phi of the likelihood
 (model.py:894) and PNG on the light-cone and curved-sky forms of the Kaiser model."""
 import os
 
@@ -397,20 +398,53 @@ def phys2cell_vel(vel, box_rot, box_size, mesh_shape):
     return (np.asarray(vel, dtype=np.float64) @ rot_matrix(box_rot)) / np.divide(box_size, mesh_shape)
 
 
+AP_KEYS = ("alpha_iso", "alpha_ap")
+
+
+def scale_pos(pos, los, scale_par, scale_perp):
+    """Scale positions in the directions parallel and perpendicular to `los` (bricks.py:708-716); host float64."""
+    pos, los = np.asarray(pos, dtype=np.float64), np.asarray(los, dtype=np.float64)
+    pos_par = (pos * los).sum(-1, keepdims=True) * los
+    pos_perp = pos - pos_par
+    return pos_par * scale_par + pos_perp * scale_perp
+
+
+def parperp2isoap(alpha_par, alpha_perp):
+    """Parallel and perpendicular scalings -> isotropic and anisotropic scalings (bricks.py:718-724)."""
+    alpha_iso = (alpha_par * alpha_perp ** 2) ** (1 / 3)
+    alpha_ap = alpha_par / alpha_perp
+    return alpha_iso, alpha_ap
+
+
+def isoap2parperp(alpha_iso, alpha_ap):
+    """Isotropic and anisotropic scalings -> parallel and perpendicular scalings (bricks.py:726-732)."""
+    alpha_par = alpha_iso * alpha_ap ** (2 / 3)
+    alpha_perp = alpha_iso * alpha_ap ** (-1 / 3)
+    return alpha_par, alpha_perp
+
+
 class ObsCtx:
     def __init__(self, **kw):
         self.__dict__.update(kw)
 
 
+def _ap_args(ctx):
+    from . import nbody
+    return (ctx.ap_mode, ctx.alpha_iso, ctx.alpha_ap, nbody._ptr(ctx.ap_tables), ctx.nap, ctx.nfid)
+
+
 def observe_pos(cosmo, pos, vel, box_center, box_rot, box_size, evol_shape, paint_shape, a_obs=None, curved_sky=True,
-                dvel=None, return_ctx=False):
+                dvel=None, return_ctx=False, ap_auto=None, ap=None, cosmo_fid=None):
     """Evolved particles (cell units of evol_shape) -> redshift-space positions in cell units of paint_shape: the chain
-    los_scalefactor_pos -> cell2phys_pos -> + rsd(vel, los, a, dvel) -> phys2cell_pos of model.py:780-797 (no
-    Alcock-Paczynski), fused in one HIP pass (mcpm_observe_pos_f32).  a_obs=None is the light cone (a = chi2a(|x|)).
-    A LatticePos comes back as a LatticePos on the paint mesh (same particle lattice), an array as an (N,3) tensor."""
+    los_scalefactor_pos -> cell2phys_pos -> + rsd(vel, los, a, dvel) -> [ap_auto | ap_param] -> phys2cell_pos of
+    model.py:780-797, fused in one HIP pass (mcpm_observe_pos_f32 / mcpm_observe_pos_ap_f32).  a_obs=None is the light cone
+    (a = chi2a(|x|)).  A LatticePos comes back as a LatticePos on the paint mesh (same particle lattice), an array as an (N,3) tensor.
+    Alcock-Paczynski (model.py:787-794): ap_auto=None none (nothing new runs); True: positions scaled by
+    a2chi(cosmo_fid, chi2a(cosmo, r)) / r (bricks.py:795-814; `cosmo_fid` required); False: by the parameters of
+    `ap` = {'alpha_iso', 'alpha_ap'} (missing = 1; bricks.py:848-857)."""
     import ctypes as C
     import torch
-    from . import nbody
+    from . import nbody, _lib
     evol_shape = tuple(int(s) for s in evol_shape)
     paint_shape = tuple(int(s) for s in paint_shape)
     plan, p, n, mode = nbody._pos_args(pos, evol_shape)
@@ -427,28 +461,72 @@ def observe_pos(cosmo, pos, vel, box_center, box_rot, box_size, evol_shape, pain
         nchi, ngrow = len(d["chi"]), len(gtab["a"])
         tables = torch.from_numpy(np.concatenate([d["chi"][::-1], d["a"][::-1], gtab["a"], gtab["g"], gtab["f"]])).to(p.device)
     out = torch.empty((n, 3), dtype=torch.float32, device=p.device)
-    plan.call("mcpm_observe_pos_f32", nbody._ptr(p), nbody._ptr(v), nbody._ptr(dv), n, mode, geom, flags, nbody._ptr(tables), nchi,
-              ngrow, nbody._ptr(out))
+    apkw = dict(ap_mode=_lib.AP_NONE, alpha_iso=1.0, alpha_ap=1.0, ap_tables=None, nap=0, nfid=0)
+    if ap_auto is None:
+        plan.call("mcpm_observe_pos_f32", nbody._ptr(p), nbody._ptr(v), nbody._ptr(dv), n, mode, geom, flags, nbody._ptr(tables), nchi,
+                  ngrow, nbody._ptr(out))
+    else:
+        if ap_auto:
+            if cosmo_fid is None:
+                raise ValueError("ap_auto=True needs the fiducial cosmology `cosmo_fid`")
+            d, df = nbody._dist_cache(cosmo), nbody._dist_cache(cosmo_fid)
+            apkw.update(ap_mode=_lib.AP_AUTO, nap=len(d["chi"]), nfid=len(df["a"]),
+                        ap_tables=torch.from_numpy(np.concatenate([d["chi"][::-1], d["a"][::-1], df["a"], df["chi"]])).to(p.device))
+        else:
+            ap = ap or {}
+            apkw.update(ap_mode=_lib.AP_PARAM, alpha_iso=float(ap.get("alpha_iso", 1.0)), alpha_ap=float(ap.get("alpha_ap", 1.0)))
+        plan.call("mcpm_observe_pos_ap_f32", nbody._ptr(p), nbody._ptr(v), nbody._ptr(dv), n, mode, geom, flags, nbody._ptr(tables), nchi,
+                  ngrow, apkw["ap_mode"], apkw["alpha_iso"], apkw["alpha_ap"], nbody._ptr(apkw["ap_tables"]), apkw["nap"], apkw["nfid"],
+                  nbody._ptr(out))
     res = nbody.LatticePos(out, paint_shape, pos.ptcl_shape) if isinstance(pos, nbody.LatticePos) else out
     if return_ctx:
-        return res, ObsCtx(plan=plan, p=p, v=v, dv=dv, n=n, mode=mode, geom=geom, flags=flags, tables=tables, nchi=nchi, ngrow=ngrow)
+        return res, ObsCtx(plan=plan, p=p, v=v, dv=dv, n=n, mode=mode, geom=geom, flags=flags, tables=tables, nchi=nchi, ngrow=ngrow, **apkw)
     return res
 
 
 def observe_pos_vjp(ctx, out_bar):
     """VJP of observe_pos: cotangent of the returned positions (N,3) -> (pos_bar, vel_bar, dvel_bar or None, gf_bar) where
-    gf_bar is the cotangent of the scalar a2g(a_obs) a2f(a_obs) (0.0 on the light cone)."""
+    gf_bar is the cotangent of the scalar a2g(a_obs) a2f(a_obs) (0.0 on the light cone).  With Alcock-Paczynski (ap_auto not None)
+    a fifth output follows: {'alpha_iso': ..., 'alpha_ap': ...}, the cotangents of the two parameters (0 for ap_auto=True, whose
+    cosmology dependence is a table cotangent: `observe_pos_tables_vjp`; alpha_ap's is 0 on a curved sky)."""
     import torch
-    from . import nbody
+    from . import nbody, _lib
     n, dev = ctx.n, ctx.p.device
     ob = nbody._f32(out_bar, (n, 3))
     pb = torch.empty((n, 3), dtype=torch.float32, device=dev)
     vb = torch.empty((n, 3), dtype=torch.float32, device=dev)
     db = torch.empty((n, 3), dtype=torch.float32, device=dev) if ctx.dv is not None else None
-    gfb = torch.zeros(1, dtype=torch.float64, device=dev)
-    ctx.plan.call("mcpm_observe_pos_vjp_f32", nbody._ptr(ctx.p), nbody._ptr(ctx.v), nbody._ptr(ctx.dv), n, ctx.mode, ctx.geom, ctx.flags,
-                  nbody._ptr(ctx.tables), ctx.nchi, ctx.ngrow, nbody._ptr(ob), nbody._ptr(pb), nbody._ptr(vb), nbody._ptr(db), nbody._ptr(gfb))
-    return pb, vb, db, float(gfb.item())
+    if getattr(ctx, "ap_mode", _lib.AP_NONE) == _lib.AP_NONE:
+        gfb = torch.zeros(1, dtype=torch.float64, device=dev)
+        ctx.plan.call("mcpm_observe_pos_vjp_f32", nbody._ptr(ctx.p), nbody._ptr(ctx.v), nbody._ptr(ctx.dv), n, ctx.mode, ctx.geom, ctx.flags,
+                      nbody._ptr(ctx.tables), ctx.nchi, ctx.ngrow, nbody._ptr(ob), nbody._ptr(pb), nbody._ptr(vb), nbody._ptr(db), nbody._ptr(gfb))
+        return pb, vb, db, float(gfb.item())
+    sc = torch.zeros(3, dtype=torch.float64, device=dev)      # gf_bar, alpha_iso_bar, alpha_ap_bar
+    ctx.plan.call("mcpm_observe_pos_ap_vjp_f32", nbody._ptr(ctx.p), nbody._ptr(ctx.v), nbody._ptr(ctx.dv), n, ctx.mode, ctx.geom, ctx.flags,
+                  nbody._ptr(ctx.tables), ctx.nchi, ctx.ngrow, *_ap_args(ctx), nbody._ptr(ob), nbody._ptr(pb), nbody._ptr(vb), nbody._ptr(db),
+                  nbody._ptr(sc), sc.data_ptr() + 8)
+    s = sc.cpu().numpy()
+    return pb, vb, db, float(s[0]), {"alpha_iso": float(s[1]), "alpha_ap": float(s[2])}
+
+
+def observe_pos_tables_vjp(ctx, out_bar):
+    """Cotangents of the look-up tables inside observe_pos (device float64): chi_bar[nchi], g_bar[ngrow], f_bar[ngrow] on the light
+    cone (the growth look-ups at the evolved positions plus, with ap_auto=True, the chi2a(cosmo, r') of the Alcock-Paczynski
+    step); at fixed a_obs with ap_auto=True chi_bar alone.  mcpm_observe_pos_tables_vjp_f32 / mcpm_observe_pos_ap_tables_vjp_f32."""
+    import torch
+    from . import nbody, _lib
+    n, dev = ctx.n, ctx.p.device
+    ob = nbody._f32(out_bar, (n, 3))
+    if getattr(ctx, "ap_mode", _lib.AP_NONE) == _lib.AP_NONE:
+        tb = torch.empty(ctx.nchi + 2 * ctx.ngrow, dtype=torch.float64, device=dev)
+        ctx.plan.call("mcpm_observe_pos_tables_vjp_f32", nbody._ptr(ctx.p), nbody._ptr(ctx.v), nbody._ptr(ctx.dv), n, ctx.mode, ctx.geom,
+                      ctx.flags, nbody._ptr(ctx.tables), ctx.nchi, ctx.ngrow, nbody._ptr(ob), nbody._ptr(tb))
+        return tb
+    lc = bool(ctx.flags & 2)
+    tb = torch.empty((ctx.nchi + 2 * ctx.ngrow) if lc else ctx.nap, dtype=torch.float64, device=dev)
+    ctx.plan.call("mcpm_observe_pos_ap_tables_vjp_f32", nbody._ptr(ctx.p), nbody._ptr(ctx.v), nbody._ptr(ctx.dv), n, ctx.mode, ctx.geom,
+                  ctx.flags, nbody._ptr(ctx.tables), ctx.nchi, ctx.ngrow, *_ap_args(ctx), nbody._ptr(ob), nbody._ptr(tb))
+    return tb
 
 
 # ------------------------------------------------------------------------------------------------

@@ -1,13 +1,19 @@
-// Evolved particles -> redshift-space positions on the paint mesh (montecosmo/model.py:780-797 without Alcock-Paczynski):
+// Evolved particles -> redshift-space positions on the paint mesh (montecosmo/model.py:780-797):
 //   los, a   = los_scalefactor_pos(pos)                      bricks.py:750-768
 //   pos_phys = cell2phys_pos(pos)                            bricks.py:628-636
 //   pos_phys += rsd(vel, los, a, dvel)                       bricks.py:791-803
+//   pos_phys = ap_auto(pos_phys) | ap_param(pos_phys)        bricks.py:795-814, :848-857 (Alcock-Paczynski; the *_ap_* entry points)
 //   pos_out  = phys2cell_pos(pos_phys, paint_shape)          bricks.py:638-646
 // fused into one pass with its VJP.  cell2phys then phys2cell with the same box cancel exactly, so the kernel evaluates
 //   out = x * (cell_e / cell_p) + R^T [ (V . l) l ] / cell_p,   V = R (vel * cell_e) g(a) f(a) + dvel,
 // P = R (x * cell_e - box/2) + centre, l = P/|P| (curved sky) or centre/|centre| (flat), a = chi2a(|P|) or |P . l|,
 // which keeps the displacement-from-lattice encoding of the positions (no box-sized float32 round trip).
 // Light cone: a and g(a) f(a) come from the same two linear-interpolation tables as the host (chi -> a, a -> g, f).
+// Alcock-Paczynski: with P' = P + (V . l) l the remapped position is alpha P' (auto: alpha = a2chi(cosmo_fid, chi2a(cosmo, r')) / r',
+// r' = |P'| or |P' . l_flat|; param: alpha_iso, or alpha_par / alpha_perp along / across l_flat).  It is evaluated as
+//   out += R^T [ c1 P' + c2 (P' . l_flat) l_flat ] / cell_p,   c1 = alpha - 1 (alpha_perp - 1 on the flat sky), c2 = alpha_par - alpha_perp,
+// with the auto c1 = (rho - r') / r' formed in float64 from the tables: the small difference of two distances of thousands of Mpc/h
+// never passes through float32.
 #include "mcpm_internal.h"
 #include "reduce_dev.h"
 
@@ -25,6 +31,14 @@ struct Obs {
 
 struct Tables {                 // device, float64; chi ascending
     const double *chi, *a_of_chi, *a, *g, *f;
+};
+
+// Alcock-Paczynski stage.  mode: MCPM_AP_NONE / MCPM_AP_AUTO / MCPM_AP_PARAM (a template argument of the kernels).
+struct Ap {
+    float c1, c2;                               // param: alpha - 1 (curved) or alpha_perp - 1, alpha_par - alpha_perp (flat)
+    double dc[4];                               // param: d c1 / d alpha_iso, d c2 / d alpha_iso, d c1 / d alpha_ap, d c2 / d alpha_ap
+    const double *chi, *a_of_chi, *afid, *chifid;   // auto (device float64): chi ascending -> a of the sampled cosmology; a ascending -> chi_fid
+    int nap, nfid;
 };
 
 // np.interp (clamped) and its slope
@@ -92,6 +106,63 @@ __device__ __forceinline__ void forward(const Obs &og, const Tables &tb, const f
     w.s = w.V[0] * w.l[0] + w.V[1] * w.l[1] + w.V[2] * w.l[2];
 }
 
+struct ApW {
+    float Pp[3], c1, dl, dc1_dr, sgn, rp, ir;   // P', c1, P' . l_flat, d c1 / d r', sign(P' . l_flat), r', 1 / r' (0 at r' = 0)
+};
+
+// Alcock-Paczynski displacement D = alpha(P') P' - P' of one particle (Mpc/h), to be added to the RSD displacement
+template <int AP>
+__device__ __forceinline__ void ap_forward(const Obs &og, const Ap &ap, const Fwd &w, ApW &q, float (&D)[3]) {
+#pragma unroll
+    for (int a = 0; a < 3; ++a) q.Pp[a] = w.P[a] + w.s * w.l[a];
+    float rp;
+    q.sgn = 1.f;
+    q.dl = 0.f;
+    if (og.curved) {
+        rp = sqrtf(q.Pp[0] * q.Pp[0] + q.Pp[1] * q.Pp[1] + q.Pp[2] * q.Pp[2]);
+    } else {
+        q.dl = q.Pp[0] * og.lf[0] + q.Pp[1] * og.lf[1] + q.Pp[2] * og.lf[2];
+        q.sgn = q.dl < 0.f ? -1.f : 1.f;
+        rp = fabsf(q.dl);
+    }
+    q.rp = rp;
+    q.ir = rp == 0.f ? 0.f : 1.f / rp;
+    q.c1 = ap.c1;
+    q.dc1_dr = 0.f;
+    if (AP == MCPM_AP_AUTO) {
+        q.c1 = -1.f;                                 // safe_div(rho, 0) = 0
+        if (rp != 0.f) {
+            const double r = (double)rp;
+            double sc, sf;
+            const double a = interp1(r, ap.chi, ap.a_of_chi, ap.nap, sc);
+            const double rho = interp1(a, ap.afid, ap.chifid, ap.nfid, sf);
+            q.c1 = (float)((rho - r) / r);
+            q.dc1_dr = (float)((sc * sf - rho / r) / r);
+        }
+    }
+    const float c2d = (AP == MCPM_AP_PARAM && !og.curved) ? ap.c2 * q.dl : 0.f;
+#pragma unroll
+    for (int a = 0; a < 3; ++a) D[a] = q.c1 * q.Pp[a] + c2d * og.lf[a];
+}
+
+// Db: cotangent of the displacement D (and of the RSD displacement: the same R (out_bar / cell_p)).  Returns the cotangent of P'
+// and the cotangents of c1 and c2.
+template <int AP>
+__device__ __forceinline__ void ap_backward(const Obs &og, const Ap &ap, const ApW &q, const float (&Db)[3], float (&Ppb)[3], float &c1b,
+                                            float &c2b) {
+    c1b = Db[0] * q.Pp[0] + Db[1] * q.Pp[1] + Db[2] * q.Pp[2];
+    const float dbl = Db[0] * og.lf[0] + Db[1] * og.lf[1] + Db[2] * og.lf[2];
+    const bool par = AP == MCPM_AP_PARAM && !og.curved;
+    c2b = par ? dbl * q.dl : 0.f;
+#pragma unroll
+    for (int a = 0; a < 3; ++a) Ppb[a] = q.c1 * Db[a] + (par ? ap.c2 * dbl * og.lf[a] : 0.f);
+    if (AP == MCPM_AP_AUTO) {
+        const float rb = c1b * q.dc1_dr;             // through r'
+#pragma unroll
+        for (int a = 0; a < 3; ++a) Ppb[a] += og.curved ? rb * q.Pp[a] * q.ir : rb * q.sgn * og.lf[a];
+    }
+}
+
 __device__ __forceinline__ void lattice_point(const Geom &g, int64_t i, float (&q)[3]) {
     const int ipz = (int)(i % g.pz);
     const int64_t t = i / g.pz;
@@ -101,8 +172,8 @@ __device__ __forceinline__ void lattice_point(const Geom &g, int64_t i, float (&
     q[2] = (float)((double)ipz * g.nz / g.pz);
 }
 
-template <int MODE>
-__global__ __launch_bounds__(256) void observe_kernel(Geom g, Obs og, Tables tb, const float *__restrict__ pos,
+template <int MODE, int AP>
+__global__ __launch_bounds__(256) void observe_kernel(Geom g, Obs og, Tables tb, Ap ap, const float *__restrict__ pos,
                                                       const float *__restrict__ vel, const float *__restrict__ dvel, int64_t n,
                                                       float *__restrict__ out) {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
@@ -120,17 +191,27 @@ __global__ __launch_bounds__(256) void observe_kernel(Geom g, Obs og, Tables tb,
     forward(og, tb, x, v, dv, w);
     float D[3] = {w.s * w.l[0], w.s * w.l[1], w.s * w.l[2]}, Dr[3];
     rot_t(og.R, D, Dr);
+    if (AP == MCPM_AP_NONE) {
 #pragma unroll
-    for (int a = 0; a < 3; ++a) out[3 * i + a] = d[a] * (og.ce[a] / og.cp[a]) + Dr[a] / og.cp[a];  // lattice mode: displacement from q * ce/cp
+        for (int a = 0; a < 3; ++a) out[3 * i + a] = d[a] * (og.ce[a] / og.cp[a]) + Dr[a] / og.cp[a];  // lattice mode: displacement from q * ce/cp
+    } else {
+        ApW aw;
+        float A[3], Ar[3];
+        ap_forward<AP>(og, ap, w, aw, A);
+        rot_t(og.R, A, Ar);
+#pragma unroll
+        for (int a = 0; a < 3; ++a) out[3 * i + a] = d[a] * (og.ce[a] / og.cp[a]) + Dr[a] / og.cp[a] + Ar[a] / og.cp[a];
+    }
 }
 
-template <int MODE>
-__global__ __launch_bounds__(256) void observe_vjp_kernel(Geom g, Obs og, Tables tb, const float *__restrict__ pos,
+template <int MODE, int AP>
+__global__ __launch_bounds__(256) void observe_vjp_kernel(Geom g, Obs og, Tables tb, Ap ap, const float *__restrict__ pos,
                                                           const float *__restrict__ vel, const float *__restrict__ dvel, int64_t n,
                                                           const float *__restrict__ ob, float *__restrict__ pos_bar,
                                                           float *__restrict__ vel_bar, float *__restrict__ dvel_bar, double *part) {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    double red[1] = {0.};
+    constexpr int NR = AP == MCPM_AP_NONE ? 1 : 3;      // gf_bar [, alpha_iso_bar, alpha_ap_bar]
+    double red[NR] = {};
     if (i < n) {
         float q[3] = {0.f, 0.f, 0.f}, x[3], v[3], dv[3] = {0.f, 0.f, 0.f}, o[3];
         if (MODE == MCPM_POS_LATTICE) lattice_point(g, i, q);
@@ -147,6 +228,19 @@ __global__ __launch_bounds__(256) void observe_vjp_kernel(Geom g, Obs og, Tables
 #pragma unroll
         for (int a = 0; a < 3; ++a) t[a] = o[a] / og.cp[a];
         rot(og.R, t, Db);                                                   // D_bar = R (out_bar / cell_p)
+        float Ppb[3] = {0.f, 0.f, 0.f};
+        if constexpr (AP != MCPM_AP_NONE) {      // P' = P + s l: its cotangent joins D_bar on the way to s and l, and goes to P directly
+            ApW aw;
+            float A[3], c1b, c2b;
+            ap_forward<AP>(og, ap, w, aw, A);
+            ap_backward<AP>(og, ap, aw, Db, Ppb, c1b, c2b);
+            if constexpr (AP == MCPM_AP_PARAM) {
+                red[NR - 2] = (double)c1b * ap.dc[0] + (double)c2b * ap.dc[1];
+                red[NR - 1] = (double)c1b * ap.dc[2] + (double)c2b * ap.dc[3];
+            }
+#pragma unroll
+            for (int a = 0; a < 3; ++a) Db[a] += Ppb[a];
+        }
         const float sb = Db[0] * w.l[0] + Db[1] * w.l[1] + Db[2] * w.l[2];  // s_bar
         float lb[3], Vb[3];
 #pragma unroll
@@ -173,13 +267,17 @@ __global__ __launch_bounds__(256) void observe_vjp_kernel(Geom g, Obs og, Tables
 #pragma unroll
             for (int a = 0; a < 3; ++a) Pb[a] = rb * w.sgn * w.l[a];
         }
+        if constexpr (AP != MCPM_AP_NONE) {
+#pragma unroll
+            for (int a = 0; a < 3; ++a) Pb[a] += Ppb[a];
+        }
         float xt[3];
         rot_t(og.R, Pb, xt);
 #pragma unroll
         for (int a = 0; a < 3; ++a) pos_bar[3 * i + a] = o[a] * (og.ce[a] / og.cp[a]) + xt[a] * og.ce[a];
         red[0] = og.lightcone ? 0. : (double)gfb;
     }
-    block_partial<1>(red, part, gridDim.x, blockIdx.x);
+    block_partial<NR>(red, part, gridDim.x, blockIdx.x);
 }
 
 
@@ -335,8 +433,11 @@ __global__ __launch_bounds__(256) void lightcone_tables_vjp_kernel(const float *
 
 // Eulerian side (model.py:781-784): gf_p = a2g(a_p) a2f(a_p), a_p = chi2a(r_p) at the evolved particle's distance.
 // tables as in observe_kernel (chi, a(chi), a, g, f);  accumulators: chi_bar[nchi], g_bar[ngrow], f_bar[ngrow] (kinds 0, 1, 2).
-template <int MODE, int PASS>
-__global__ __launch_bounds__(256) void observe_tables_vjp_kernel(Geom g, Obs og, Tables tb, const float *__restrict__ pos,
+// Automatic Alcock-Paczynski (bricks.py:799-801): rho = a2chi(cosmo_fid, chi2a(cosmo, r')) moves with the NODES of the chi -> a
+// look-up at r' (the fiducial table is constant): a_bar = rho_bar d chi_fid / d a goes into the same chi_bar accumulator.  Off the
+// light cone (og.lightcone = 0, ngrow = 0) that is the only contribution.
+template <int MODE, int AP, int PASS>
+__global__ __launch_bounds__(256) void observe_tables_vjp_kernel(Geom g, Obs og, Tables tb, Ap ap, const float *__restrict__ pos,
                                                                  const float *__restrict__ vel, const float *__restrict__ dvel, int64_t n,
                                                                  const float *__restrict__ ob, unsigned *__restrict__ mxbits,
                                                                  unsigned long long *__restrict__ out) {
@@ -362,17 +463,35 @@ __global__ __launch_bounds__(256) void observe_tables_vjp_kernel(Geom g, Obs og,
 #pragma unroll
         for (int a = 0; a < 3; ++a) t[a] = o[a] / og.cp[a];
         rot(og.R, t, Db);
-        const float sb = Db[0] * w.l[0] + Db[1] * w.l[1] + Db[2] * w.l[2];
-        const double gfb = (double)sb * ((double)w.l[0] * w.Vr[0] + (double)w.l[1] * w.Vr[1] + (double)w.l[2] * w.Vr[2]);
-        const Interp ba = interp_idx((double)w.r, tb.chi, tb.a_of_chi, og.nchi);
-        const Interp bg = interp_idx(ba.y, tb.a, tb.g, og.ngrow);
-        double f, sf;
-        interp_at(bg, tb.a, tb.f, f, sf);
-        const double gb = gfb * f, fb = gfb * bg.y, ab = gb * bg.slope + fb * sf;
-        bad = bad || !(gb == gb && fb == fb && ab == ab);
-        scatter_fp<PASS>(A, 1, o_g, bg, gb);
-        scatter_fp<PASS>(A, 2, o_f, bg, fb);
-        scatter_xp<PASS>(A, 0, o_chi, ba, ab);
+        if constexpr (AP != MCPM_AP_NONE) {
+            ApW aw;
+            float D[3], Ppb[3], c1b, c2b;
+            ap_forward<AP>(og, ap, w, aw, D);
+            ap_backward<AP>(og, ap, aw, Db, Ppb, c1b, c2b);
+            if (AP == MCPM_AP_AUTO && aw.rp != 0.f) {
+                const Interp bp = interp_idx((double)aw.rp, ap.chi, ap.a_of_chi, ap.nap);
+                double sfid;
+                interp1(bp.y, ap.afid, ap.chifid, ap.nfid, sfid);
+                const double apb = (double)c1b / (double)aw.rp * sfid;      // rho_bar = c1_bar / r';  a_bar = rho_bar d chi_fid / d a
+                bad = bad || !(apb == apb);
+                scatter_xp<PASS>(A, 0, o_chi, bp, apb);
+            }
+#pragma unroll
+            for (int a = 0; a < 3; ++a) Db[a] += Ppb[a];      // the growth product moves P' = P + s l as well
+        }
+        if (og.lightcone) {
+            const float sb = Db[0] * w.l[0] + Db[1] * w.l[1] + Db[2] * w.l[2];
+            const double gfb = (double)sb * ((double)w.l[0] * w.Vr[0] + (double)w.l[1] * w.Vr[1] + (double)w.l[2] * w.Vr[2]);
+            const Interp ba = interp_idx((double)w.r, tb.chi, tb.a_of_chi, og.nchi);
+            const Interp bg = interp_idx(ba.y, tb.a, tb.g, og.ngrow);
+            double f, sf;
+            interp_at(bg, tb.a, tb.f, f, sf);
+            const double gb = gfb * f, fb = gfb * bg.y, ab = gb * bg.slope + fb * sf;
+            bad = bad || !(gb == gb && fb == fb && ab == ab);
+            scatter_fp<PASS>(A, 1, o_g, bg, gb);
+            scatter_fp<PASS>(A, 2, o_f, bg, fb);
+            scatter_xp<PASS>(A, 0, o_chi, ba, ab);
+        }
     }
     acc_end<PASS>(A, ntot, mxbits, out, bad);
 }
@@ -399,6 +518,47 @@ Obs make_obs(const mcpm_plan *p, const float *geom, int flags, int nchi, int ngr
     return og;
 }
 
+// Alcock-Paczynski arguments of the *_ap_* entry points -> the kernels' struct.  ap_tables (device float64) = chi ascending [nap],
+// a(chi) [nap] of the sampled cosmology, a ascending [nfid], chi_fid(a) [nfid] of the fiducial one.
+int make_ap(mcpm_plan *p, const char *who, int curved, int lightcone, int nchi, int ap_mode, double alpha_iso, double alpha_ap,
+            const double *t, int nap, int nfid, Ap *out) {
+    Ap ap{};
+    MCPM_REQUIRE(p, ap_mode == MCPM_AP_NONE || ap_mode == MCPM_AP_AUTO || ap_mode == MCPM_AP_PARAM, MCPM_E_ARG, std::string(who) + ": bad ap_mode");
+    if (ap_mode == MCPM_AP_AUTO) {
+        MCPM_REQUIRE(p, t && nap >= 2 && nfid >= 2, MCPM_E_ARG, std::string(who) + ": automatic Alcock-Paczynski needs ap_tables");
+        MCPM_REQUIRE(p, !lightcone || nap == nchi, MCPM_E_ARG, std::string(who) + ": on the light cone ap_tables' chi nodes are those of tables (nap = nchi)");
+        ap.chi = t, ap.a_of_chi = t + nap, ap.afid = t + 2 * nap, ap.chifid = t + 2 * nap + nfid;
+        ap.nap = nap, ap.nfid = nfid;
+    } else if (ap_mode == MCPM_AP_PARAM) {
+        MCPM_REQUIRE(p, std::isfinite(alpha_iso), MCPM_E_ARG, std::string(who) + ": alpha_iso must be finite");
+        MCPM_REQUIRE(p, curved || (alpha_ap > 0. && std::isfinite(alpha_ap)), MCPM_E_ARG, std::string(who) + ": alpha_ap must be positive and finite");
+        if (curved) {                                   // bricks.py:852-853
+            ap.c1 = (float)(alpha_iso - 1.), ap.c2 = 0.f;
+            ap.dc[0] = 1.;
+        } else {                                        // bricks.py:726-732, :855-856
+            const double m = std::pow(alpha_ap, -1. / 3.), q = std::pow(alpha_ap, 2. / 3.);      // alpha_perp, alpha_par over alpha_iso
+            ap.c1 = (float)(alpha_iso * m - 1.), ap.c2 = (float)(alpha_iso * (q - m));
+            ap.dc[0] = m, ap.dc[1] = q - m;
+            ap.dc[2] = -alpha_iso * m / (3. * alpha_ap), ap.dc[3] = alpha_iso * (2. * q + m) / (3. * alpha_ap);
+        }
+    }
+    *out = ap;
+    return MCPM_OK;
+}
+
+#define OBS_DISPATCH(K, MO, AP, ...)                                                                    \
+    do {                                                                                                \
+        if ((MO) == MCPM_POS_LATTICE) {                                                                 \
+            if ((AP) == MCPM_AP_NONE) { K(MCPM_POS_LATTICE, MCPM_AP_NONE); }                            \
+            else if ((AP) == MCPM_AP_AUTO) { K(MCPM_POS_LATTICE, MCPM_AP_AUTO); }                       \
+            else { K(MCPM_POS_LATTICE, MCPM_AP_PARAM); }                                                \
+        } else {                                                                                        \
+            if ((AP) == MCPM_AP_NONE) { K(MCPM_POS_ABSOLUTE, MCPM_AP_NONE); }                           \
+            else if ((AP) == MCPM_AP_AUTO) { K(MCPM_POS_ABSOLUTE, MCPM_AP_AUTO); }                      \
+            else { K(MCPM_POS_ABSOLUTE, MCPM_AP_PARAM); }                                               \
+        }                                                                                               \
+    } while (0)
+
 }  // namespace
 
 extern "C" {
@@ -408,49 +568,72 @@ extern "C" {
 // a(chi) [nchi], a [ngrow], g [ngrow], f [ngrow] -- the host's growth / distance tables).  pos / out follow pos_mode:
 // MCPM_POS_LATTICE: displacements from the plan's particle lattice on the evolution mesh in, displacements from the same
 // lattice scaled to the paint mesh out; MCPM_POS_ABSOLUTE: absolute cell coordinates in and out.
-int mcpm_observe_pos_f32(mcpm_plan *p, const float *pos, const float *vel, const float *dvel, int64_t n, int mode,
-                         const float *geom, int flags, const double *tables, int nchi, int ngrow, float *out) {
+int mcpm_observe_pos_ap_f32(mcpm_plan *p, const float *pos, const float *vel, const float *dvel, int64_t n, int mode,
+                            const float *geom, int flags, const double *tables, int nchi, int ngrow, int ap_mode, double alpha_iso,
+                            double alpha_ap, const double *ap_tables, int nap, int nfid, float *out) {
     if (!p) return MCPM_E_ARG;
-    MCPM_REQUIRE(p, pos && vel && geom && out && n > 0, MCPM_E_ARG, "mcpm_observe_pos_f32: bad argument");
-    MCPM_REQUIRE(p, mode == MCPM_POS_ABSOLUTE || (mode == MCPM_POS_LATTICE && n == p->Np), MCPM_E_ARG, "mcpm_observe_pos_f32: bad pos_mode / count");
-    MCPM_REQUIRE(p, !(flags & 2) || (tables && nchi >= 2 && ngrow >= 2), MCPM_E_ARG, "mcpm_observe_pos_f32: light cone needs the tables");
+    MCPM_REQUIRE(p, pos && vel && geom && out && n > 0, MCPM_E_ARG, "mcpm_observe_pos_ap_f32: bad argument");
+    MCPM_REQUIRE(p, mode == MCPM_POS_ABSOLUTE || (mode == MCPM_POS_LATTICE && n == p->Np), MCPM_E_ARG, "mcpm_observe_pos_ap_f32: bad pos_mode / count");
+    MCPM_REQUIRE(p, !(flags & 2) || (tables && nchi >= 2 && ngrow >= 2), MCPM_E_ARG, "mcpm_observe_pos_ap_f32: light cone needs the tables");
     Obs og = make_obs(p, geom, flags, nchi, ngrow);
+    Ap ap;
+    MCPM_TRY(make_ap(p, "mcpm_observe_pos_ap_f32", og.curved, og.lightcone, nchi, ap_mode, alpha_iso, alpha_ap, ap_tables, nap, nfid, &ap));
     Tables tb{tables, tables ? tables + nchi : nullptr, tables ? tables + 2 * nchi : nullptr,
               tables ? tables + 2 * nchi + ngrow : nullptr, tables ? tables + 2 * nchi + 2 * ngrow : nullptr};
     const unsigned nb = (unsigned)((n + 255) / 256);
     StageTimer st_(p, ST_LPT, (dvel ? 48.0 : 36.0) * n);
-    if (mode == MCPM_POS_LATTICE) observe_kernel<MCPM_POS_LATTICE><<<nb, 256, 0, p->stream>>>(p->g, og, tb, pos, vel, dvel, n, out);
-    else observe_kernel<MCPM_POS_ABSOLUTE><<<nb, 256, 0, p->stream>>>(p->g, og, tb, pos, vel, dvel, n, out);
+#define K(MO, AP) observe_kernel<MO, AP><<<nb, 256, 0, p->stream>>>(p->g, og, tb, ap, pos, vel, dvel, n, out)
+    OBS_DISPATCH(K, mode, ap_mode);
+#undef K
     MCPM_LAUNCH_CHECK(p, "observe_kernel");
     return MCPM_OK;
 }
 
+int mcpm_observe_pos_f32(mcpm_plan *p, const float *pos, const float *vel, const float *dvel, int64_t n, int mode,
+                         const float *geom, int flags, const double *tables, int nchi, int ngrow, float *out) {
+    return mcpm_observe_pos_ap_f32(p, pos, vel, dvel, n, mode, geom, flags, tables, nchi, ngrow, MCPM_AP_NONE, 1., 1., nullptr, 0, 0, out);
+}
+
 // VJP: out_bar (n,3) -> pos_bar, vel_bar, dvel_bar (NULL if dvel was NULL) and gf_bar (device double; the cotangent of the
 // scalar g(a_obs) f(a_obs); 0 on the light cone, where the growth dependence on the particle distance is already in pos_bar
-// and the dependence of the tables on the cosmology is not propagated).
-int mcpm_observe_pos_vjp_f32(mcpm_plan *p, const float *pos, const float *vel, const float *dvel, int64_t n, int mode,
-                             const float *geom, int flags, const double *tables, int nchi, int ngrow, const float *out_bar,
-                             float *pos_bar, float *vel_bar, float *dvel_bar, double *gf_bar) {
+// and the dependence of the tables on the cosmology is left to mcpm_observe_pos_ap_tables_vjp_f32).  alpha_bar (device double[2],
+// NULL allowed with MCPM_AP_NONE): cotangents of alpha_iso and alpha_ap (0 unless MCPM_AP_PARAM; alpha_ap_bar = 0 on a curved sky).
+int mcpm_observe_pos_ap_vjp_f32(mcpm_plan *p, const float *pos, const float *vel, const float *dvel, int64_t n, int mode,
+                                const float *geom, int flags, const double *tables, int nchi, int ngrow, int ap_mode, double alpha_iso,
+                                double alpha_ap, const double *ap_tables, int nap, int nfid, const float *out_bar, float *pos_bar,
+                                float *vel_bar, float *dvel_bar, double *gf_bar, double *alpha_bar) {
     if (!p) return MCPM_E_ARG;
-    MCPM_REQUIRE(p, pos && vel && geom && out_bar && pos_bar && vel_bar && gf_bar && n > 0, MCPM_E_ARG, "mcpm_observe_pos_vjp_f32: bad argument");
-    MCPM_REQUIRE(p, mode == MCPM_POS_ABSOLUTE || (mode == MCPM_POS_LATTICE && n == p->Np), MCPM_E_ARG, "mcpm_observe_pos_vjp_f32: bad pos_mode / count");
-    MCPM_REQUIRE(p, !(flags & 2) || (tables && nchi >= 2 && ngrow >= 2), MCPM_E_ARG, "mcpm_observe_pos_vjp_f32: light cone needs the tables");
-    MCPM_REQUIRE(p, (dvel == nullptr) == (dvel_bar == nullptr), MCPM_E_ARG, "mcpm_observe_pos_vjp_f32: dvel and dvel_bar go together");
+    MCPM_REQUIRE(p, pos && vel && geom && out_bar && pos_bar && vel_bar && gf_bar && n > 0, MCPM_E_ARG, "mcpm_observe_pos_ap_vjp_f32: bad argument");
+    MCPM_REQUIRE(p, mode == MCPM_POS_ABSOLUTE || (mode == MCPM_POS_LATTICE && n == p->Np), MCPM_E_ARG, "mcpm_observe_pos_ap_vjp_f32: bad pos_mode / count");
+    MCPM_REQUIRE(p, !(flags & 2) || (tables && nchi >= 2 && ngrow >= 2), MCPM_E_ARG, "mcpm_observe_pos_ap_vjp_f32: light cone needs the tables");
+    MCPM_REQUIRE(p, (dvel == nullptr) == (dvel_bar == nullptr), MCPM_E_ARG, "mcpm_observe_pos_ap_vjp_f32: dvel and dvel_bar go together");
+    MCPM_REQUIRE(p, ap_mode == MCPM_AP_NONE || alpha_bar, MCPM_E_ARG, "mcpm_observe_pos_ap_vjp_f32: alpha_bar is required with Alcock-Paczynski");
     Obs og = make_obs(p, geom, flags, nchi, ngrow);
+    Ap ap;
+    MCPM_TRY(make_ap(p, "mcpm_observe_pos_ap_vjp_f32", og.curved, og.lightcone, nchi, ap_mode, alpha_iso, alpha_ap, ap_tables, nap, nfid, &ap));
     Tables tb{tables, tables ? tables + nchi : nullptr, tables ? tables + 2 * nchi : nullptr,
               tables ? tables + 2 * nchi + ngrow : nullptr, tables ? tables + 2 * nchi + 2 * ngrow : nullptr};
     double *P, *Q;
     unsigned *ticket, R;
     const unsigned nb = (unsigned)((n + 255) / 256);
+    const int nred = ap_mode == MCPM_AP_NONE ? 1 : 3;
     StageTimer st_(p, ST_LPT, (dvel ? 84.0 : 60.0) * n);
-    MCPM_TRY(mcpm_det_scratch(p, 1, nb, &P, &Q, &ticket, &R));
-    if (mode == MCPM_POS_LATTICE)
-        observe_vjp_kernel<MCPM_POS_LATTICE><<<nb, 256, 0, p->stream>>>(p->g, og, tb, pos, vel, dvel, n, out_bar, pos_bar, vel_bar, dvel_bar, P);
-    else
-        observe_vjp_kernel<MCPM_POS_ABSOLUTE><<<nb, 256, 0, p->stream>>>(p->g, og, tb, pos, vel, dvel, n, out_bar, pos_bar, vel_bar, dvel_bar, P);
-    det_fold_kernel<<<R, 256, 0, p->stream>>>(P, nb, 1, Q, ticket, 1.0, det_outs(gf_bar));
+    MCPM_TRY(mcpm_det_scratch(p, nred, nb, &P, &Q, &ticket, &R));
+#define K(MO, AP) observe_vjp_kernel<MO, AP><<<nb, 256, 0, p->stream>>>(p->g, og, tb, ap, pos, vel, dvel, n, out_bar, pos_bar, vel_bar, dvel_bar, P)
+    OBS_DISPATCH(K, mode, ap_mode);
+#undef K
+    DetOuts outs = det_outs(gf_bar);
+    if (nred == 3) outs.p[1] = alpha_bar, outs.p[2] = alpha_bar + 1;
+    det_fold_kernel<<<R, 256, 0, p->stream>>>(P, nb, nred, Q, ticket, 1.0, outs);
     MCPM_LAUNCH_CHECK(p, "observe_vjp_kernel");
     return MCPM_OK;
+}
+
+int mcpm_observe_pos_vjp_f32(mcpm_plan *p, const float *pos, const float *vel, const float *dvel, int64_t n, int mode,
+                             const float *geom, int flags, const double *tables, int nchi, int ngrow, const float *out_bar,
+                             float *pos_bar, float *vel_bar, float *dvel_bar, double *gf_bar) {
+    return mcpm_observe_pos_ap_vjp_f32(p, pos, vel, dvel, n, mode, geom, flags, tables, nchi, ngrow, MCPM_AP_NONE, 1., 1., nullptr, 0, 0,
+                                       out_bar, pos_bar, vel_bar, dvel_bar, gf_bar, nullptr);
 }
 
 // Light cone, Lagrangian side: table cotangents of the look-ups a_q = chi2a(r0_q), a2g / a2g2 / a2dg2dg (a_q) (see
@@ -475,32 +658,50 @@ int mcpm_lightcone_tables_vjp_f32(mcpm_plan *p, const float *r0, int64_t n, cons
     return MCPM_OK;
 }
 
-// Light cone, observation side: table cotangents of gf_p = a2g(a_p) a2f(a_p), a_p = chi2a(|P_p|) inside mcpm_observe_pos_f32 (same
-// arguments; flags must have the light-cone bit).  table_bar (device float64, OVERWRITTEN): chi_bar[nchi], g_bar[ngrow], f_bar[ngrow].
-int mcpm_observe_pos_tables_vjp_f32(mcpm_plan *p, const float *pos, const float *vel, const float *dvel, int64_t n, int mode,
-                                    const float *geom, int flags, const double *tables, int nchi, int ngrow, const float *out_bar,
-                                    double *table_bar) {
+// Observation side: table cotangents of gf_p = a2g(a_p) a2f(a_p), a_p = chi2a(|P_p|) inside mcpm_observe_pos_f32 (light-cone bit) and
+// of the automatic Alcock-Paczynski look-up chi2a(r') (MCPM_AP_AUTO, with or without the light-cone bit).  table_bar (device float64,
+// OVERWRITTEN): chi_bar[nchi], g_bar[ngrow], f_bar[ngrow] on the light cone; chi_bar[nap] alone off it.
+int mcpm_observe_pos_ap_tables_vjp_f32(mcpm_plan *p, const float *pos, const float *vel, const float *dvel, int64_t n, int mode,
+                                       const float *geom, int flags, const double *tables, int nchi, int ngrow, int ap_mode,
+                                       double alpha_iso, double alpha_ap, const double *ap_tables, int nap, int nfid, const float *out_bar,
+                                       double *table_bar) {
     if (!p) return MCPM_E_ARG;
-    MCPM_REQUIRE(p, pos && vel && geom && out_bar && table_bar && n > 0, MCPM_E_ARG, "mcpm_observe_pos_tables_vjp_f32: bad argument");
-    MCPM_REQUIRE(p, mode == MCPM_POS_ABSOLUTE || (mode == MCPM_POS_LATTICE && n == p->Np), MCPM_E_ARG, "mcpm_observe_pos_tables_vjp_f32: bad pos_mode / count");
-    MCPM_REQUIRE(p, (flags & 2) && tables && nchi >= 2 && ngrow >= 2, MCPM_E_ARG, "mcpm_observe_pos_tables_vjp_f32: light cone only (flags bit 1, tables)");
+    MCPM_REQUIRE(p, pos && vel && geom && out_bar && table_bar && n > 0, MCPM_E_ARG, "mcpm_observe_pos_ap_tables_vjp_f32: bad argument");
+    MCPM_REQUIRE(p, mode == MCPM_POS_ABSOLUTE || (mode == MCPM_POS_LATTICE && n == p->Np), MCPM_E_ARG, "mcpm_observe_pos_ap_tables_vjp_f32: bad pos_mode / count");
+    const bool lc = (flags & 2) != 0;
+    MCPM_REQUIRE(p, lc || ap_mode == MCPM_AP_AUTO, MCPM_E_ARG, "mcpm_observe_pos_ap_tables_vjp_f32: light cone only (flags bit 1, tables), or automatic Alcock-Paczynski");
+    MCPM_REQUIRE(p, !lc || (tables && nchi >= 2 && ngrow >= 2), MCPM_E_ARG, "mcpm_observe_pos_ap_tables_vjp_f32: light cone needs the tables");
+    if (!lc) nchi = nap, ngrow = 0;      // the accumulator's layout: the Alcock-Paczynski look-up's chi nodes alone
     const size_t ntot = (size_t)nchi + 2 * (size_t)ngrow;
-    MCPM_REQUIRE(p, ntot + 8 <= 3072 && ntot * sizeof(double) <= 60 * 1024, MCPM_E_ARG, "mcpm_observe_pos_tables_vjp_f32: tables exceed the accumulators");
+    MCPM_REQUIRE(p, ntot + 8 <= 3072 && ntot * sizeof(double) <= 60 * 1024, MCPM_E_ARG, "mcpm_observe_pos_ap_tables_vjp_f32: tables exceed the accumulators");
     Obs og = make_obs(p, geom, flags, nchi, ngrow);
-    Tables tb{tables, tables + nchi, tables + 2 * nchi, tables + 2 * nchi + ngrow, tables + 2 * nchi + 2 * ngrow};
+    Ap ap;
+    MCPM_TRY(make_ap(p, "mcpm_observe_pos_ap_tables_vjp_f32", og.curved, og.lightcone, nchi, ap_mode, alpha_iso, alpha_ap, ap_tables, nap, nfid, &ap));
+    Tables tb{tables, tables ? tables + nchi : nullptr, tables ? tables + 2 * nchi : nullptr,
+              tables ? tables + 2 * nchi + ngrow : nullptr, tables ? tables + 2 * nchi + 2 * ngrow : nullptr};
     unsigned long long *acc = reinterpret_cast<unsigned long long *>(p->reduce);
     unsigned *mx = reinterpret_cast<unsigned *>(acc + ntot);
     MCPM_HIP(p, hipMemsetAsync(acc, 0, (ntot + 4) * sizeof(double), p->stream));
     const unsigned nb = (unsigned)std::min<int64_t>((n + 255) / 256, 2048);
-#define LAUNCH(MO)                                                                                                                              \
-    observe_tables_vjp_kernel<MO, 0><<<nb, 256, 0, p->stream>>>(p->g, og, tb, pos, vel, dvel, n, out_bar, mx, acc);                              \
-    observe_tables_vjp_kernel<MO, 1><<<nb, 256, ntot * sizeof(double), p->stream>>>(p->g, og, tb, pos, vel, dvel, n, out_bar, mx, acc)
-    if (mode == MCPM_POS_LATTICE) { LAUNCH(MCPM_POS_LATTICE); } else { LAUNCH(MCPM_POS_ABSOLUTE); }
-#undef LAUNCH
+    StageTimer st_(ap_mode == MCPM_AP_NONE ? nullptr : p, ST_LPT, 60.0 * n);      // the mode-none light-cone call stays unbooked, as before
+#define K(MO, AP)                                                                                                                    \
+    observe_tables_vjp_kernel<MO, AP, 0><<<nb, 256, 0, p->stream>>>(p->g, og, tb, ap, pos, vel, dvel, n, out_bar, mx, acc);              \
+    observe_tables_vjp_kernel<MO, AP, 1><<<nb, 256, ntot * sizeof(double), p->stream>>>(p->g, og, tb, ap, pos, vel, dvel, n, out_bar, mx, acc)
+    OBS_DISPATCH(K, mode, ap_mode);
+#undef K
     // kinds 0, 1, 2 = chi, g, f (the scale kernel's last two boundaries coincide with the end)
     lc_scale_kernel<<<(unsigned)((ntot + 255) / 256), 256, 0, p->stream>>>(acc, mx, (int)ntot, nchi, nchi + ngrow, (int)ntot, (int)ntot, table_bar);
     MCPM_LAUNCH_CHECK(p, "observe_tables_vjp_kernel");
     return MCPM_OK;
+}
+
+int mcpm_observe_pos_tables_vjp_f32(mcpm_plan *p, const float *pos, const float *vel, const float *dvel, int64_t n, int mode,
+                                    const float *geom, int flags, const double *tables, int nchi, int ngrow, const float *out_bar,
+                                    double *table_bar) {
+    if (!p) return MCPM_E_ARG;
+    MCPM_REQUIRE(p, (flags & 2) && tables && nchi >= 2 && ngrow >= 2, MCPM_E_ARG, "mcpm_observe_pos_tables_vjp_f32: light cone only (flags bit 1, tables)");
+    return mcpm_observe_pos_ap_tables_vjp_f32(p, pos, vel, dvel, n, mode, geom, flags, tables, nchi, ngrow, MCPM_AP_NONE, 1., 1., nullptr, 0, 0,
+                                              out_bar, table_bar);
 }
 
 }  // extern "C"

@@ -142,7 +142,9 @@ class FieldLevelLogDensity:
     fixed    : name -> value for the base parameters that are not sampled; between them `latents` and `fixed` must
                provide Omega_m, sigma8, the eight bias parameters, ngbars, s_e, s_ed, s_e2.  The six PNG parameters
                (bricks.PNG_KEYS: fNL, fNL_bp, fNL_bpd, fNL_bpd2, fNL_bps2, fNL_bn2p) may appear in either; a missing one is
-               fixed at 0.  They reach the model only when `fwd.png_type` is set.  The stochastic term s_ep * phi of the
+               fixed at 0.  They reach the model only when `fwd.png_type` is set.  The Alcock-Paczynski parameters alpha_iso, alpha_ap
+               (bricks.AP_KEYS; the reference's prior: truncated normal, loc 1, scale 0.1, low 0, model.py:189-204) may appear in
+               either as well; a missing one is fixed at 1.  They are read only when `fwd.ap_auto is False`.  The stochastic term s_ep * phi of the
                reference's likelihood (model.py:894) is not built.
     make_cosmo(base) -> cosmology object (default: Planck18 with Omega_c = Omega_m - Omega_b and sigma8)
     """
@@ -390,7 +392,10 @@ class FieldLevelLogDensity:
         png = {k: float(base.get(k, 0.0)) for k in bricks.PNG_KEYS} if fwd.png_type is not None else None
         # Omega_m sampled: the forward model makes the two evaluations of the growth-table Jacobian as soon as it has queued its kernels
         fwd.cosmo_fd_params = ("Omega_m",) if "Omega_m" in self.latents else None
-        gxy, ctx = fwd.evolve(cosmo, bias, white, return_ctx=True) if png is None else fwd.evolve(cosmo, bias, white, png=png, return_ctx=True)
+        kw = {} if png is None else {"png": png}
+        if getattr(fwd, "ap_auto", None) is False:
+            kw["ap"] = {k: float(base.get(k, 1.0)) for k in bricks.AP_KEYS}
+        gxy, ctx = fwd.evolve(cosmo, bias, white, return_ctx=True, **kw)
         # likelihood (model.py:852-866, :893-908): per-cell count multiplier from the shells' mean densities
         rcounts = np.atleast_1d(np.asarray(base["ngbars"], dtype=np.float64)) * fwd.cell_length ** 3
         rc_ext = torch.from_numpy(np.append(rcounts, 1.0).astype(np.float32)).to(gxy.device)
@@ -465,6 +470,8 @@ class FieldLevelLogDensity:
             grad["ngbars_"] = ngb_prior_grad + ngb_bar * ngb_dbase
         base_bar = {k: 0.0 for k in bricks.PNG_KEYS}      # (without png_type the model does not read them)
         base_bar.update(g.get("png", {}))
+        base_bar.update({k: 0.0 for k in bricks.AP_KEYS})      # (read only with ap_auto = False)
+        base_bar.update(g.get("ap", {}))
         base_bar.update(g["bias"])
         base_bar.update(stoch_bar)
         base_bar["sigma8"] = g["sigma8"]

@@ -2,10 +2,12 @@
 
 Built branch: bias_type 'lagrangian', evolution 'lpt' (scalar a_obs or light cone), 'nbody' (scalar a_obs, as the
 reference asserts) or 'kaiser' (flat sky, scalar a_obs: bricks.py:170-198), png_type None, 'fNL' or 'bias' (local primordial
-non-Gaussianity: `evolve(..., png={'fNL': ..., ...})`, model.py:688, :751-758), ap_auto None, kernel_type 'rectangular', linear power from a table (`lin_kpow`,
+non-Gaussianity: `evolve(..., png={'fNL': ..., ...})`, model.py:688, :751-758), ap_auto None, True or False (Alcock-Paczynski:
+model.py:64, :787-794; `evolve(..., ap={'alpha_iso': ..., 'alpha_ap': ...})` for False), kernel_type 'rectangular', linear power from a table (`lin_kpow`,
 bricks.py:75-77) or, with lin_kpow = None, from the Eisenstein-Hu fit of the current cosmology (bricks.py:72-74; power.py).
 Priors, likelihood and samplers: logdensity.py, samplers.py.  Not built: Eulerian bias, the stochastic term s_ep * phi of the
-likelihood (model.py:894), PNG on the light-cone / curved-sky Kaiser forms.
+likelihood (model.py:894), PNG on the light-cone / curved-sky Kaiser forms, Alcock-Paczynski in the Kaiser model (model.py:703-729
+computes the moved positions and discards them), `ap_auto_absdetjac` and `rsd_ap_auto` (no live call site in the reference).
 
     fwd = FieldLevelForward(final_shape=(64, 64, 64), cell_length=20., box_center=(0, 0, 2000.), evolution='nbody',
                             a_obs=0.7, lin_kpow=(ks, pows))
@@ -15,7 +17,7 @@ likelihood (model.py:894), PNG on the light-cone / curved-sky Kaiser forms.
 Chain (every arrow is a HIP kernel sequence of libmcpm.so, each with its VJP):
 white_mesh -white2lin-> init_mesh -chreshape-> evol mesh -lagrangian_bias-> (weights, dvel, phi); [-add_png(phi)-> -chreshape to
 init_shape and back->] -lpt | nbody_bf-> (pos, vel)
--observe_pos (los, rsd)-> pos on init_shape -nufft(weights, paint_shape)-> spectrum -chreshape-> -irfftn-> gxy_mesh.
+-observe_pos (los, rsd, Alcock-Paczynski)-> pos on init_shape -nufft(weights, paint_shape)-> spectrum -chreshape-> -irfftn-> gxy_mesh.
 """
 from __future__ import annotations
 
@@ -35,7 +37,7 @@ class FieldLevelForward:
     def __init__(self, final_shape=(64, 64, 64), cell_length=20., box_center=(0., 0., 0.), box_rotvec=(0., 0., 0.),
                  evolution='lpt', nbody_a_start=0., nbody_n_steps=10, lpt_order=2, paint_order=2, paint_deconv=True,
                  init_oversamp=3 / 2, evol_oversamp=7 / 4, ptcl_oversamp=7 / 4, paint_oversamp=7 / 4, interlace_order=2,
-                 a_obs=None, curved_sky=True, lin_kpow=None, png_type=None):
+                 a_obs=None, curved_sky=True, lin_kpow=None, png_type=None, ap_auto=None, cosmo_fid=None):
         if evolution not in ('kaiser', 'lpt', 'nbody'):
             raise ValueError("evolution must be 'kaiser', 'lpt' or 'nbody'")
         if evolution == 'kaiser' and (curved_sky or a_obs is None):
@@ -44,6 +46,14 @@ class FieldLevelForward:
         if png_type not in (None, 'fNL', 'bias'):
             raise ValueError("png_type must be None, 'fNL' or 'bias'")
         self.png_type = png_type
+        if ap_auto is not None and evolution == 'kaiser':
+            raise NotImplementedError("Alcock-Paczynski is not built for the Kaiser model: the reference's branch (model.py:703-729) "
+                                      "computes the moved positions and discards them")
+        if ap_auto and cosmo_fid is None:
+            raise ValueError("ap_auto=True needs the fiducial cosmology `cosmo_fid` (the one the catalogue was gridded with)")
+        # None: no Alcock-Paczynski; True: automatic, from the sampled and the fiducial cosmology; False: alpha_iso / alpha_ap (model.py:64)
+        self.ap_auto = None if ap_auto is None else bool(ap_auto)
+        self.cosmo_fid = cosmo_fid
         self.final_shape = tuple(int(s) for s in final_shape)
         self.cell_length = float(cell_length)
         self.box_center = np.asarray(box_center, dtype=np.float64)
@@ -189,11 +199,12 @@ class FieldLevelForward:
                 "kaiser": {"g": (1.0 + b1) * c0 + f * c1, "f": D * c1}, **extra}
 
     # ---- forward -----------------------------------------------------------------------------------------
-    def evolve(self, cosmo, bias, white_mesh, png=None, return_ctx=False):
+    def evolve(self, cosmo, bias, white_mesh, png=None, return_ctx=False, ap=None):
         """cosmo: duck-typed cosmology (Omega_m, Omega_de, Omega_k, w0, wa, sigma8, _workspace); bias: dict of the
         Lagrangian bias parameters; white_mesh: complex half-spectrum of shape r2chshape(init_shape) (what
         samp2base_mesh returns); png: dict with the keys bricks.PNG_KEYS (missing = 0), read only when the model's png_type is
-        set.  Returns gxy_mesh (paint_shape, float32 device tensor) = 1 + delta_obs.
+        set; ap: dict with 'alpha_iso', 'alpha_ap' (missing = 1), read only when the model's ap_auto is False (model.py:793).
+        Returns gxy_mesh (paint_shape, float32 device tensor) = 1 + delta_obs.
         With png_type (model.py:688, :751-758): fNL_bias -> bias weights from the GAUSSIAN evolution mesh -> add_png on it (phi is
         handed over from the bias step: three extra transforms in all) -> chreshape to init_shape and back, which cuts the modes
         phi^2 filled above the initial Nyquist -> lpt / nbody.  As in the reference, the transfer table of these two steps is the
@@ -231,8 +242,9 @@ class FieldLevelForward:
             vel = vel.reshape(-1, 3)
         # the growth-table Jacobian of cosmo_vjp: a millisecond of host work, done HERE -- the device has the whole evolution queued
         fd = self._cosmo_scalar_fd(cosmo, self.cosmo_fd_params) if (return_ctx and self.a_obs is not None and getattr(self, "cosmo_fd_params", None)) else None
+        apkw = {} if self.ap_auto is None else dict(ap_auto=self.ap_auto, ap=ap, cosmo_fid=self.cosmo_fid)
         pos_c, octx = bricks.observe_pos(cosmo, pos, vel, self.box_center, self.box_rotvec, self.box_size, self.evol_shape,
-                                         self.init_shape, a_obs=self.a_obs, curved_sky=self.curved_sky, dvel=dvel, return_ctx=True)
+                                         self.init_shape, a_obs=self.a_obs, curved_sky=self.curved_sky, dvel=dvel, return_ctx=True, **apkw)
         gxy_k = nbody.nufft(pos_c, self.init_shape, self.paint_shape, weights=w, paint_order=self.paint_order,
                             interlace_order=self.interlace_order, paint_deconv=self.paint_deconv)
         jac = float(np.divide(self.init_shape, self.ptcl_shape).prod())
@@ -248,6 +260,8 @@ class FieldLevelForward:
         """Cotangent of gxy_mesh (real, paint_shape) -> {'white_mesh': complex64 cotangent (real-pair convention),
         'bias': dict, 'sigma8': float, 'growth': cotangents of the growth scalars (see nbody.lpt_vjp / nbody_bf_vjp),
         'bias_growth': cotangent(s) of a2g(a) through the bias weights, 'gf': cotangent of a2g(a_obs) a2f(a_obs) through rsd}.
+        With ap_auto also 'ap': {'alpha_iso', 'alpha_ap'} cotangents (0 for ap_auto=True), and for ap_auto=True at fixed a_obs 'ap_chi_bar':
+        the cotangent of the chi nodes of chi2a(cosmo, r') (device float64; cosmo_vjp).
         With png_type also 'png': cotangents of the six entries of the `png` dict given to evolve (the fNL_bias reparametrisation
         chained back, its b1 / b2 share added to 'bias'), and 'trans_bar': cotangent of the transfer table's entries (cosmo_vjp)."""
         if self.evolution == 'kaiser':
@@ -261,8 +275,13 @@ class FieldLevelForward:
         kb = chreshape_vjp(kb, r2chshape(self.init_shape)) * ctx.jac
         pb, wb = nbody.nufft_vjp(ctx.pos_c, self.init_shape, ctx.w, kb, self.paint_order, self.interlace_order, self.paint_deconv,
                                  paint_shape=self.paint_shape)
-        xb, vb, dvb, gfb = bricks.observe_pos_vjp(ctx.octx, pb)
         extra = {}
+        if self.ap_auto is None:
+            xb, vb, dvb, gfb = bricks.observe_pos_vjp(ctx.octx, pb)
+        else:
+            xb, vb, dvb, gfb, extra["ap"] = bricks.observe_pos_vjp(ctx.octx, pb)
+            if self.ap_auto and self.a_obs is not None:      # the one new launch group: auto AP is the only per-particle table look-up here
+                extra["ap_chi_bar"] = bricks.observe_pos_tables_vjp(ctx.octx, pb)
         if ctx.actx is None:
             mesh_b, bias_bar, bg_bar = bricks.lagrangian_bias_vjp(ctx.bctx, wb, dvb)
         else:
@@ -278,7 +297,7 @@ class FieldLevelForward:
             png_bar, bb = bricks.fNL_bias_vjp(ctx.png_in, ctx.bias, png_bar, p=1., png_type=self.png_type)
             bias_bar["b1"] += bb["b1"]
             bias_bar["b2"] += bb["b2"]
-            extra = {"png": png_bar, "trans_bar": trans_bar}
+            extra.update({"png": png_bar, "trans_bar": trans_bar})
         mesh_b = mesh_b + mb
         init_b = chreshape_vjp(mesh_b, r2chshape(self.init_shape))
         white_b = self._power_mult(init_b, cosmo)
@@ -293,13 +312,14 @@ class FieldLevelForward:
         field on the device) the cosmology enters evolve through host float64 scalars looked up in the 128-point growth tables -- the
         BullFrog coefficients and the 2LPT start (nbody.cosmo_vjp), a2g(a_obs) in the bias weights, a2g a2f in the
         RSD -- so dL/dtheta = sum_s s_bar ds/dtheta with the table Jacobian taken by central finite differences.
+        With ap_auto=True <chi_bar, d chi / d theta> is added: the chi nodes of the Alcock-Paczynski look-up chi2a(cosmo, r'), by the
+        same central difference of the host distance table as `_cosmo_vjp_lightcone` (the fiducial table does not move).
         `params`: attribute names of the cosmology object; 'Omega_m' varies Omega_c at fixed Omega_b.  On the light cone
         (a_obs = None) the look-ups are per particle: `_cosmo_vjp_lightcone`."""
         import copy
         if self.a_obs is None:
             return self._cosmo_vjp_lightcone(ctx, grads, params, rel_eps)
         cosmo, a = ctx.cosmo, self.a_obs
-        scalars = self._cosmo_scalars
         pre = getattr(ctx, "scalar_fd", None) or {}
 
         if self.evolution == 'kaiser':
@@ -314,6 +334,7 @@ class FieldLevelForward:
         else:
             bars += [float(g["dg"])] + list(g["alpha"]) + list(g["beta"]) + [float(g["g"]), float(g["g2"]), float(g["dg2dg"])]
         bars = np.array(bars)
+        chi_bar = grads["ap_chi_bar"].cpu().numpy() if grads.get("ap_chi_bar") is not None else None
         out = {}
         for name in params:
             attr = "Omega_c" if name == "Omega_m" else name
@@ -324,10 +345,12 @@ class FieldLevelForward:
             for sgn in (+1, -1):
                 c = copy.copy(cosmo)
                 setattr(c, attr, base + sgn * h)
-                vals.append(cached[len(vals)] if cached is not None else scalars(c))
+                vals.append(cached[len(vals)] if cached is not None else self._cosmo_scalars_chi(c))
                 if self.lin_kpow is None:      # the Eisenstein-Hu shape moves with the cosmology: init_mesh = white sqrt(P)
                     inits.append(self._power_mult(ctx.white, c))
-            out[name] = float(np.dot(bars, (vals[0] - vals[1]) / (2 * h))) + self._trans_term(cosmo, grads, attr, base, h)
+            out[name] = float(np.dot(bars, (vals[0][0] - vals[1][0]) / (2 * h))) + self._trans_term(cosmo, grads, attr, base, h)
+            if chi_bar is not None:
+                out[name] += float(np.dot(chi_bar, (vals[0][1] - vals[1][1]) / (2 * h)))
             if inits:
                 out[name] += float((grads["init_bar"].conj() * (inits[0] - inits[1])).real.sum().item()) / (2 * h)
         cosmo._workspace = {}
@@ -362,8 +385,14 @@ class FieldLevelForward:
             out += [dg] + list(al) + list(be) + list(ls)
         return np.array(out)
 
+    def _cosmo_scalars_chi(self, c):
+        """(`_cosmo_scalars`, chi nodes ascending of the distance table or None): the second entry only with ap_auto=True, where the
+        Alcock-Paczynski look-up chi2a(cosmo, r') is the one per-particle table dependence at fixed a_obs."""
+        s = self._cosmo_scalars(c)
+        return s, (nbody._dist_cache(c)["chi"][::-1].copy() if (self.ap_auto and self.evolution != 'kaiser') else None)
+
     def _cosmo_scalar_fd(self, cosmo, params, rel_eps=1e-5):
-        """{(name, rel_eps): (scalars at +h, scalars at -h)}: the two evaluations of cosmo_vjp's central difference.  Host work of about
+        """{(name, rel_eps): ((scalars, chi nodes) at +h, the same at -h)}: the two evaluations of cosmo_vjp's central difference.  Host work of about
         a millisecond (two growth-table solves per parameter) that `evolve` does right after it has queued the forward pass, while the
         device runs it; left to cosmo_vjp it sits at the very end of a gradient, with the device idle (`cosmo_fd_params`)."""
         import copy
@@ -376,7 +405,7 @@ class FieldLevelForward:
             for sgn in (+1, -1):
                 c = copy.copy(cosmo)
                 setattr(c, attr, base + sgn * h)
-                pair.append(self._cosmo_scalars(c))
+                pair.append(self._cosmo_scalars_chi(c))
             out[(name, rel_eps)] = tuple(pair)
         return out      # (the copies carry their own tables: `cosmo`'s cached ones stay for the rest of evolve)
 
@@ -393,7 +422,8 @@ class FieldLevelForward:
         """Cotangents of those tables (dict of float64 arrays): the Lagrangian look-ups a_q = chi2a(r0_q) -> a2g (bias weights,
         model.py:756, and lpt), a2g2, a2dg2dg (lpt, nbody.py:652-666) contracted with the per-particle cotangents of
         `evolve_vjp` (mcpm_lightcone_tables_vjp_f32), plus the observation-side a2g a2f at the evolved positions
-        (model.py:781-784; mcpm_observe_pos_tables_vjp_f32)."""
+        (model.py:781-784; mcpm_observe_pos_tables_vjp_f32) and, with ap_auto=True, the chi2a(cosmo, r') of ap_auto in the same chi bar
+        (mcpm_observe_pos_ap_tables_vjp_f32)."""
         cosmo = ctx.cosmo
         d, gt = nbody._dist_cache(cosmo), nbody._growth_cache(cosmo)
         nchi, ng = len(d["chi"]), len(gt["a"])
@@ -408,9 +438,7 @@ class FieldLevelForward:
         plan.call("mcpm_lightcone_tables_vjp_f32", nbody._ptr(self._r0), n, nbody._ptr(tabs), nchi, ng, nbody._ptr(gB), nbody._ptr(g2B),
                   nbody._ptr(dB), nbody._ptr(tbL))
         o = ctx.octx
-        tbO = torch.empty(nchi + 2 * ng, dtype=torch.float64, device=dev)
-        o.plan.call("mcpm_observe_pos_tables_vjp_f32", nbody._ptr(o.p), nbody._ptr(o.v), nbody._ptr(o.dv), o.n, o.mode, o.geom, o.flags,
-                    nbody._ptr(o.tables), o.nchi, o.ngrow, nbody._ptr(grads["obs_bar"]), nbody._ptr(tbO))
+        tbO = bricks.observe_pos_tables_vjp(o, grads["obs_bar"])      # with ap_auto=True the Alcock-Paczynski look-up arrives in its chi bar
         L, O = tbL.cpu().numpy(), tbO.cpu().numpy()
         out = {"chi": L[:nchi] + O[:nchi], "g": L[nchi:nchi + ng] + O[nchi:nchi + ng], "g2": L[nchi + ng:nchi + 2 * ng],
                "f": L[nchi + 2 * ng:nchi + 3 * ng] + O[nchi + ng:], "f2": L[nchi + 3 * ng:]}

@@ -14,6 +14,9 @@ Schema (key: meaning; * = mandatory)
     paint_order, interlace_order, paint_deconv, kernel_type, cell_budget, padding
     lin_kpow                                 (2, N): k and P(k) / sigma8^2
     white_mesh | white_fake                  whitened initial conditions, half-spectrum at r2chshape(init_shape)
+    png_type                                 'fNL' | 'bias' (absent / None: no primordial non-Gaussianity)
+    ap_auto                                  Alcock-Paczynski (model.py:64): True automatic (the catalogue was gridded with cosmo_fid),
+                                             False alpha_iso / alpha_ap parameters, absent / None: none
 
 Container: HDF5 through h5py, as the reference's `h5save` / `h5load` (utils.py:76-160) lay it out: one dataset per key,
 nested dicts as groups, None left out.  h5py is an optional dependency (it is absent from the build image): `.npz` files with
@@ -25,7 +28,7 @@ import numpy as np
 
 MANDATORY = ("cell_length", "box_center", "box_rotvec", "init_oversamp", "paint_oversamp", "cosmo_fid", "count_mesh")
 OPTIONAL = ("selec_mesh", "mask_mesh", "n_tracers", "n_randoms", "a_obs", "curved_sky", "paint_order", "interlace_order",
-            "paint_deconv", "kernel_type", "cell_budget", "padding", "lin_kpow", "white_mesh", "white_fake", "png_type")
+            "paint_deconv", "kernel_type", "cell_budget", "padding", "lin_kpow", "white_mesh", "white_fake", "png_type", "ap_auto")
 
 
 def _flatten(d, prefix=""):
@@ -123,6 +126,17 @@ def model_arguments(reg, **overrides):
             fwd[k] = reg[k]
     if reg.get("png_type") not in (None, "None"):      # 'fNL' or 'bias' (model.py:84); absent or None: no primordial non-Gaussianity
         fwd["png_type"] = str(reg["png_type"])
+    if reg.get("ap_auto") not in (None, "None"):       # True / False (model.py:64); absent or None: no Alcock-Paczynski
+        from . import bricks
+        v = reg["ap_auto"]
+        if isinstance(v, str):                         # a container that hands strings back: 'True' / 'False', nothing else
+            if v not in ("True", "False"):
+                raise ValueError(f"register: ap_auto must be True, False or None, got {v!r}")
+            v = v == "True"
+        fwd["ap_auto"] = bool(v)
+        fid = bricks.Planck18(sigma8=float(reg["cosmo_fid"]["sigma8"]))      # the cosmology register_catalog gridded the catalogue with
+        fid.Omega_c = float(reg["cosmo_fid"]["Omega_m"]) - fid.Omega_b
+        fwd["cosmo_fid"] = fid
     if reg.get("kernel_type", "rectangular") != "rectangular":
         raise NotImplementedError("FieldLevelForward paints with kernel_type='rectangular' (nbody.paint itself takes 'kaiser_bessel')")
     if reg.get("lin_kpow") is not None:
