@@ -67,7 +67,7 @@ int mcpm_plan_slab_oob(mcpm_plan *plan, int64_t *count);
 int mcpm_plan_destroy(mcpm_plan *plan);
 const char *mcpm_last_error(const mcpm_plan *plan); /* plan may be NULL: last error of a failed create */
 /* ABI revision string; the Python loader (montecosmo_amd/_lib.py) refuses a library that reports another one. */
-#define MCPM_ABI_VERSION "mcpm 0.9 (gfx950)"
+#define MCPM_ABI_VERSION "mcpm 0.10 (gfx950)"
 const char *mcpm_version(void);
 /* Tiled CIC paints (montecosmo_amd/csrc/paint_tiled.hip).  A tile's window is a box of lattice points per axis -- chosen on the device
    for every input and every tile from the displacement field around it, or (16 + 2 halo + 1)^3 around the tile's bulk displacement when a
@@ -449,6 +449,31 @@ int mcpm_nbody_bf_vjp_f32(mcpm_plan *plan, const float *init_mesh, int n_steps, 
                           const double *beta, double dg, const double *lpt_scalars, int lpt_order,
                           int paint_order, const float *ckpt, const float *pos_bar, const float *vel_bar,
                           float *init_mesh_bar, double *scalar_bars);
+
+/* ---- likelihoods besides 'quad_gauss' (montecosmo/model.py:872-886, :911-932), value and gradient in one pass ---------------- */
+#define MCPM_LIK_SHASH 0
+#define MCPM_LIK_POISSON 1
+/* Real-space families over n cells (the plan lends its stream and reduction scratch; n need not be its mesh size).
+     MCPM_LIK_SHASH  : delta = count / selec - 1, scale1 = (|s_e + s_ed delta| + 1e-9) sqrt(selec), scale2 = s_e2 sqrt(selec),
+                       obs ~ SinhArcsinh(mean count, std sqrt(scale1^2 + 2 scale2^2), skewness 3.540 scale2 / scale1,
+                       tailweight 1 + 5.884 (scale2 / scale1)^2), standardised by a 20-node Gauss-Hermite rule per cell (utils.py:392-450).
+     MCPM_LIK_POISSON: obs ~ Poisson(|count|) (temp = 1); |count| = 0 gives lp = -inf (obs > 0) or 0 (obs = 0) and a zero gradient;
+                       selec and the three scalars are not read.
+   selec: a mesh, or NULL for the scalar selec_scalar; mask (bytes, non-zero = observed cell, may be NULL): unobserved cells are given
+   safe inputs before any arithmetic and are removed by selection.  count_bar (n floats) = d lp / d count at fixed selec, through the
+   location and through delta; sqsel_bar (n floats, may be NULL) = d lp / d sqrt(selec) at fixed count.  sums_out (device, 5 doubles):
+   lp, d lp / d s_e, d s_ed, d s_e2, sum of sqsel_bar -- fixed-order float64 sums, bitwise equal call after call. */
+int mcpm_lik_real_f32(mcpm_plan *plan, int family, int64_t n, const float *obs, const float *count, const float *selec,
+                      float selec_scalar, const unsigned char *mask, float s_e, float s_ed, float s_e2, float *count_bar,
+                      float *sqsel_bar, double *sums_out);
+/* 'fourier_gauss' on the plan's mesh (all sides even): obs_rg = cgh2rg(rfftn(count_obs)) (real layout, M floats),
+   Y = rfftn(count) (plain half-spectrum); obs_rg[r] ~ Normal(cgh2rg(Y)[r], sigma), sigma = cgh2rg_amp(|s_e + s_k2e k^2 +
+   s_kmu2e (k mu)^2|) sqrt(selec), k in h/Mpc from the mode index and the box size (no k table), mu = k . los / |k| (0 at k = 0),
+   selec a scalar.  Y_bar: cotangent of Y in the real-pair convention (dlp = sum over stored modes of Y_bar.re dY.re + Y_bar.im dY.im);
+   every stored mode is written once, the redundant mirror modes of the kz = 0 and kz = nz/2 faces receive zero.  sums_out
+   (device, 5 doubles): lp, d lp / d s_e, d s_k2e, d s_kmu2e, d lp / d sqrt(selec). */
+int mcpm_lik_fourier_f32(mcpm_plan *plan, const float *Y, const float *obs_rg, float box_x, float box_y, float box_z, float los_x,
+                         float los_y, float los_z, float selec, float s_e, float s_k2e, float s_kmu2e, float *Y_bar, double *sums_out);
 
 /* ---- host-side float64 growth tables (nbody.py:679-745) ------------------------------------- */
 /* rg2cgh / cgh2rg with norm = "backward" (montecosmo/utils.py:785-921): a real Gaussian tensor (nx, ny, nz), all sizes

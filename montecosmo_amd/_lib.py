@@ -14,6 +14,7 @@ LIB_PATH = os.environ.get("MCPM_LIB") or os.path.join(_HERE, "libmcpm.so")      
 OK = 0
 POS_ABSOLUTE, POS_LATTICE = 0, 1
 AP_NONE, AP_AUTO, AP_PARAM = 0, 1, 2
+LIK_SHASH, LIK_POISSON = 0, 1
 FD_INF, FD_2, FD_4 = 0, 2, 4
 
 _f32p = C.c_void_p  # device pointers travel as integers
@@ -75,6 +76,9 @@ SIGNATURES = {
     "mcpm_png_weights_f32": (C.c_int, [C.c_void_p, C.c_int64, _f32p, _f32p, _f32p, _f32p, _f32p, C.c_float, C.POINTER(C.c_float), _f32p, C.c_void_p]),
     "mcpm_png_weights_vjp_f32": (C.c_int, [C.c_void_p, C.c_int64, _f32p, _f32p, _f32p, _f32p, _f32p, C.c_float, C.POINTER(C.c_float), _f32p,
                                            _f32p, _f32p, _f32p, _f32p, _f32p, C.c_void_p]),
+    "mcpm_lik_real_f32": (C.c_int, [C.c_void_p, C.c_int, C.c_int64, _f32p, _f32p, _f32p, C.c_float, C.c_void_p, C.c_float, C.c_float, C.c_float,
+                                    _f32p, _f32p, C.c_void_p]),
+    "mcpm_lik_fourier_f32": (C.c_int, [C.c_void_p, _f32p, _f32p] + [C.c_float] * 10 + [_f32p, C.c_void_p]),
     "mcpm_lpt_combine_f32": (C.c_int, [C.c_void_p, _f32p, _f32p, _f32p, C.c_int64, _f32p, _f32p]),
     "mcpm_lpt_combine_vjp_f32": (C.c_int, [C.c_void_p, _f32p, _f32p, _f32p, C.c_int64, _f32p, _f32p, _f32p]),
     "mcpm_observe_pos_f32": (C.c_int, [C.c_void_p, _f32p, _f32p, _f32p, C.c_int64, C.c_int, C.POINTER(C.c_float), C.c_int,
@@ -163,7 +167,7 @@ SIGNATURES = {
 }
 
 
-ABI_VERSION = "mcpm 0.9 (gfx950)"   # must equal mcpm_version() of the loaded library (include/mcpm.h MCPM_ABI_VERSION)
+ABI_VERSION = "mcpm 0.10 (gfx950)"   # must equal mcpm_version() of the loaded library (include/mcpm.h MCPM_ABI_VERSION)
 
 
 def _load():

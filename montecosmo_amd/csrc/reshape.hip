@@ -10,6 +10,7 @@
 // Here every output element gathers its (at most 8) sources directly; the VJP is a gather too: every input element collects the terms of
 // the outputs that list it (chreshape_vjp_gather_kernel).
 #include "mcpm_internal.h"
+#include "cgh_dev.h"
 
 namespace {
 
@@ -169,47 +170,6 @@ __global__ __launch_bounds__(256) void chreshape_vjp_gather_kernel(RS r, const f
 //                   i > hx: re x[nx - i, j, k]          im -x[hx + nx - i, j, k]
 //                   i in {0, hx}: re sqrt2 x[i, j, k]   im 0
 // all times sqrt(M / 2).
-struct CghSrc {
-    int64_t re, im;   // flat indices into the real tensor (im < 0: none)
-    float wre, wim;
-};
-__device__ __forceinline__ CghSrc cgh_source(int nx, int ny, int nz, int i, int j, int k) {
-    const int hx = nx / 2, hy = ny / 2, hz = nz / 2;
-    auto at = [&](int a, int b, int c) { return ((int64_t)a * ny + b) * nz + c; };
-    CghSrc r;
-    r.wre = 1.f;
-    r.wim = 1.f;
-    if (k > 0 && k < hz) {
-        r.re = at(i, j, k);
-        r.im = at(i, j, hz + k);
-    } else if (j != 0 && j != hy) {
-        if (j < hy) {
-            r.re = at(i, j, k);
-            r.im = at(i, hy + j, k);
-        } else {
-            const int mi = i ? nx - i : 0;
-            r.re = at(mi, ny - j, k);
-            r.im = at(mi, hy + ny - j, k);
-            r.wim = -1.f;
-        }
-    } else if (i != 0 && i != hx) {
-        if (i < hx) {
-            r.re = at(i, j, k);
-            r.im = at(hx + i, j, k);
-        } else {
-            r.re = at(nx - i, j, k);
-            r.im = at(hx + nx - i, j, k);
-            r.wim = -1.f;
-        }
-    } else {
-        r.re = at(i, j, k);
-        r.im = -1;
-        r.wre = 1.41421356237309505f;
-        r.wim = 0.f;
-    }
-    return r;
-}
-
 // MODE 0: out = rg2cgh(in real).  MODE 1 (VJP): in = cotangent of the complex output, out = cotangent of the real
 // tensor (zeroed by the caller, scattered with atomics: face modes share their source with their Hermitian mirror)
 template <int MODE>
@@ -238,24 +198,13 @@ __global__ __launch_bounds__(256) void rg2cgh_kernel(int nx, int ny, int nz, flo
 template <bool AMP>
 __global__ __launch_bounds__(256) void cgh2rg_kernel(int nx, int ny, int nz, float scale, const float *__restrict__ in,
                                                      float *__restrict__ out) {
-    const int hx = nx / 2, hy = ny / 2, hz = nz / 2, nzc = hz + 1;
     const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x, n = (int64_t)nx * ny * nz;
     if (idx >= n) return;
     const int z = (int)(idx % nz);
     const int64_t t = idx / nz;
     const int y = (int)(t % ny), x = (int)(t / ny);
-    auto at = [&](int a, int b, int c) { return 2 * (((int64_t)a * ny + b) * nzc + c); };
-    float v;
-    if (z != 0 && z != hz) {
-        v = z < hz ? in[at(x, y, z)] : (AMP ? in[at(x, y, z - hz)] : in[at(x, y, z - hz) + 1]);
-    } else if (y != 0 && y != hy) {
-        const int mx_ = x ? nx - x : 0;
-        v = y < hy ? in[at(mx_, ny - y, z)] : (AMP ? in[at(mx_, ny + hy - y, z)] : -in[at(mx_, ny + hy - y, z) + 1]);
-    } else if (x != 0 && x != hx) {
-        v = x < hx ? in[at(nx - x, y, z)] : (AMP ? in[at(nx + hx - x, y, z)] : -in[at(nx + hx - x, y, z) + 1]);
-    } else {
-        v = in[at(x, y, z)] * (AMP ? 1.f : 0.70710678118654752f);
-    }
+    const CghRead r = cgh2rg_read(nx, ny, nz, x, y, z);      // the rule itself: cgh_dev.h
+    const float v = AMP ? in[2 * r.mode] : in[2 * r.mode + r.part] * r.w;
     out[idx] = scale * v;
 }
 

@@ -15,6 +15,15 @@ Bounded latents (`low` / `high` in their config) use the reference's detruncated
 (utils.py:189-226, :267-311) within |x| < 12 sigma; latents without `loc` / `scale` have a uniform prior on [low, high] in the
 same parametrisation (DetruncUnif, utils.py:314-353).
 
+Other likelihoods (`lik_type`; value and gradient in one HIP kernel each, csrc/likelihood.hip, on the same count / selec):
+    'shash'         obs[mask] ~ SinhArcsinh(count, sqrt(scale1^2 + 2 scale2^2), 3.540 scale2 / scale1, 1 + 5.884 (scale2 / scale1)^2) with the
+                    scales of 'quad_gauss' (model.py:911-932; the default of the reference's drivers)
+    'poisson'       obs[mask] ~ Poisson(|count|) (model.py:872-873)
+    'fourier_gauss' cgh2rg(rfftn(obs)) ~ Normal(cgh2rg(rfftn(count)), cgh2rg_amp(|s_e + s_k2e k^2 + s_kmu2e (k mu)^2|) sqrt(selec)), full sky and
+                    scalar selection only (model.py:875-886).
+Not built: 'two_quad_gauss' (a 64-node quadrature), the s_ep * phi term of scale1 (phi would have to be carried out of `evolve`), temp != 1;
+'quad_gauss' itself stays on its torch path.
+
 The gradient is hand-derived end to end: elementwise likelihood / prior terms here (device tensors), the mesh and
 particle operators through their `*_vjp` twins -- no autodiff framework.
 """
@@ -25,7 +34,9 @@ import math
 import numpy as np
 import torch
 
-from . import nbody, bricks
+import ctypes as C
+
+from . import nbody, bricks, _lib
 from .utils import r2chshape, chreshape, chreshape_vjp, rg2cgh, rg2cgh_vjp, cgh2rg
 
 LOG2PI = math.log(2 * math.pi)
@@ -151,9 +162,12 @@ class FieldLevelLogDensity:
 
     COSMO = ("Omega_m", "sigma8")
     STOCH = ("s_e", "s_ed", "s_e2")
+    # stochastic parameters each likelihood reads; one it does not read need not be supplied, and gets a zero likelihood gradient if sampled
+    LIK_STOCH = {"quad_gauss": STOCH, "shash": STOCH, "fourier_gauss": ("s_e", "s_k2e", "s_kmu2e"), "poisson": ()}
+    ALL_STOCH = ("s_e", "s_ed", "s_e2", "s_k2e", "s_kmu2e")
 
     def __init__(self, fwd, count_obs, latents, fixed, precond="fourier", make_cosmo=None, selec_mesh=None, mask_mesh=None,
-                 redges=None, n_rbins=None):
+                 redges=None, n_rbins=None, lik_type="quad_gauss"):
         """selec_mesh: real, fwd.paint_shape (None = 1); mask_mesh: bool, final_shape, True = observed cell (None = all);
         ngbars: fixed (a scalar or one mean density per radial shell) or a latent whose config entries are broadcast to the
         n_rbins shells (model.py:1087-1103; sample key 'ngbars_' is then an array); redges: shell edges (default: equal-width
@@ -161,7 +175,13 @@ class FieldLevelLogDensity:
         max(int((rmax - rmin) / (sqrt(3) cell)), 1)).  count_obs is the full final mesh (only observed cells are used)."""
         if precond not in ("fourier", "real", "kaiser"):
             raise ValueError(f"Unknown preconditioning type: {precond}")
-        self.fwd, self.precond = fwd, precond
+        if lik_type not in self.LIK_STOCH:
+            raise ValueError(f"Unknown likelihood type: {lik_type} (built: {sorted(self.LIK_STOCH)})")
+        if lik_type == "fourier_gauss" and mask_mesh is not None:
+            raise ValueError("Fourier likelihood not implemented for cut-sky.")      # model.py:876
+        if lik_type == "fourier_gauss" and selec_mesh is not None:
+            raise ValueError("Fourier likelihood takes a scalar selection: the per-mode scale does not broadcast with a selection mesh")
+        self.fwd, self.precond, self.lik_type = fwd, precond, lik_type
         latents = dict(latents)
         self._ngb_conf = latents.pop("ngbars", None)
         self._n_rbins = n_rbins
@@ -175,7 +195,7 @@ class FieldLevelLogDensity:
                 c.setdefault("loc_fid", (c["low"] + c["high"]) / 2)              # model.py:1081-1084
                 c.setdefault("scale_fid", (c["high"] - c["low"]) / 12 ** .5)
         self.fixed = dict(fixed)
-        need = set(self.COSMO) | set(bricks.BIAS_KEYS) | {"ngbars"} | set(self.STOCH)
+        need = set(self.COSMO) | set(bricks.BIAS_KEYS) | {"ngbars"} | set(self.LIK_STOCH[lik_type])
         missing = need - set(self.latents) - set(self.fixed) - ({"ngbars"} if self._ngb_conf is not None else set())
         if missing:
             raise ValueError(f"parameters neither sampled nor fixed: {sorted(missing)}")
@@ -184,6 +204,15 @@ class FieldLevelLogDensity:
         self.make_cosmo = make_cosmo or self._planck
         self._setup_selection(selec_mesh, mask_mesh, redges)
         self.scale, self.transfer = self._precond_scale_and_transfer()
+        if lik_type == "fourier_gauss":      # the observation in the real layout, once (model.py:885 applied to the data)
+            self.los_fid = self._los_fid()
+            self.obs_rg = cgh2rg(nbody.rfftn(self.count_obs))
+
+    def _los_fid(self):
+        """Line of sight in cell coordinates (model.py:607-608), as the 'kaiser' preconditioning takes it."""
+        fwd = self.fwd
+        los = nbody.safe_div(fwd.box_center, np.linalg.norm(fwd.box_center))
+        return bricks.rot_matrix(fwd.box_rotvec).T @ los
 
     @staticmethod
     def _planck(base):
@@ -299,13 +328,100 @@ class FieldLevelLogDensity:
         ks, pows = fwd.kpow(cosmo_fid)
         pmesh = np.interp(kmesh.reshape(-1), ks, pows * float(fid["sigma8"]) ** 2, left=0., right=0.).reshape(kmesh.shape)
         pmesh *= unit ** 2                                                                # power in cell units
-        var_fid = float(fid["s_e"]) / (self.ngbar_mean * fwd.cell_length ** 3 * self.selec_fid)   # model.py:602, :609, :1140
+        var_fid = float(fid.get("s_e", 1.0)) / (self.ngbar_mean * fwd.cell_length ** 3 * self.selec_fid)   # model.py:602, :609, :1140 ('poisson' reads no s_e: 1)
         scale_k = (1 + boost ** 2 / var_fid * pmesh) ** .5
         cosmo_fid._workspace = {}
         dev = self.count_obs.device
         transfer = torch.from_numpy((unit / scale_k).astype(np.float32)).to(dev)
         scale = cgh2rg(torch.from_numpy(scale_k.astype(np.complex64)).to(dev), norm="amp")
         return scale, transfer
+
+    def _lik_hip(self, base, cm, selec, want_sqsel):
+        """The likelihood term of 'shash', 'poisson' or 'fourier_gauss' on the mean counts `cm` (final mesh) and the selection (a mesh or a
+        float).  Returns (lp, count_bar = d lp / d cm at fixed selec, the cotangents of the stochastic parameters, sqsel_bar = d lp / d sqrt(selec)
+        per cell at fixed count (real-space families with `want_sqsel`, else None), its sum, the selection made safe outside the mask)."""
+        plan = nbody.get_plan(self.final_shape)
+        sums = torch.empty(5, dtype=torch.float64, device=cm.device)
+        cm = cm.contiguous()
+        if self.lik_type == "fourier_gauss":
+            Y = nbody.rfftn(cm)
+            Yb = torch.empty_like(Y)
+            box, los = [float(v) for v in self.fwd.box_size], [float(v) for v in self.los_fid]
+            plan.call("mcpm_lik_fourier_f32", nbody._ptr(Y), nbody._ptr(self.obs_rg), *box, *los, float(selec), float(base["s_e"]),
+                      float(base["s_k2e"]), float(base["s_kmu2e"]), nbody._ptr(Yb), nbody._ptr(sums))
+            Yb[..., 1:self.final_shape[-1] // 2] *= 0.5      # adjoint of rfftn, real-pair convention: the C2R counts these modes twice
+            cm_bar = torch.empty(self.final_shape, dtype=torch.float32, device=cm.device)
+            plan.call("mcpm_fft_c2r", nbody._ptr(Yb), nbody._ptr(cm_bar), 1)
+            v = sums.cpu().numpy()
+            return float(v[0]), cm_bar, {"s_e": float(v[1]), "s_k2e": float(v[2]), "s_kmu2e": float(v[3])}, None, float(v[4]), selec
+        mesh_sel = torch.is_tensor(selec)
+        if mesh_sel:
+            selec = (selec if self.mask is None else torch.where(self.mask, selec, torch.ones_like(selec))).contiguous()
+        shash = self.lik_type == "shash"
+        cm_bar = torch.empty_like(cm)
+        qb = torch.empty_like(cm) if (want_sqsel and mesh_sel) else None
+        st = [float(base[k]) if shash else 0.0 for k in self.STOCH]
+        plan.call("mcpm_lik_real_f32", _lib.LIK_SHASH if shash else _lib.LIK_POISSON, C.c_int64(cm.numel()), nbody._ptr(self.count_obs),
+                  nbody._ptr(cm), nbody._ptr(selec if mesh_sel else None), 1.0 if mesh_sel else float(selec), nbody._ptr(self.mask), *st,
+                  nbody._ptr(cm_bar), nbody._ptr(qb), nbody._ptr(sums))
+        v = sums.cpu().numpy()
+        stoch_bar = {"s_e": float(v[1]), "s_ed": float(v[2]), "s_e2": float(v[3])} if shash else {}
+        return float(v[0]), cm_bar, stoch_bar, qb, float(v[4]), selec
+
+    def mean_counts(self, sample):
+        """(count, selec) of the likelihood at `sample` (model.py:850-866): the mean counts on the final mesh, and the selection there (a mesh
+        with a selection mesh, else the float mean(rcounts))."""
+        fwd = self.fwd
+        base = self.base_params(sample)
+        w = nbody._f32(sample["white_mesh_"], fwd.init_shape)
+        white = (nbody.rfftn(w) if self.precond == "real" else rg2cgh(w)) * self.transfer
+        kw = {"png": {k: float(base.get(k, 0.0)) for k in bricks.PNG_KEYS}} if fwd.png_type is not None else {}
+        if getattr(fwd, "ap_auto", None) is False:
+            kw["ap"] = {k: float(base.get(k, 1.0)) for k in bricks.AP_KEYS}
+        gxy = fwd.evolve(self.make_cosmo(base), {k: base[k] for k in bricks.BIAS_KEYS}, white, **kw)
+        rcounts = np.atleast_1d(np.asarray(base["ngbars"], dtype=np.float64)) * fwd.cell_length ** 3
+        rc = torch.from_numpy(np.append(rcounts, 1.0).astype(np.float32)).to(gxy.device)[self.shell]
+        cm = self._down(gxy if self.selec_mesh is None else gxy * self.selec_mesh) * rc
+        return cm, (float(rcounts.mean()) if self.sel_down is None else (self.sel_down * rc).abs())
+
+    def draw_counts(self, sample, seed=0):
+        """One observed count mesh drawn from the likelihood at `sample` (model.py:873, :886, :901, :929): float32 device tensor, final_shape,
+        zero in the unobserved cells.  Host float64 draws on the mean counts of the HIP forward model; not on the hot path."""
+        fwd, rng = self.fwd, np.random.default_rng(seed)
+        base = self.base_params(sample)
+        cm, selec = self.mean_counts(sample)
+        cm = cm.double().cpu().numpy()
+        sel_mean = selec if not torch.is_tensor(selec) else None
+        selec = selec.double().cpu().numpy() if torch.is_tensor(selec) else np.full(self.final_shape, selec)
+        mask = np.ones(self.final_shape, bool) if self.mask is None else self.mask.cpu().numpy()
+        cm, selec = np.where(mask, cm, 0.), np.where(mask, selec, 1.)
+        eps = rng.standard_normal(self.final_shape)
+        if self.lik_type == "poisson":
+            obs = rng.poisson(np.abs(cm)).astype(np.float64)
+        elif self.lik_type == "fourier_gauss":
+            kvec = nbody.rfftk(self.final_shape, fwd.box_size)
+            k2 = sum(ki ** 2 for ki in kvec)
+            kl2 = sum(ki * li for ki, li in zip(kvec, self.los_fid)) ** 2      # (k mu)^2 = (k . los)^2, 0 at k = 0
+            amp = np.abs(base["s_e"] + base["s_k2e"] * k2 + base["s_kmu2e"] * kl2) * sel_mean ** .5
+            amp = np.broadcast_to(amp, r2chshape(self.final_shape))
+            sigma = cgh2rg(torch.from_numpy(amp.astype(np.complex64)), norm="amp")
+            obs_rg = cgh2rg(nbody.rfftn(cm.astype(np.float32))) + sigma * torch.from_numpy(eps.astype(np.float32)).to(sigma.device)
+            return nbody.irfftn(rg2cgh(obs_rg))
+        else:
+            b = (np.abs(base["s_e"] + base["s_ed"] * (cm / selec - 1.0)) + 1e-9) * selec ** .5
+            a = float(base["s_e2"]) * selec ** .5
+            if self.lik_type == "quad_gauss":      # utils.py:492-494
+                obs = cm + b * eps + a * (eps ** 2 - 1.0)
+            else:      # 'shash', utils.py:431-435
+                from numpy.polynomial.hermite_e import hermegauss
+                x, wq = hermegauss(20)
+                wq = (wq / np.sqrt(2 * np.pi)).reshape(-1, 1, 1, 1)
+                skew, tail = 3.540 * a / b, 1.0 + 5.884 * (a / b) ** 2
+                Zq = np.sinh((np.arcsinh(x).reshape(-1, 1, 1, 1) + skew) * tail)
+                m = (wq * Zq).sum(0)
+                sd = np.sqrt((wq * Zq ** 2).sum(0) - m ** 2)
+                obs = cm + np.sqrt(b ** 2 + 2 * a ** 2) * (np.sinh((np.arcsinh(eps) + skew) * tail) - m) / sd
+        return nbody._f32(np.where(mask, obs, 0.), self.final_shape)
 
     def names(self):
         """Sample-space parameter names: scalars (in a fixed order) then 'white_mesh_'."""
@@ -405,46 +521,63 @@ class FieldLevelLogDensity:
         resh = tuple(gxy.shape) != self.final_shape
         dn = self._down(gsel)
         cm = dn * rc
-        # Only the observed cells carry a likelihood term: the reference extracts them first (mesh2masked, model.py:856-863).
-        # Here every cell is evaluated, so the unobserved ones are given safe inputs (selection 1, count 0 -- a cut-sky
-        # selection is exactly 0 there and count / selec would be NaN) and are removed with `where`, never by multiplying.
-        obs, cmu = self.count_obs, cm
-        if self.mask is not None:
-            if torch.is_tensor(selec):
-                selec = torch.where(self.mask, selec, torch.ones_like(selec))
-            cmu = torch.where(self.mask, cm, torch.zeros_like(cm))
-            obs = torch.where(self.mask, obs, torch.zeros_like(obs))
-        delta = cmu / selec - 1.0
-        lin = base["s_e"] + base["s_ed"] * delta
-        b = (lin.abs() + 1e-9) * selec ** .5
-        a = 0.0 if abs(float(base["s_e2"])) < 1e-10 else float(base["s_e2"]) * selec ** .5
-        lpe, g_loc, g_b, g_a = quad_gaussian_log_prob_and_grad(obs, cmu, b, a)
-        if self.mask is not None:
-            zero = torch.zeros_like(lpe)
-            lpe, g_loc, g_b = torch.where(self.mask, lpe, zero), torch.where(self.mask, g_loc, zero), torch.where(self.mask, g_b, zero)
-            g_a = torch.where(self.mask, g_a, zero) if torch.is_tensor(g_a) else g_a
-        lp += float(lpe.double().sum())
-        if not need_grad:
-            return lp, None
-        sgn = torch.sign(lin) * selec ** .5
-        cm_bar = g_loc + g_b * sgn * (base["s_ed"] / selec)
-        stoch_bar = {"s_e": float((g_b * sgn).double().sum()), "s_ed": float((g_b * sgn * delta).double().sum()),
-                     "s_e2": float((g_a * selec ** .5).double().sum())}
-        gxy_bar = cm_bar * rc
-        ngb_bar = None
-        if self.ngb_lat is not None:      # d/d rcounts: through count = dn rc and through selec (|S rc| per cell, or mean(rcounts))
-            wsel = g_b * (lin.abs() + 1e-9) + (g_a * float(base["s_e2"]) if torch.is_tensor(g_a) else 0.0)   # d lp / d sqrt(selec)
-            if self.sel_down is not None:
-                # delta = count / selec does not move with rc; selec = |S| |rc|
-                rc_bar = g_loc * dn + wsel * 0.5 * selec ** -.5 * self.sel_down.abs() * torch.sign(rc)
-                per = torch.bincount(self.shell.reshape(-1), weights=rc_bar.double().reshape(-1), minlength=self.n_rbins + 1)[:self.n_rbins]
-                rcounts_bar = per.cpu().numpy()
-            else:
-                rc_bar = cm_bar * dn
-                per = torch.bincount(self.shell.reshape(-1), weights=rc_bar.double().reshape(-1), minlength=self.n_rbins + 1)[:self.n_rbins]
-                common = float((-(g_b * sgn * base["s_ed"]) * cmu / selec ** 2 + wsel * 0.5 * selec ** -.5).double().sum())
-                rcounts_bar = per.cpu().numpy() + common / self.n_rbins
-            ngb_bar = rcounts_bar * fwd.cell_length ** 3
+        if self.lik_type != "quad_gauss":      # csrc/likelihood.hip: value, mesh cotangents and float64 sums from one kernel
+            lpl, cm_bar, stoch_bar, qb, qsum, selec = self._lik_hip(base, cm, selec, self.ngb_lat is not None)
+            lp += lpl
+            if not need_grad:
+                return lp, None
+            gxy_bar = cm_bar * rc
+            ngb_bar = None
+            if self.ngb_lat is not None:      # d/d rcounts: count = dn rc at fixed selec, and selec (|S rc| per cell, or mean(rcounts)) at fixed count
+                per = torch.bincount(self.shell.reshape(-1), weights=(cm_bar * dn).double().reshape(-1), minlength=self.n_rbins + 1)[:self.n_rbins]
+                if self.sel_down is not None:
+                    sq_bar = qb * 0.5 * selec ** -.5 * self.sel_down.abs() * torch.sign(rc)
+                    per = per + torch.bincount(self.shell.reshape(-1), weights=sq_bar.double().reshape(-1), minlength=self.n_rbins + 1)[:self.n_rbins]
+                    rcounts_bar = per.cpu().numpy()
+                else:
+                    rcounts_bar = per.cpu().numpy() + qsum * 0.5 * selec ** -.5 / self.n_rbins
+                ngb_bar = rcounts_bar * fwd.cell_length ** 3
+        else:
+            # Only the observed cells carry a likelihood term: the reference extracts them first (mesh2masked, model.py:856-863).
+            # Here every cell is evaluated, so the unobserved ones are given safe inputs (selection 1, count 0 -- a cut-sky
+            # selection is exactly 0 there and count / selec would be NaN) and are removed with `where`, never by multiplying.
+            obs, cmu = self.count_obs, cm
+            if self.mask is not None:
+                if torch.is_tensor(selec):
+                    selec = torch.where(self.mask, selec, torch.ones_like(selec))
+                cmu = torch.where(self.mask, cm, torch.zeros_like(cm))
+                obs = torch.where(self.mask, obs, torch.zeros_like(obs))
+            delta = cmu / selec - 1.0
+            lin = base["s_e"] + base["s_ed"] * delta
+            b = (lin.abs() + 1e-9) * selec ** .5
+            a = 0.0 if abs(float(base["s_e2"])) < 1e-10 else float(base["s_e2"]) * selec ** .5
+            lpe, g_loc, g_b, g_a = quad_gaussian_log_prob_and_grad(obs, cmu, b, a)
+            if self.mask is not None:
+                zero = torch.zeros_like(lpe)
+                lpe, g_loc, g_b = torch.where(self.mask, lpe, zero), torch.where(self.mask, g_loc, zero), torch.where(self.mask, g_b, zero)
+                g_a = torch.where(self.mask, g_a, zero) if torch.is_tensor(g_a) else g_a
+            lp += float(lpe.double().sum())
+            if not need_grad:
+                return lp, None
+            sgn = torch.sign(lin) * selec ** .5
+            cm_bar = g_loc + g_b * sgn * (base["s_ed"] / selec)
+            stoch_bar = {"s_e": float((g_b * sgn).double().sum()), "s_ed": float((g_b * sgn * delta).double().sum()),
+                         "s_e2": float((g_a * selec ** .5).double().sum())}
+            gxy_bar = cm_bar * rc
+            ngb_bar = None
+            if self.ngb_lat is not None:      # d/d rcounts: through count = dn rc and through selec (|S rc| per cell, or mean(rcounts))
+                wsel = g_b * (lin.abs() + 1e-9) + (g_a * float(base["s_e2"]) if torch.is_tensor(g_a) else 0.0)   # d lp / d sqrt(selec)
+                if self.sel_down is not None:
+                    # delta = count / selec does not move with rc; selec = |S| |rc|
+                    rc_bar = g_loc * dn + wsel * 0.5 * selec ** -.5 * self.sel_down.abs() * torch.sign(rc)
+                    per = torch.bincount(self.shell.reshape(-1), weights=rc_bar.double().reshape(-1), minlength=self.n_rbins + 1)[:self.n_rbins]
+                    rcounts_bar = per.cpu().numpy()
+                else:
+                    rc_bar = cm_bar * dn
+                    per = torch.bincount(self.shell.reshape(-1), weights=rc_bar.double().reshape(-1), minlength=self.n_rbins + 1)[:self.n_rbins]
+                    common = float((-(g_b * sgn * base["s_ed"]) * cmu / selec ** 2 + wsel * 0.5 * selec ** -.5).double().sum())
+                    rcounts_bar = per.cpu().numpy() + common / self.n_rbins
+                ngb_bar = rcounts_bar * fwd.cell_length ** 3
         if resh:      # adjoints of irfftn, chreshape, rfftn (real-pair convention)
             Mf = float(np.prod(self.final_shape))
             kb = nbody.rfftn(gxy_bar) / Mf
@@ -473,6 +606,7 @@ class FieldLevelLogDensity:
         base_bar.update({k: 0.0 for k in bricks.AP_KEYS})      # (read only with ap_auto = False)
         base_bar.update(g.get("ap", {}))
         base_bar.update(g["bias"])
+        base_bar.update({k: 0.0 for k in self.ALL_STOCH})      # (a stochastic parameter the likelihood does not read)
         base_bar.update(stoch_bar)
         base_bar["sigma8"] = g["sigma8"]
         if "Omega_m" in self.latents:

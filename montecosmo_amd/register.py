@@ -114,8 +114,10 @@ def model_arguments(reg, **overrides):
        loc       -> fiducial values of the latents: Omega_m, sigma8 from cosmo_fid, and ngbars = n_tracers / (observed cells
                     x cell_length^3) (model.py:546-549)
        white_mesh-> the registered initial conditions (or None).
-    `overrides` replace forward arguments (evolution, nbody_n_steps, ...)."""
+    `overrides` replace forward arguments (evolution, nbody_n_steps, ...); `lik_type` among them (or in the register) goes to the
+    density arguments instead: FieldLevelLogDensity(..., lik_type=density['lik_type'])."""
     validate(reg)
+    lik_type = overrides.pop("lik_type", reg.get("lik_type"))
     count = np.asarray(reg["count_mesh"], dtype=np.float64)
     mask = None if reg.get("mask_mesh") is None else np.asarray(reg["mask_mesh"], dtype=bool)
     fwd = dict(final_shape=tuple(int(s) for s in count.shape), cell_length=float(reg["cell_length"]),
@@ -149,6 +151,9 @@ def model_arguments(reg, **overrides):
     sel = reg.get("selec_mesh")
     sel = None if (sel is None or np.ndim(sel) == 0) else np.asarray(sel, dtype=np.float64)
     white = reg.get("white_mesh", reg.get("white_fake"))
-    return dict(forward=fwd, density=dict(count_mesh=count, selec_mesh=sel, mask_mesh=mask),
+    density = dict(count_mesh=count, selec_mesh=sel, mask_mesh=mask)
+    if lik_type not in (None, "None"):
+        density["lik_type"] = str(lik_type)
+    return dict(forward=fwd, density=density,
                 loc=dict(Omega_m=float(reg["cosmo_fid"]["Omega_m"]), sigma8=float(reg["cosmo_fid"]["sigma8"]), ngbars=ngbar),
                 white_mesh=None if white is None else np.asarray(white))
