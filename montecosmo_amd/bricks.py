@@ -559,13 +559,4 @@ def samp2base_mesh_vjp(base_bar, precond, transfer, temp=1.):
     from . import nbody, utils
     tr = torch.as_tensor(np.asarray(transfer, dtype=np.float32) * temp ** .5, device=nbody._device())
     kb = nbody._c64(base_bar) * tr
-    if precond == 'real':        # adjoint of rfftn under the real-pair convention: unnormalised C2R of the cotangent
-        kb = kb.clone()
-        shape = utils.ch2rshape(kb.shape)
-        plan = nbody.get_plan(shape)
-        # irfftn's multiplicity weights must not be applied: halve the doubly counted modes first
-        kb[..., 1:shape[-1] // 2] *= 0.5
-        out = torch.empty(shape, dtype=torch.float32, device=kb.device)
-        plan.call("mcpm_fft_c2r", nbody._ptr(kb), nbody._ptr(out), 1)
-        return out
-    return utils.rg2cgh_vjp(kb)
+    return nbody.rfftn_vjp(kb) if precond == 'real' else utils.rg2cgh_vjp(kb)

@@ -26,10 +26,19 @@ Not built: 'two_quad_gauss' (a 64-node quadrature), the s_ep * phi term of scale
 
 The gradient is hand-derived end to end: elementwise likelihood / prior terms here (device tensors), the mesh and
 particle operators through their `*_vjp` twins -- no autodiff framework.
+
+`logdensity_and_grad` runs three stages and one reverse tail:
+    1. `_prior`: every latent -- scalars and the per-shell ngbars alike, and `base_params` -- through `latent_log_prob_and_grad`, which picks
+       uniform / truncated normal / normal from the latent's config; a saturated tail ends the call here with -inf and a zero gradient.
+    2. `_forward`: white field -> transfer -> `evolve` -> mean counts `cm` and selection on the final mesh; `mean_counts` is this stage alone.
+    3. one likelihood method (`_lik_quad_gauss`, `_lik_hip`): (base, forward result, need_grad) -> (lp, cm_bar, stoch_bar, rcounts_bar or None).
+       A new likelihood is one more such method.  Each keeps its own closed form of the shell gradient; `_per_shell` is the shared plumbing.
+    tail: gxy_bar = cm_bar rc -> `_down_vjp` -> selection -> `evolve_vjp` -> white-field adjoint -> `_base_bar` chained to the latents.
 """
 from __future__ import annotations
 
 import math
+from types import SimpleNamespace
 
 import numpy as np
 import torch
@@ -144,6 +153,18 @@ def detrunc_unif_log_prob_and_grad(x, c):
     return -math.log(c["high"] - c["low"]) + math.log(abs(d1)), d2 / d1, y, d1
 
 
+def latent_log_prob_and_grad(x, c):
+    """Prior of ONE latent at the sample value `x`, by its config `c`: (lp, d lp / dx, base, d base / dx).  No `loc` / `scale`: uniform on
+    [low, high] (model.py:1122-1123); a finite `low` or `high`: truncated normal (model.py:1120-1121, bricks.py:271-273); else
+    x ~ Normal((loc - loc_fid) / scale_fid, scale / scale_fid) with base = x scale_fid + loc_fid (model.py:1117-1119, bricks.py:270-276)."""
+    if "loc" not in c:
+        return detrunc_unif_log_prob_and_grad(x, c)
+    if c["low"] != -math.inf or c["high"] != math.inf:
+        return detrunc_truncnorm_log_prob_and_grad(x, c)
+    mu, sd = (c["loc"] - c["loc_fid"]) / c["scale_fid"], c["scale"] / c["scale_fid"]
+    return -0.5 * LOG2PI - math.log(sd) - 0.5 * ((x - mu) / sd) ** 2, -(x - mu) / sd ** 2, x * c["scale_fid"] + c["loc_fid"], c["scale_fid"]
+
+
 class FieldLevelLogDensity:
     """log p(sample params, observed counts) and its gradient.
 
@@ -205,14 +226,8 @@ class FieldLevelLogDensity:
         self._setup_selection(selec_mesh, mask_mesh, redges)
         self.scale, self.transfer = self._precond_scale_and_transfer()
         if lik_type == "fourier_gauss":      # the observation in the real layout, once (model.py:885 applied to the data)
-            self.los_fid = self._los_fid()
+            self.los_fid = fwd.los_cell()
             self.obs_rg = cgh2rg(nbody.rfftn(self.count_obs))
-
-    def _los_fid(self):
-        """Line of sight in cell coordinates (model.py:607-608), as the 'kaiser' preconditioning takes it."""
-        fwd = self.fwd
-        los = nbody.safe_div(fwd.box_center, np.linalg.norm(fwd.box_center))
-        return bricks.rot_matrix(fwd.box_rotvec).T @ los
 
     @staticmethod
     def _planck(base):
@@ -221,21 +236,17 @@ class FieldLevelLogDensity:
         c.sigma8 = float(base["sigma8"])
         return c
 
-    def _radius_mesh(self):
-        """Physical distance of the final-mesh cells (bricks.py:665-686); host float64, set-up only."""
-        fwd = self.fwd
-        p = bricks.cell2phys_pos(bricks.regular_pos(self.final_shape), fwd.box_center, fwd.box_rotvec, fwd.box_size, self.final_shape)
-        if fwd.curved_sky:
-            r = np.linalg.norm(p, axis=-1)
-        else:
-            r = np.abs(p @ nbody.safe_div(fwd.box_center, np.linalg.norm(fwd.box_center)))
-        return r.reshape(self.final_shape)
-
     def _down(self, mesh):
         """irfftn(chreshape(rfftn(mesh), final_shape)) (model.py:855, :861); identity when the shapes agree."""
         if tuple(mesh.shape) == self.final_shape:
             return mesh
         return nbody.irfftn(chreshape(nbody.rfftn(mesh), r2chshape(self.final_shape)))
+
+    def _down_vjp(self, mesh_bar, shape):
+        """Adjoint of `_down` for a mesh of `shape`: the adjoints of irfftn, chreshape and rfftn (real-pair convention)."""
+        if tuple(shape) == self.final_shape:
+            return mesh_bar
+        return nbody.rfftn_vjp(chreshape_vjp(nbody.irfftn_vjp(mesh_bar), r2chshape(tuple(shape))), overwrite=True)
 
     def _setup_selection(self, selec_mesh, mask_mesh, redges):
         """Radial shells as a per-cell index (set_radial_count, bricks.py:1106-1122: cell -> its shell's count), the
@@ -243,7 +254,7 @@ class FieldLevelLogDensity:
         prior configuration (model.py:1099-1103)."""
         fwd, dev = self.fwd, self.count_obs.device
         mask = None if mask_mesh is None else np.asarray(mask_mesh, dtype=bool).reshape(self.final_shape)
-        rmesh = self._radius_mesh()
+        rmesh = fwd.lattice_radius(self.final_shape).reshape(self.final_shape)      # distance of the final-mesh cells; set-up only
         if self._ngb_conf is None:
             nb = len(np.atleast_1d(self.fixed["ngbars"]))
         elif redges is not None:
@@ -295,16 +306,7 @@ class FieldLevelLogDensity:
     def _fiducial_scale_factor(self, cosmo_fid):
         """a_fid = g2a(mean a2g(a)) over the final-mesh cells (model.py:604-606)."""
         fwd = self.fwd
-        if fwd.a_obs is not None:
-            a = fwd.a_obs
-        else:
-            p = bricks.cell2phys_pos(bricks.regular_pos(self.final_shape), fwd.box_center, fwd.box_rotvec, fwd.box_size,
-                                     self.final_shape)
-            if fwd.curved_sky:
-                r = np.linalg.norm(p, axis=-1)
-            else:
-                r = np.abs(p @ nbody.safe_div(fwd.box_center, np.linalg.norm(fwd.box_center)))
-            a = nbody.chi2a(cosmo_fid, r)
+        a = fwd.a_obs if fwd.a_obs is not None else nbody.chi2a(cosmo_fid, fwd.lattice_radius(self.final_shape))
         return float(nbody.g2a(cosmo_fid, np.mean(nbody.a2g(cosmo_fid, a))))
 
     def _precond_scale_and_transfer(self):
@@ -319,11 +321,9 @@ class FieldLevelLogDensity:
         fid = self.fiducial()
         cosmo_fid = self.make_cosmo(fid)
         a_fid = self._fiducial_scale_factor(cosmo_fid)
-        los = nbody.safe_div(fwd.box_center, np.linalg.norm(fwd.box_center))
-        los_fid = bricks.rot_matrix(fwd.box_rotvec).T @ los                              # model.py:607-608, cell los
         kvec = nbody.rfftk(fwd.init_shape, fwd.box_size)
         kmesh = sum(ki ** 2 for ki in kvec) ** .5
-        mu = nbody.safe_div(sum(ki * li for ki, li in zip(kvec, los_fid)), kmesh)
+        mu = nbody.safe_div(sum(ki * li for ki, li in zip(kvec, fwd.los_cell())), kmesh)
         boost = float(nbody.a2g(cosmo_fid, a_fid)) * ((1.0 + float(fid["b1"])) + float(nbody.a2f(cosmo_fid, a_fid)) * mu ** 2)
         ks, pows = fwd.kpow(cosmo_fid)
         pmesh = np.interp(kmesh.reshape(-1), ks, pows * float(fid["sigma8"]) ** 2, left=0., right=0.).reshape(kmesh.shape)
@@ -336,53 +336,144 @@ class FieldLevelLogDensity:
         scale = cgh2rg(torch.from_numpy(scale_k.astype(np.complex64)).to(dev), norm="amp")
         return scale, transfer
 
-    def _lik_hip(self, base, cm, selec, want_sqsel):
-        """The likelihood term of 'shash', 'poisson' or 'fourier_gauss' on the mean counts `cm` (final mesh) and the selection (a mesh or a
-        float).  Returns (lp, count_bar = d lp / d cm at fixed selec, the cotangents of the stochastic parameters, sqsel_bar = d lp / d sqrt(selec)
-        per cell at fixed count (real-space families with `want_sqsel`, else None), its sum, the selection made safe outside the mask)."""
+    # ---- stage 1: priors of the latents --------------------------------------------------------------------------------------------
+    def _prior(self, sample):
+        """(lp, base, grad, dbase) of the scalar latents and the per-shell ngbars (same priors, model.py:1105-1125): the summed prior, the
+        base parameters (fixed ones included), grad[name_] = d lp / d name_ and dbase[name] = d base / d name_ (arrays for ngbars)."""
+        lp, base, grad, dbase = 0.0, dict(self.fixed), {}, {}
+        for name, c in self.latents.items():
+            l, grad[name + "_"], base[name], dbase[name] = latent_log_prob_and_grad(float(sample[name + "_"]), c)
+            lp += l
+        if self.ngb_lat is not None:
+            xs = np.atleast_1d(np.asarray(sample["ngbars_"], dtype=np.float64))
+            terms = np.array([latent_log_prob_and_grad(float(xs[i]), self._ngb_elem(i)) for i in range(self.n_rbins)])
+            for l in terms[:, 0]:
+                lp += float(l)
+            grad["ngbars_"], base["ngbars"], dbase["ngbars"] = terms[:, 1].copy(), terms[:, 2].copy(), terms[:, 3].copy()
+        return lp, base, grad, dbase
+
+    def base_params(self, sample):
+        return self._prior(sample)[1]
+
+    def _white_prior(self, w):
+        """white_mesh_ ~ Normal(0, scale) per cell (model.py:666-672; scale None = 1)."""
+        if self.scale is None:
+            return float(-0.5 * LOG2PI * w.numel() - 0.5 * (w.double() ** 2).sum())
+        return float(-0.5 * LOG2PI * w.numel() - self.scale.double().log().sum() - 0.5 * ((w / self.scale).double() ** 2).sum())
+
+    # ---- stage 2: forward model up to the mean counts --------------------------------------------------------------------------------
+    def _forward(self, base, white_mesh_, need_ctx=False):
+        """What every likelihood is evaluated on (model.py:850-866): gxy (the galaxy mesh of `evolve`; ctx: its context when `need_ctx`),
+        rc (per-cell count multiplier from the shells' mean densities), dn (gxy times the selection mesh, brought to the final mesh),
+        cm = dn rc (the mean counts) and selec (a mesh with a selection mesh, else the float mean(rcounts))."""
+        fwd = self.fwd
+        w = nbody._f32(white_mesh_, fwd.init_shape)
+        white = (nbody.rfftn(w) if self.precond == "real" else rg2cgh(w)) * self.transfer
+        kw = {"png": {k: float(base.get(k, 0.0)) for k in bricks.PNG_KEYS}} if fwd.png_type is not None else {}
+        if fwd.ap_auto is False:
+            kw["ap"] = {k: float(base.get(k, 1.0)) for k in bricks.AP_KEYS}
+        if need_ctx:
+            # Omega_m sampled: the forward model makes the two evaluations of the growth-table Jacobian as soon as it has queued its kernels
+            fwd.cosmo_fd_params = ("Omega_m",) if "Omega_m" in self.latents else None
+        out = fwd.evolve(self.make_cosmo(base), {k: base[k] for k in bricks.BIAS_KEYS}, white, return_ctx=need_ctx, **kw)
+        gxy, ctx = out if need_ctx else (out, None)
+        rcounts = np.atleast_1d(np.asarray(base["ngbars"], dtype=np.float64)) * fwd.cell_length ** 3
+        rc = torch.from_numpy(np.append(rcounts, 1.0).astype(np.float32)).to(gxy.device)[self.shell]
+        selec = float(rcounts.mean()) if self.sel_down is None else (self.sel_down * rc).abs()
+        dn = self._down(gxy if self.selec_mesh is None else gxy * self.selec_mesh)
+        return SimpleNamespace(gxy=gxy, ctx=ctx, rc=rc, dn=dn, cm=dn * rc, selec=selec)
+
+    def mean_counts(self, sample):
+        """(count, selec) of the likelihood at `sample` (model.py:850-866): the mean counts on the final mesh, and the selection there (a mesh
+        with a selection mesh, else the float mean(rcounts))."""
+        f = self._forward(self.base_params(sample), sample["white_mesh_"])
+        return f.cm, f.selec
+
+    # ---- stage 3: likelihoods.  Each: (base, f = _forward's result, need_grad) -> (lp, cm_bar = d lp / d cm at fixed selec, the cotangents
+    # of the stochastic parameters, rcounts_bar = d lp / d rcounts per shell through count AND selec, or None with fixed ngbars); with
+    # need_grad = False only lp is formed and the rest is None ---------------------------------------------------------------------------
+    def _per_shell(self, cell_bar):
+        """A per-cell cotangent summed over each radial shell (float64 device tensor; the cells in no shell are dropped)."""
+        return torch.bincount(self.shell.reshape(-1), weights=cell_bar.double().reshape(-1), minlength=self.n_rbins + 1)[:self.n_rbins]
+
+    def _lik_hip(self, base, f, need_grad):
+        """'shash', 'poisson' or 'fourier_gauss': value, mesh cotangents and float64 sums from one kernel (csrc/likelihood.hip).  The kernel
+        gives count_bar at fixed selec and sqsel_bar = d lp / d sqrt(selec) at fixed count (per cell for the real-space families, its sum in
+        sums[4]); the shells get both."""
         plan = nbody.get_plan(self.final_shape)
+        cm, selec, want_sqsel = f.cm.contiguous(), f.selec, self.ngb_lat is not None
         sums = torch.empty(5, dtype=torch.float64, device=cm.device)
-        cm = cm.contiguous()
+        mesh_sel, qb = torch.is_tensor(selec), None
         if self.lik_type == "fourier_gauss":
             Y = nbody.rfftn(cm)
             Yb = torch.empty_like(Y)
             box, los = [float(v) for v in self.fwd.box_size], [float(v) for v in self.los_fid]
             plan.call("mcpm_lik_fourier_f32", nbody._ptr(Y), nbody._ptr(self.obs_rg), *box, *los, float(selec), float(base["s_e"]),
                       float(base["s_k2e"]), float(base["s_kmu2e"]), nbody._ptr(Yb), nbody._ptr(sums))
-            Yb[..., 1:self.final_shape[-1] // 2] *= 0.5      # adjoint of rfftn, real-pair convention: the C2R counts these modes twice
-            cm_bar = torch.empty(self.final_shape, dtype=torch.float32, device=cm.device)
-            plan.call("mcpm_fft_c2r", nbody._ptr(Yb), nbody._ptr(cm_bar), 1)
-            v = sums.cpu().numpy()
-            return float(v[0]), cm_bar, {"s_e": float(v[1]), "s_k2e": float(v[2]), "s_kmu2e": float(v[3])}, None, float(v[4]), selec
-        mesh_sel = torch.is_tensor(selec)
-        if mesh_sel:
-            selec = (selec if self.mask is None else torch.where(self.mask, selec, torch.ones_like(selec))).contiguous()
-        shash = self.lik_type == "shash"
-        cm_bar = torch.empty_like(cm)
-        qb = torch.empty_like(cm) if (want_sqsel and mesh_sel) else None
-        st = [float(base[k]) if shash else 0.0 for k in self.STOCH]
-        plan.call("mcpm_lik_real_f32", _lib.LIK_SHASH if shash else _lib.LIK_POISSON, C.c_int64(cm.numel()), nbody._ptr(self.count_obs),
-                  nbody._ptr(cm), nbody._ptr(selec if mesh_sel else None), 1.0 if mesh_sel else float(selec), nbody._ptr(self.mask), *st,
-                  nbody._ptr(cm_bar), nbody._ptr(qb), nbody._ptr(sums))
+            keys = ("s_e", "s_k2e", "s_kmu2e")
+        else:
+            if mesh_sel:      # the selection made safe outside the mask
+                selec = (selec if self.mask is None else torch.where(self.mask, selec, torch.ones_like(selec))).contiguous()
+            shash = self.lik_type == "shash"
+            cm_bar = torch.empty_like(cm)
+            qb = torch.empty_like(cm) if (want_sqsel and mesh_sel) else None
+            st = [float(base[k]) if shash else 0.0 for k in self.STOCH]
+            plan.call("mcpm_lik_real_f32", _lib.LIK_SHASH if shash else _lib.LIK_POISSON, C.c_int64(cm.numel()), nbody._ptr(self.count_obs),
+                      nbody._ptr(cm), nbody._ptr(selec if mesh_sel else None), 1.0 if mesh_sel else float(selec), nbody._ptr(self.mask), *st,
+                      nbody._ptr(cm_bar), nbody._ptr(qb), nbody._ptr(sums))
+            keys = self.STOCH if shash else ()
         v = sums.cpu().numpy()
-        stoch_bar = {"s_e": float(v[1]), "s_ed": float(v[2]), "s_e2": float(v[3])} if shash else {}
-        return float(v[0]), cm_bar, stoch_bar, qb, float(v[4]), selec
+        if not need_grad:
+            return float(v[0]), None, None, None
+        if self.lik_type == "fourier_gauss":
+            cm_bar = nbody.rfftn_vjp(Yb, overwrite=True)
+        stoch_bar = {k: float(v[1 + i]) for i, k in enumerate(keys)}
+        if not want_sqsel:
+            return float(v[0]), cm_bar, stoch_bar, None
+        per = self._per_shell(cm_bar * f.dn)      # count = dn rc at fixed selec
+        if mesh_sel:      # selec = |S rc| per cell
+            per = per + self._per_shell(qb * 0.5 * selec ** -.5 * self.sel_down.abs() * torch.sign(f.rc))
+            return float(v[0]), cm_bar, stoch_bar, per.cpu().numpy()
+        return float(v[0]), cm_bar, stoch_bar, per.cpu().numpy() + float(v[4]) * 0.5 * selec ** -.5 / self.n_rbins      # selec = mean(rcounts)
 
-    def mean_counts(self, sample):
-        """(count, selec) of the likelihood at `sample` (model.py:850-866): the mean counts on the final mesh, and the selection there (a mesh
-        with a selection mesh, else the float mean(rcounts))."""
-        fwd = self.fwd
-        base = self.base_params(sample)
-        w = nbody._f32(sample["white_mesh_"], fwd.init_shape)
-        white = (nbody.rfftn(w) if self.precond == "real" else rg2cgh(w)) * self.transfer
-        kw = {"png": {k: float(base.get(k, 0.0)) for k in bricks.PNG_KEYS}} if fwd.png_type is not None else {}
-        if getattr(fwd, "ap_auto", None) is False:
-            kw["ap"] = {k: float(base.get(k, 1.0)) for k in bricks.AP_KEYS}
-        gxy = fwd.evolve(self.make_cosmo(base), {k: base[k] for k in bricks.BIAS_KEYS}, white, **kw)
-        rcounts = np.atleast_1d(np.asarray(base["ngbars"], dtype=np.float64)) * fwd.cell_length ** 3
-        rc = torch.from_numpy(np.append(rcounts, 1.0).astype(np.float32)).to(gxy.device)[self.shell]
-        cm = self._down(gxy if self.selec_mesh is None else gxy * self.selec_mesh) * rc
-        return cm, (float(rcounts.mean()) if self.sel_down is None else (self.sel_down * rc).abs())
+    def _lik_quad_gauss(self, base, f, need_grad):
+        """'quad_gauss' on its torch path (model.py:852-866, :893-908).
+        Only the observed cells carry a likelihood term: the reference extracts them first (mesh2masked, model.py:856-863).
+        Here every cell is evaluated, so the unobserved ones are given safe inputs (selection 1, count 0 -- a cut-sky
+        selection is exactly 0 there and count / selec would be NaN) and are removed with `where`, never by multiplying."""
+        obs, cmu, selec = self.count_obs, f.cm, f.selec
+        if self.mask is not None:
+            if torch.is_tensor(selec):
+                selec = torch.where(self.mask, selec, torch.ones_like(selec))
+            cmu = torch.where(self.mask, f.cm, torch.zeros_like(f.cm))
+            obs = torch.where(self.mask, obs, torch.zeros_like(obs))
+        delta = cmu / selec - 1.0
+        lin = base["s_e"] + base["s_ed"] * delta
+        b = (lin.abs() + 1e-9) * selec ** .5
+        a = 0.0 if abs(float(base["s_e2"])) < 1e-10 else float(base["s_e2"]) * selec ** .5
+        lpe, g_loc, g_b, g_a = quad_gaussian_log_prob_and_grad(obs, cmu, b, a)
+        if self.mask is not None:
+            zero = torch.zeros_like(lpe)
+            lpe, g_loc, g_b = torch.where(self.mask, lpe, zero), torch.where(self.mask, g_loc, zero), torch.where(self.mask, g_b, zero)
+            g_a = torch.where(self.mask, g_a, zero) if torch.is_tensor(g_a) else g_a
+        lp = float(lpe.double().sum())
+        if not need_grad:
+            return lp, None, None, None
+        sgn = torch.sign(lin) * selec ** .5
+        cm_bar = g_loc + g_b * sgn * (base["s_ed"] / selec)
+        stoch_bar = {"s_e": float((g_b * sgn).double().sum()), "s_ed": float((g_b * sgn * delta).double().sum()),
+                     "s_e2": float((g_a * selec ** .5).double().sum())}
+        if self.ngb_lat is None:
+            return lp, cm_bar, stoch_bar, None
+        # d/d rcounts: through count = dn rc and through selec (|S rc| per cell, or mean(rcounts)), each in its closed form
+        wsel = g_b * (lin.abs() + 1e-9) + (g_a * float(base["s_e2"]) if torch.is_tensor(g_a) else 0.0)   # d lp / d sqrt(selec)
+        if self.sel_down is not None:
+            # delta = count / selec does not move with rc; selec = |S| |rc|
+            rc_bar = g_loc * f.dn + wsel * 0.5 * selec ** -.5 * self.sel_down.abs() * torch.sign(f.rc)
+            return lp, cm_bar, stoch_bar, self._per_shell(rc_bar).cpu().numpy()
+        per = self._per_shell(cm_bar * f.dn)
+        common = float((-(g_b * sgn * base["s_ed"]) * cmu / selec ** 2 + wsel * 0.5 * selec ** -.5).double().sum())
+        return lp, cm_bar, stoch_bar, per.cpu().numpy() + common / self.n_rbins
 
     def draw_counts(self, sample, seed=0):
         """One observed count mesh drawn from the likelihood at `sample` (model.py:873, :886, :901, :929): float32 device tensor, final_shape,
@@ -427,180 +518,21 @@ class FieldLevelLogDensity:
         """Sample-space parameter names: scalars (in a fixed order) then 'white_mesh_'."""
         return [k + "_" for k in self.latents] + (["ngbars_"] if self.ngb_lat is not None else []) + ["white_mesh_"]
 
-    @staticmethod
-    def _bounded(c):
-        return c["low"] != -math.inf or c["high"] != math.inf
-
-    def base_params(self, sample):
-        base = dict(self.fixed)
-        for name, c in self.latents.items():
-            x = float(sample[name + "_"])
-            base[name] = std2trunc_and_derivs(x, c["loc_fid"], c["scale_fid"], c["low"], c["high"])[0] if self._bounded(c) \
-                else x * c["scale_fid"] + c["loc_fid"]
-        if self.ngb_lat is not None:
-            xs = np.atleast_1d(np.asarray(sample["ngbars_"], dtype=np.float64))
-            out = np.empty(self.n_rbins)
-            for i in range(self.n_rbins):
-                c = self._ngb_elem(i)
-                out[i] = std2trunc_and_derivs(float(xs[i]), c["loc_fid"], c["scale_fid"], c["low"], c["high"])[0] if self._bounded(c) \
-                    else float(xs[i]) * c["scale_fid"] + c["loc_fid"]
-            base["ngbars"] = out
-        return base
-
     def __call__(self, sample):
         return self.logdensity_and_grad(sample)[0]
 
-    def logdensity_and_grad(self, sample, need_grad=True):
-        """sample: dict with the scalars `name_` (floats) and 'white_mesh_' (real tensor, fwd.init_shape).
-        Returns (log density, dict of gradients with the same keys)."""
-        fwd = self.fwd
-        base = self.base_params(sample)
-        lp, grad, dbase = 0.0, {}, {}
-        for name, c in self.latents.items():
-            x = float(sample[name + "_"])
-            if "loc" not in c:        # uniform latent (model.py:1122-1123)
-                l, gl, _, d1 = detrunc_unif_log_prob_and_grad(x, c)
-                lp += l
-                grad[name + "_"], dbase[name] = gl, d1
-            elif self._bounded(c):    # truncated-normal latent (model.py:1120-1121, bricks.py:271-273)
-                l, gl, _, d1 = detrunc_truncnorm_log_prob_and_grad(x, c)
-                lp += l
-                grad[name + "_"], dbase[name] = gl, d1
-            else:
-                mu, sd = (c["loc"] - c["loc_fid"]) / c["scale_fid"], c["scale"] / c["scale_fid"]
-                lp += -0.5 * LOG2PI - math.log(sd) - 0.5 * ((x - mu) / sd) ** 2
-                grad[name + "_"], dbase[name] = -(x - mu) / sd ** 2, c["scale_fid"]
-        ngb_prior_grad = ngb_dbase = None
-        if self.ngb_lat is not None:      # one latent per radial shell, same priors as the scalars (model.py:1105-1125)
-            xs = np.atleast_1d(np.asarray(sample["ngbars_"], dtype=np.float64))
-            ngb_prior_grad, ngb_dbase = np.empty(self.n_rbins), np.empty(self.n_rbins)
-            for i in range(self.n_rbins):
-                c, x = self._ngb_elem(i), float(xs[i])
-                if "loc" not in c:
-                    l, gl, _, d1 = detrunc_unif_log_prob_and_grad(x, c)
-                elif self._bounded(c):
-                    l, gl, _, d1 = detrunc_truncnorm_log_prob_and_grad(x, c)
-                else:
-                    mu, sd = (c["loc"] - c["loc_fid"]) / c["scale_fid"], c["scale"] / c["scale_fid"]
-                    l, gl, d1 = -0.5 * LOG2PI - math.log(sd) - 0.5 * ((x - mu) / sd) ** 2, -(x - mu) / sd ** 2, c["scale_fid"]
-                lp += l
-                ngb_prior_grad[i], ngb_dbase[i] = gl, d1
-        if lp == -math.inf:      # a latent sits in a saturated tail: zero density whatever the field (no forward model needed)
-            # the gradient keeps its full structure (zeros), so that callers which index it before looking at the value --
-            # jax_bridge.logdensity_fn builds a tuple over all names -- get a rejected proposal, not a KeyError
-            if not need_grad:
-                return -math.inf, None
-            zgrad = {name + "_": 0.0 for name in self.latents}
-            if self.ngb_lat is not None:
-                zgrad["ngbars_"] = np.zeros(self.n_rbins)
-            w0 = sample["white_mesh_"]
-            zgrad["white_mesh_"] = (torch.zeros_like(w0) if torch.is_tensor(w0)
-                                    else torch.zeros(fwd.init_shape, dtype=torch.float32, device=nbody._device()))
-            return -math.inf, zgrad
-        w = nbody._f32(sample["white_mesh_"], fwd.init_shape)
-        if self.scale is None:
-            lp += float(-0.5 * LOG2PI * w.numel() - 0.5 * (w.double() ** 2).sum())
-        else:      # white_mesh_ ~ Normal(0, scale) (model.py:666-672)
-            lp += float(-0.5 * LOG2PI * w.numel() - self.scale.double().log().sum() - 0.5 * ((w / self.scale).double() ** 2).sum())
-        white = (nbody.rfftn(w) if self.precond == "real" else rg2cgh(w)) * self.transfer
-        cosmo = self.make_cosmo(base)
-        bias = {k: base[k] for k in bricks.BIAS_KEYS}
-        png = {k: float(base.get(k, 0.0)) for k in bricks.PNG_KEYS} if fwd.png_type is not None else None
-        # Omega_m sampled: the forward model makes the two evaluations of the growth-table Jacobian as soon as it has queued its kernels
-        fwd.cosmo_fd_params = ("Omega_m",) if "Omega_m" in self.latents else None
-        kw = {} if png is None else {"png": png}
-        if getattr(fwd, "ap_auto", None) is False:
-            kw["ap"] = {k: float(base.get(k, 1.0)) for k in bricks.AP_KEYS}
-        gxy, ctx = fwd.evolve(cosmo, bias, white, return_ctx=True, **kw)
-        # likelihood (model.py:852-866, :893-908): per-cell count multiplier from the shells' mean densities
-        rcounts = np.atleast_1d(np.asarray(base["ngbars"], dtype=np.float64)) * fwd.cell_length ** 3
-        rc_ext = torch.from_numpy(np.append(rcounts, 1.0).astype(np.float32)).to(gxy.device)
-        rc = rc_ext[self.shell]
-        selec = float(rcounts.mean()) if self.sel_down is None else (self.sel_down * rc).abs()
-        gsel = gxy if self.selec_mesh is None else gxy * self.selec_mesh
-        resh = tuple(gxy.shape) != self.final_shape
-        dn = self._down(gsel)
-        cm = dn * rc
-        if self.lik_type != "quad_gauss":      # csrc/likelihood.hip: value, mesh cotangents and float64 sums from one kernel
-            lpl, cm_bar, stoch_bar, qb, qsum, selec = self._lik_hip(base, cm, selec, self.ngb_lat is not None)
-            lp += lpl
-            if not need_grad:
-                return lp, None
-            gxy_bar = cm_bar * rc
-            ngb_bar = None
-            if self.ngb_lat is not None:      # d/d rcounts: count = dn rc at fixed selec, and selec (|S rc| per cell, or mean(rcounts)) at fixed count
-                per = torch.bincount(self.shell.reshape(-1), weights=(cm_bar * dn).double().reshape(-1), minlength=self.n_rbins + 1)[:self.n_rbins]
-                if self.sel_down is not None:
-                    sq_bar = qb * 0.5 * selec ** -.5 * self.sel_down.abs() * torch.sign(rc)
-                    per = per + torch.bincount(self.shell.reshape(-1), weights=sq_bar.double().reshape(-1), minlength=self.n_rbins + 1)[:self.n_rbins]
-                    rcounts_bar = per.cpu().numpy()
-                else:
-                    rcounts_bar = per.cpu().numpy() + qsum * 0.5 * selec ** -.5 / self.n_rbins
-                ngb_bar = rcounts_bar * fwd.cell_length ** 3
-        else:
-            # Only the observed cells carry a likelihood term: the reference extracts them first (mesh2masked, model.py:856-863).
-            # Here every cell is evaluated, so the unobserved ones are given safe inputs (selection 1, count 0 -- a cut-sky
-            # selection is exactly 0 there and count / selec would be NaN) and are removed with `where`, never by multiplying.
-            obs, cmu = self.count_obs, cm
-            if self.mask is not None:
-                if torch.is_tensor(selec):
-                    selec = torch.where(self.mask, selec, torch.ones_like(selec))
-                cmu = torch.where(self.mask, cm, torch.zeros_like(cm))
-                obs = torch.where(self.mask, obs, torch.zeros_like(obs))
-            delta = cmu / selec - 1.0
-            lin = base["s_e"] + base["s_ed"] * delta
-            b = (lin.abs() + 1e-9) * selec ** .5
-            a = 0.0 if abs(float(base["s_e2"])) < 1e-10 else float(base["s_e2"]) * selec ** .5
-            lpe, g_loc, g_b, g_a = quad_gaussian_log_prob_and_grad(obs, cmu, b, a)
-            if self.mask is not None:
-                zero = torch.zeros_like(lpe)
-                lpe, g_loc, g_b = torch.where(self.mask, lpe, zero), torch.where(self.mask, g_loc, zero), torch.where(self.mask, g_b, zero)
-                g_a = torch.where(self.mask, g_a, zero) if torch.is_tensor(g_a) else g_a
-            lp += float(lpe.double().sum())
-            if not need_grad:
-                return lp, None
-            sgn = torch.sign(lin) * selec ** .5
-            cm_bar = g_loc + g_b * sgn * (base["s_ed"] / selec)
-            stoch_bar = {"s_e": float((g_b * sgn).double().sum()), "s_ed": float((g_b * sgn * delta).double().sum()),
-                         "s_e2": float((g_a * selec ** .5).double().sum())}
-            gxy_bar = cm_bar * rc
-            ngb_bar = None
-            if self.ngb_lat is not None:      # d/d rcounts: through count = dn rc and through selec (|S rc| per cell, or mean(rcounts))
-                wsel = g_b * (lin.abs() + 1e-9) + (g_a * float(base["s_e2"]) if torch.is_tensor(g_a) else 0.0)   # d lp / d sqrt(selec)
-                if self.sel_down is not None:
-                    # delta = count / selec does not move with rc; selec = |S| |rc|
-                    rc_bar = g_loc * dn + wsel * 0.5 * selec ** -.5 * self.sel_down.abs() * torch.sign(rc)
-                    per = torch.bincount(self.shell.reshape(-1), weights=rc_bar.double().reshape(-1), minlength=self.n_rbins + 1)[:self.n_rbins]
-                    rcounts_bar = per.cpu().numpy()
-                else:
-                    rc_bar = cm_bar * dn
-                    per = torch.bincount(self.shell.reshape(-1), weights=rc_bar.double().reshape(-1), minlength=self.n_rbins + 1)[:self.n_rbins]
-                    common = float((-(g_b * sgn * base["s_ed"]) * cmu / selec ** 2 + wsel * 0.5 * selec ** -.5).double().sum())
-                    rcounts_bar = per.cpu().numpy() + common / self.n_rbins
-                ngb_bar = rcounts_bar * fwd.cell_length ** 3
-        if resh:      # adjoints of irfftn, chreshape, rfftn (real-pair convention)
-            Mf = float(np.prod(self.final_shape))
-            kb = nbody.rfftn(gxy_bar) / Mf
-            kb[..., 1:self.final_shape[-1] // 2] *= 2.0
-            kb = chreshape_vjp(kb, r2chshape(tuple(gxy.shape)))
-            kb[..., 1:gxy.shape[-1] // 2] *= 0.5
-            plan = nbody.get_plan(tuple(gxy.shape))
-            gxy_bar = torch.empty(tuple(gxy.shape), dtype=torch.float32, device=kb.device)
-            plan.call("mcpm_fft_c2r", nbody._ptr(kb), nbody._ptr(gxy_bar), 1)
-        if self.selec_mesh is not None:
-            gxy_bar = gxy_bar * self.selec_mesh
-        g = fwd.evolve_vjp(ctx, gxy_bar)
-        wb = g["white_mesh"] * self.transfer
-        if self.precond != "real":
-            wbar = rg2cgh_vjp(wb)
-        else:
-            wb = wb.clone()
-            wb[..., 1:fwd.init_shape[-1] // 2] *= 0.5
-            wbar = torch.empty(fwd.init_shape, dtype=torch.float32, device=wb.device)
-            nbody.get_plan(fwd.init_shape).call("mcpm_fft_c2r", nbody._ptr(wb), nbody._ptr(wbar), 1)
-        grad["white_mesh_"] = wbar - (w if self.scale is None else w / self.scale ** 2)
-        if ngb_bar is not None:
-            grad["ngbars_"] = ngb_prior_grad + ngb_bar * ngb_dbase
+    def _zero_grad(self, sample):
+        """The gradient's full structure, all zeros."""
+        zgrad = {name + "_": 0.0 for name in self.latents}
+        if self.ngb_lat is not None:
+            zgrad["ngbars_"] = np.zeros(self.n_rbins)
+        w0 = sample["white_mesh_"]
+        zgrad["white_mesh_"] = (torch.zeros_like(w0) if torch.is_tensor(w0)
+                                else torch.zeros(self.fwd.init_shape, dtype=torch.float32, device=nbody._device()))
+        return zgrad
+
+    def _base_bar(self, f, g, stoch_bar):
+        """Cotangents of the scalar base parameters from those of `evolve_vjp` (g) and of the likelihood; 0 for one that is not read."""
         base_bar = {k: 0.0 for k in bricks.PNG_KEYS}      # (without png_type the model does not read them)
         base_bar.update(g.get("png", {}))
         base_bar.update({k: 0.0 for k in bricks.AP_KEYS})      # (read only with ap_auto = False)
@@ -610,7 +542,35 @@ class FieldLevelLogDensity:
         base_bar.update(stoch_bar)
         base_bar["sigma8"] = g["sigma8"]
         if "Omega_m" in self.latents:
-            base_bar["Omega_m"] = fwd.cosmo_vjp(ctx, g, params=("Omega_m",))["Omega_m"]
+            base_bar["Omega_m"] = self.fwd.cosmo_vjp(f.ctx, g, params=("Omega_m",))["Omega_m"]
+        return base_bar
+
+    def logdensity_and_grad(self, sample, need_grad=True):
+        """sample: dict with the scalars `name_` (floats) and 'white_mesh_' (real tensor, fwd.init_shape).
+        Returns (log density, dict of gradients with the same keys)."""
+        fwd = self.fwd
+        lp, base, grad, dbase = self._prior(sample)
+        if lp == -math.inf:      # a latent sits in a saturated tail: zero density whatever the field (no forward model needed)
+            # the gradient keeps its full structure (zeros), so that callers which index it before looking at the value --
+            # jax_bridge.logdensity_fn builds a tuple over all names -- get a rejected proposal, not a KeyError
+            return -math.inf, (self._zero_grad(sample) if need_grad else None)
+        w = nbody._f32(sample["white_mesh_"], fwd.init_shape)
+        lp += self._white_prior(w)
+        f = self._forward(base, w, need_ctx=True)
+        lpl, cm_bar, stoch_bar, rcounts_bar = (self._lik_quad_gauss if self.lik_type == "quad_gauss" else self._lik_hip)(base, f, need_grad)
+        lp += lpl
+        if not need_grad:
+            return lp, None
+        gxy_bar = self._down_vjp(cm_bar * f.rc, f.gxy.shape)
+        if self.selec_mesh is not None:
+            gxy_bar = gxy_bar * self.selec_mesh
+        g = fwd.evolve_vjp(f.ctx, gxy_bar)
+        wb = g["white_mesh"] * self.transfer
+        wbar = nbody.rfftn_vjp(wb, overwrite=True) if self.precond == "real" else rg2cgh_vjp(wb)
+        grad["white_mesh_"] = wbar - (w if self.scale is None else w / self.scale ** 2)
+        if rcounts_bar is not None:
+            grad["ngbars_"] = grad.pop("ngbars_") + rcounts_bar * fwd.cell_length ** 3 * dbase["ngbars"]
+        base_bar = self._base_bar(f, g, stoch_bar)
         for name in self.latents:
             grad[name + "_"] += base_bar[name] * dbase[name]
         return lp, grad

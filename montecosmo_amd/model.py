@@ -72,7 +72,7 @@ class FieldLevelForward:
         # (bricks.py:69-79; montecosmo_amd/power.py), re-tabulated whenever Omega_m / Omega_b / h / n_s change
         self.lin_kpow = None if lin_kpow is None else (np.asarray(lin_kpow[0], dtype=np.float64), np.asarray(lin_kpow[1], dtype=np.float64))
         self._dev_kpow = {}
-        self._r0 = None
+        self._r0 = self._los_cell = None
 
     def config(self):
         """The model attributes as a dict (what the parity tests hand to their float64 checker)."""
@@ -119,6 +119,20 @@ class FieldLevelForward:
                   nbody.C.c_void_p(tab.data_ptr() + 8 * nt), nt, nbody._ptr(out))
         return out
 
+    def los_cell(self):
+        """Line of sight (the direction of the box centre) in cell axes (model.py:607-608); host float64, computed once."""
+        if self._los_cell is None:
+            self._los_cell = bricks.rot_matrix(self.box_rotvec).T @ nbody.safe_div(self.box_center, np.linalg.norm(self.box_center))
+        return self._los_cell
+
+    def lattice_radius(self, mesh_shape, ptcl_shape=None, flat_dot=np.matmul):
+        """Physical distance of the points of a regular lattice (bricks.py:665-686), flat host float64 array: |x| on the curved sky, |x . los|
+        on the flat one (`flat_dot` forms the product)."""
+        p = bricks.cell2phys_pos(bricks.regular_pos(mesh_shape, ptcl_shape), self.box_center, self.box_rotvec, self.box_size, mesh_shape)
+        if self.curved_sky:
+            return np.linalg.norm(p, axis=-1)
+        return np.abs(flat_dot(p, nbody.safe_div(self.box_center, np.linalg.norm(self.box_center))))
+
     def _scale_factors(self, cosmo):
         """Scale factor(s) of the Lagrangian lattice (model.py:741-742): a_obs, or chi2a(|x|) per particle as a device
         tensor (N,1).  The lattice is fixed, so its physical distances are computed once (host float64) and kept on
@@ -126,14 +140,9 @@ class FieldLevelForward:
         if self.a_obs is not None:
             return self.a_obs
         if self._r0 is None:
-            pos = bricks.regular_pos(self.evol_shape, self.ptcl_shape)
-            p = bricks.cell2phys_pos(pos, self.box_center, self.box_rotvec, self.box_size, self.evol_shape)
-            if self.curved_sky:
-                r0 = np.linalg.norm(p, axis=-1)
-            else:
-                los = nbody.safe_div(self.box_center, np.linalg.norm(self.box_center))
-                r0 = np.abs((p * los).sum(-1))
-            self._r0 = nbody._f32(r0)
+            # the flat-sky product is summed per row here and by `@` in the log density: the two differ in the last bit of a float64,
+            # and each consumer keeps the bits it has always had
+            self._r0 = nbody._f32(self.lattice_radius(self.evol_shape, self.ptcl_shape, flat_dot=lambda p, los: (p * los).sum(-1)))
         d = nbody._dist_cache(cosmo)
         return nbody.interp_dev(self._r0, d["chi"][::-1], d["a"][::-1]).reshape(-1, 1)
 
@@ -141,10 +150,9 @@ class FieldLevelForward:
     def _mu2_mesh(self, device):
         """(k . los)^2 / k^2 on the half-spectrum of the evolution mesh, los = the box centre's direction in cell axes."""
         if getattr(self, "_mu2", None) is None:
-            los = bricks.rot_matrix(self.box_rotvec).T @ nbody.safe_div(self.box_center, np.linalg.norm(self.box_center))
             kvec = nbody.rfftk(self.evol_shape, self.box_size)
             kk = sum(k ** 2 for k in kvec)
-            mu2 = nbody.safe_div(sum(k * l for k, l in zip(kvec, los)) ** 2, kk)
+            mu2 = nbody.safe_div(sum(k * l for k, l in zip(kvec, self.los_cell())) ** 2, kk)
             self._mu2 = torch.from_numpy(np.ascontiguousarray(mu2, dtype=np.float32)).to(device)
         return self._mu2
 
@@ -173,8 +181,7 @@ class FieldLevelForward:
         cosmo = ctx.cosmo
         D, f, b1, boost = ctx.kaiser
         gb = nbody._f32(gxy_bar, self.evol_shape)
-        kb = nbody.rfftn(gb) / float(np.prod(self.evol_shape))           # irfftn adjoint (real-pair convention)
-        kb[..., 1:self.evol_shape[-1] // 2] *= 2.0
+        kb = nbody.irfftn_vjp(gb)
         prod = kb.conj() * ctx.evol_k
         c0 = float(prod.real.double().sum())                              # d/d(D b1E)
         c1 = float((prod.real * self._mu2_mesh(kb.device)).double().sum())    # d/d(D f)
@@ -268,11 +275,7 @@ class FieldLevelForward:
             return self._kaiser_vjp(ctx, gxy_bar)
         cosmo = ctx.cosmo
         gb = nbody._f32(gxy_bar, self.paint_shape)
-        # irfftn adjoint: X_bar = (w / M) rfftn(y_bar)
-        Mp = float(np.prod(self.paint_shape))
-        kb = nbody.rfftn(gb) / Mp
-        kb[..., 1:self.paint_shape[-1] // 2] *= 2.0
-        kb = chreshape_vjp(kb, r2chshape(self.init_shape)) * ctx.jac
+        kb = chreshape_vjp(nbody.irfftn_vjp(gb), r2chshape(self.init_shape)) * ctx.jac
         pb, wb = nbody.nufft_vjp(ctx.pos_c, self.init_shape, ctx.w, kb, self.paint_order, self.interlace_order, self.paint_deconv,
                                  paint_shape=self.paint_shape)
         extra = {}
@@ -316,7 +319,6 @@ class FieldLevelForward:
         same central difference of the host distance table as `_cosmo_vjp_lightcone` (the fiducial table does not move).
         `params`: attribute names of the cosmology object; 'Omega_m' varies Omega_c at fixed Omega_b.  On the light cone
         (a_obs = None) the look-ups are per particle: `_cosmo_vjp_lightcone`."""
-        import copy
         if self.a_obs is None:
             return self._cosmo_vjp_lightcone(ctx, grads, params, rel_eps)
         cosmo, a = ctx.cosmo, self.a_obs
@@ -337,18 +339,12 @@ class FieldLevelForward:
         chi_bar = grads["ap_chi_bar"].cpu().numpy() if grads.get("ap_chi_bar") is not None else None
         out = {}
         for name in params:
-            attr = "Omega_c" if name == "Omega_m" else name
-            base = float(getattr(cosmo, attr))
-            h = rel_eps * max(abs(base), 1e-2)
-            vals, inits = [], []
-            cached = pre.get((name, rel_eps))      # the table Jacobian's two evaluations, made while the device ran the forward pass
-            for sgn in (+1, -1):
-                c = copy.copy(cosmo)
-                setattr(c, attr, base + sgn * h)
-                vals.append(cached[len(vals)] if cached is not None else self._cosmo_scalars_chi(c))
-                if self.lin_kpow is None:      # the Eisenstein-Hu shape moves with the cosmology: init_mesh = white sqrt(P)
-                    inits.append(self._power_mult(ctx.white, c))
-            out[name] = float(np.dot(bars, (vals[0][0] - vals[1][0]) / (2 * h))) + self._trans_term(cosmo, grads, attr, base, h)
+            h, pair = self._cosmo_fd_pair(cosmo, name, rel_eps)
+            # the table Jacobian's two evaluations: made while the device ran the forward pass, or here
+            vals = pre.get((name, rel_eps)) or [self._cosmo_scalars_chi(c) for c in pair]
+            # the Eisenstein-Hu shape moves with the cosmology: init_mesh = white sqrt(P)
+            inits = [self._power_mult(ctx.white, c) for c in pair] if self.lin_kpow is None else []
+            out[name] = float(np.dot(bars, (vals[0][0] - vals[1][0]) / (2 * h))) + self._trans_term(grads, pair, h)
             if chi_bar is not None:
                 out[name] += float(np.dot(chi_bar, (vals[0][1] - vals[1][1]) / (2 * h)))
             if inits:
@@ -356,19 +352,31 @@ class FieldLevelForward:
         cosmo._workspace = {}
         return out
 
-    def _trans_term(self, cosmo, grads, attr, base, h):
-        """<trans_bar, d trans / d theta> for the phi -> delta transfer table (png_type set), the table Jacobian by the same host
-        central difference as the growth tables.  (sigma8 cancels in the table, so its derivative has no such term.)"""
+    @staticmethod
+    def _cosmo_fd_pair(cosmo, name, rel_eps):
+        """(h, [cosmology at +h, at -h]) of a central difference over one parameter of the cosmology; 'Omega_m' varies Omega_c at fixed
+        Omega_b.  Each copy starts with an empty `_workspace` of its own (a plain copy would share the dict), so whatever reads its tables
+        derives them from the copy's attributes and `cosmo`'s cached tables stay as they are."""
         import copy
-        if grads.get("trans_bar") is None:
-            return 0.0
-        kpow = self.lin_kpow if self.evolution == 'kaiser' else None
-        tr = []
+        attr = "Omega_c" if name == "Omega_m" else name
+        base = float(getattr(cosmo, attr))
+        h = rel_eps * max(abs(base), 1e-2)
+        pair = []
         for sgn in (+1, -1):
             c = copy.copy(cosmo)
             c._workspace = {}
             setattr(c, attr, base + sgn * h)
-            tr.append(bricks.trans_phi2delta_table(c, kpow=kpow)[1])
+            pair.append(c)
+        return h, pair
+
+    def _trans_term(self, grads, pair, h):
+        """<trans_bar, d trans / d theta> for the phi -> delta transfer table (png_type set), the table Jacobian by the same host
+        central difference (`pair`, `h` of `_cosmo_fd_pair`) as the growth tables.  (sigma8 cancels in the table, so its derivative has no
+        such term.)"""
+        if grads.get("trans_bar") is None:
+            return 0.0
+        kpow = self.lin_kpow if self.evolution == 'kaiser' else None
+        tr = [bricks.trans_phi2delta_table(c, kpow=kpow)[1] for c in pair]
         return float(np.dot(grads["trans_bar"], (tr[0] - tr[1]) / (2 * h)))
 
     def _cosmo_scalars(self, c):
@@ -395,19 +403,8 @@ class FieldLevelForward:
         """{(name, rel_eps): ((scalars, chi nodes) at +h, the same at -h)}: the two evaluations of cosmo_vjp's central difference.  Host work of about
         a millisecond (two growth-table solves per parameter) that `evolve` does right after it has queued the forward pass, while the
         device runs it; left to cosmo_vjp it sits at the very end of a gradient, with the device idle (`cosmo_fd_params`)."""
-        import copy
-        out = {}
-        for name in params:
-            attr = "Omega_c" if name == "Omega_m" else name
-            base = float(getattr(cosmo, attr))
-            h = rel_eps * max(abs(base), 1e-2)
-            pair = []
-            for sgn in (+1, -1):
-                c = copy.copy(cosmo)
-                setattr(c, attr, base + sgn * h)
-                pair.append(self._cosmo_scalars_chi(c))
-            out[(name, rel_eps)] = tuple(pair)
-        return out      # (the copies carry their own tables: `cosmo`'s cached ones stay for the rest of evolve)
+        # (the copies carry their own tables: `cosmo`'s cached ones stay for the rest of evolve)
+        return {(name, rel_eps): tuple(self._cosmo_scalars_chi(c) for c in self._cosmo_fd_pair(cosmo, name, rel_eps)[1]) for name in params}
 
     # ---- light cone: the cosmology enters through per-particle table look-ups -----------------------------------------
     _LC_TABLES = ("chi", "g", "g2", "f", "f2")
@@ -448,26 +445,17 @@ class FieldLevelForward:
         """cosmo_vjp on the light cone (a_obs = None, the reference's default configuration, model.py:45, :62): dL/dtheta =
         sum over the five tables of <table_bar, d table / d theta>, the table Jacobian by central differences of the host
         float64 RK4 tables (256-point distance table, 128-point growth tables), plus the Eisenstein-Hu term as at fixed a_obs."""
-        import copy
         if self.evolution != 'lpt':
             raise NotImplementedError("light cone is built for evolution='lpt' (model.py:770 asserts the same for 'nbody')")
         cosmo = ctx.cosmo
         bars = self.lightcone_table_bars(ctx, grads)
         out = {}
         for name in params:
-            attr = "Omega_c" if name == "Omega_m" else name
-            base = float(getattr(cosmo, attr))
-            h = rel_eps * max(abs(base), 1e-2)
-            tabs, inits = [], []
-            for sgn in (+1, -1):
-                c = copy.copy(cosmo)
-                c._workspace = {}
-                setattr(c, attr, base + sgn * h)
-                tabs.append(self._lightcone_tables(c))
-                if self.lin_kpow is None:
-                    inits.append(self._power_mult(ctx.white, c))
+            h, pair = self._cosmo_fd_pair(cosmo, name, rel_eps)
+            tabs = [self._lightcone_tables(c) for c in pair]
+            inits = [self._power_mult(ctx.white, c) for c in pair] if self.lin_kpow is None else []
             out[name] = float(sum(np.dot(bars[k], (tabs[0][k] - tabs[1][k]) / (2 * h)) for k in self._LC_TABLES))
-            out[name] += self._trans_term(cosmo, grads, attr, base, h)
+            out[name] += self._trans_term(grads, pair, h)
             if inits:
                 out[name] += float((grads["init_bar"].conj() * (inits[0] - inits[1])).real.sum().item()) / (2 * h)
         return out

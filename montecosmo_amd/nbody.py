@@ -417,6 +417,27 @@ def irfftn(spec):
     return out / plan.M
 
 
+def rfftn_vjp(spec_bar, overwrite=False):
+    """Adjoint of `rfftn` in the real-pair convention: cotangent of the half spectrum -> real mesh.  An unnormalised C2R, which counts the
+    modes 1 : n_z // 2 of the last axis twice: they are halved first.  `overwrite`: the caller owns `spec_bar` (C2R destroys its input)."""
+    spec = _c64(spec_bar)
+    if not overwrite:
+        spec = spec.clone()
+    shape = ch2rshape(spec.shape)
+    spec[..., 1:shape[-1] // 2] *= 0.5
+    out = torch.empty(shape, dtype=torch.float32, device=spec.device)
+    get_plan(shape).call("mcpm_fft_c2r", _ptr(spec), _ptr(out), 1)
+    return out
+
+
+def irfftn_vjp(mesh_bar):
+    """Adjoint of `irfftn` in the real-pair convention: cotangent of the real mesh -> half spectrum, rfftn(mesh_bar) / M with the
+    modes 1 : n_z // 2 of the last axis (each stands for itself and its mirror image) doubled."""
+    kb = rfftn(mesh_bar) / float(np.prod(mesh_bar.shape))
+    kb[..., 1:mesh_bar.shape[-1] // 2] *= 2.0
+    return kb
+
+
 # ------------------------------------------------------------------------------------------------
 # observation-side painting (nbody.py:315-334, :513-577): runs once per log-prob, outside the step loop
 def _shift_pos(pos, shift):
