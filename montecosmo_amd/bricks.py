@@ -6,9 +6,13 @@ Primordial non-Gaussianity (png_type 'fNL' / 'bias'): the transfer table, `add_p
 the `fNL_bias` reparametrisation, each with its VJP.  Alcock-Paczynski: `scale_pos`, `parperp2isoap`, `isoap2parperp` on the host and
 the `ap_auto` / `ap_param` remapping inside `observe_pos` (bricks.py:708-732, :795-857).  Out of scope: Eulerian bias, the stochastic term s_ep * phi of the likelihood
 (model.py:894) and PNG on the light-cone and curved-sky forms of the Kaiser model."""
+import ctypes as C
 import os
 
 import numpy as np
+import torch
+
+from . import _lib, nbody, power, utils
 
 
 class Cosmology:
@@ -55,9 +59,7 @@ def regular_pos(mesh_shape, ptcl_shape=None):
 BIAS_KEYS = ("b1", "b2", "bs2", "b3", "bds2", "bs3", "bn2", "bnpar")
 
 
-class BiasCtx:
-    def __init__(self, **kw):
-        self.__dict__.update(kw)
+BiasCtx = PngCtx = ObsCtx = _lib.Ctx
 
 
 def lagrangian_bias(cosmo, pos, a, box_size, lin_mesh, bias, png=None, png_type=None, kpow=None, read_order: int = 2,
@@ -69,9 +71,6 @@ def lagrangian_bias(cosmo, pos, a, box_size, lin_mesh, bias, png=None, png_type=
     png_type None: phi = 0.  Otherwise `png` holds the products 'fNL_bp', 'fNL_bpd' (what `fNL_bias` returns), 'fNL_bpd2',
     'fNL_bps2', 'fNL_bn2p' (missing = 0); phi = irfftn(lin / t) and lap phi are formed (mcpm_png_phi_f32, two transforms), read
     at the particles and the five terms of bricks.py:413-441 added (mcpm_png_weights_f32); phi comes back as a device mesh."""
-    import ctypes as C
-    import torch
-    from . import nbody
     if png_type not in (None, "fNL", "bias"):
         raise ValueError(f"png_type must be None, 'fNL' or 'bias', got {png_type!r}")
     spec = nbody._c64(lin_mesh)
@@ -83,7 +82,7 @@ def lagrangian_bias(cosmo, pos, a, box_size, lin_mesh, bias, png=None, png_type=
     fields = torch.empty((7,) + tuple(shape), dtype=torch.float32, device=dev)
     # with a context for the adjoint, delta and the Hessian meshes stay resident for it (six transforms less per gradient)
     hess6 = torch.empty((6,) + tuple(shape), dtype=torch.float32, device=dev) if (return_ctx and os.environ.get("MCPM_BIAS_KEEP", "1") != "0") else None
-    plan.call("mcpm_bias_fields_save_f32", nbody._ptr(spec), kphys[0], kphys[1], kphys[2], nbody._ptr(fields), nbody._ptr(hess6))
+    plan.call("mcpm_bias_fields_save_f32", spec, kphys[0], kphys[1], kphys[2], fields, hess6)
     # NGP read at the mesh's own lattice points is the identity: the fields themselves are the reads (no pass at all)
     ident = (int(read_order) == 1 and isinstance(pos, nbody.LatticePos) and pos.is_regular and tuple(pos.ptcl_shape) == tuple(shape))
     if ident:
@@ -92,9 +91,9 @@ def lagrangian_bias(cosmo, pos, a, box_size, lin_mesh, bias, png=None, png_type=
         gcs = 0
         reads = torch.empty((4, n), dtype=torch.float32, device=dev)
         for c in range(4):
-            plan.call("mcpm_read_f32", nbody._ptr(p), n, mode, nbody._ptr(fields[c]), 1, int(read_order), nbody._ptr(reads[c]))
+            plan.call("mcpm_read_f32", p, n, mode, fields[c], 1, int(read_order), reads[c])
         gr = torch.empty((n, 3), dtype=torch.float32, device=dev)
-        plan.call("mcpm_read_f32", nbody._ptr(p), n, mode, nbody._ptr(fields[4]), 3, int(read_order), nbody._ptr(gr))
+        plan.call("mcpm_read_f32", p, n, mode, fields[4], 3, int(read_order), gr)
     if isinstance(a, torch.Tensor) and a.is_cuda:      # per-particle scale factors on the device (light cone)
         gp, g_shape = nbody.growth_dev(cosmo, a, "g"), tuple(a.shape)
         if gp.numel() != n:
@@ -108,24 +107,21 @@ def lagrangian_bias(cosmo, pos, a, box_size, lin_mesh, bias, png=None, png_type=
     b8 = (C.c_float * 8)(*[float(bias.get(k, 0.0)) for k in BIAS_KEYS])
     w = torch.empty(n, dtype=torch.float32, device=dev)
     dvel = torch.empty((n, 3), dtype=torch.float32, device=dev)
-    plan.call("mcpm_bias_weights_f32", n, nbody._ptr(reads[0]), nbody._ptr(reads[1]), nbody._ptr(reads[2]), nbody._ptr(reads[3]),
-              nbody._ptr(gr), gcs, nbody._ptr(gp), gs, b8, nbody._ptr(w), nbody._ptr(dvel), None)
+    plan.call("mcpm_bias_weights_f32", n, reads[0], reads[1], reads[2], reads[3], gr, gcs, gp, gs, b8, w, dvel, None)
     phi, pctx = 0., None
     if png_type is not None:
         png = png or {}
         tab, nt = png_table_dev(cosmo, kpow, dev)
         pl = torch.empty((2,) + tuple(shape), dtype=torch.float32, device=dev)      # phi, lap phi
-        plan.call("mcpm_png_phi_f32", nbody._ptr(spec), kphys[0], kphys[1], kphys[2], nbody._ptr(tab), tab.data_ptr() + 8 * nt, nt,
-                  nbody._ptr(pl[0]), nbody._ptr(pl[1]))
+        plan.call("mcpm_png_phi_f32", spec, kphys[0], kphys[1], kphys[2], tab, tab[nt:], nt, pl[0], pl[1])
         if ident:
             pr = pl.reshape(2, n)
         else:
             pr = torch.empty((2, n), dtype=torch.float32, device=dev)
             for c in range(2):
-                plan.call("mcpm_read_f32", nbody._ptr(p), n, mode, nbody._ptr(pl[c]), 1, int(read_order), nbody._ptr(pr[c]))
+                plan.call("mcpm_read_f32", p, n, mode, pl[c], 1, int(read_order), pr[c])
         b5 = (C.c_float * 5)(*[float(png.get(k, 0.0)) for k in PNG_KEYS[1:]])
-        plan.call("mcpm_png_weights_f32", n, nbody._ptr(reads[0]), nbody._ptr(reads[1]), nbody._ptr(pr[0]), nbody._ptr(pr[1]), nbody._ptr(gp),
-                  gs, b5, nbody._ptr(w), None)
+        plan.call("mcpm_png_weights_f32", n, reads[0], reads[1], pr[0], pr[1], gp, gs, b5, w, None)
         phi, pctx = pl[0], BiasCtx(tab=tab, nt=nt, pr=pr, b5=b5)
     if return_ctx:
         ctx = BiasCtx(plan=plan, spec=spec, shape=shape, p=p, n=n, mode=mode, kphys=kphys, reads=reads, gr=gr, gp=gp, gs=gs,
@@ -143,8 +139,6 @@ def lagrangian_bias_vjp(ctx, weights_bar, dvel_bar, defer_phi=False):
     particles: its cotangent is a fixed-order float64 sum handed back to every particle (mcpm_png_weights_vjp_f32).
     `defer_phi`: the sixth output is instead the pair of real meshes (phi_bar, lap_phi_bar) and lin_mesh_bar leaves their share
     out -- the caller hands them to `add_png_vjp`, where they meet add_png's own phi cotangent before the single divide by t."""
-    import torch
-    from . import nbody
     plan, n, dev = ctx.plan, ctx.n, ctx.spec.device
     wb = nbody._f32(weights_bar, (n,))
     vb = nbody._f32(dvel_bar, (n, 3))
@@ -157,29 +151,27 @@ def lagrangian_bias_vjp(ctx, weights_bar, dvel_bar, defer_phi=False):
     gbar = torch.empty(n, dtype=torch.float32, device=dev) if ctx.gp is not None else None
     scal = torch.zeros(10, dtype=torch.float64, device=dev)
     r = ctx.reads
-    plan.call("mcpm_bias_weights_vjp_f32", n, nbody._ptr(r[0]), nbody._ptr(r[1]), nbody._ptr(r[2]), nbody._ptr(r[3]), nbody._ptr(ctx.gr),
-              ctx.gcs, nbody._ptr(ctx.gp), ctx.gs, ctx.b8, nbody._ptr(wb), nbody._ptr(vb), nbody._ptr(rb[0]), nbody._ptr(rb[1]),
-              nbody._ptr(rb[2]), nbody._ptr(rb[3]), nbody._ptr(grb), nbody._ptr(gbar), nbody._ptr(scal))
+    plan.call("mcpm_bias_weights_vjp_f32", n, r[0], r[1], r[2], r[3], ctx.gr, ctx.gcs, ctx.gp, ctx.gs, ctx.b8, wb, vb, rb[0], rb[1], rb[2], rb[3],
+              grb, gbar, scal)
     pc = getattr(ctx, "png", None)
     if pc is not None:
         plb = torch.empty((2,) + tuple(ctx.shape), dtype=torch.float32, device=dev)      # cotangents of the phi, lap phi meshes
         prb = plb.reshape(2, n) if ctx.gcs else torch.empty((2, n), dtype=torch.float32, device=dev)
         pscal = torch.zeros(10, dtype=torch.float64, device=dev)
-        plan.call("mcpm_png_weights_vjp_f32", n, nbody._ptr(r[0]), nbody._ptr(r[1]), nbody._ptr(pc.pr[0]), nbody._ptr(pc.pr[1]), nbody._ptr(ctx.gp),
-                  ctx.gs, pc.b5, nbody._ptr(wb), nbody._ptr(rb[0]), nbody._ptr(rb[1]), nbody._ptr(prb[0]), nbody._ptr(prb[1]), nbody._ptr(gbar),
-                  nbody._ptr(pscal))
+        plan.call("mcpm_png_weights_vjp_f32", n, r[0], r[1], pc.pr[0], pc.pr[1], ctx.gp, ctx.gs, pc.b5, wb, rb[0], rb[1], prb[0], prb[1], gbar,
+                  pscal)
         if not ctx.gcs:
             for c in range(2):
-                plan.call("mcpm_paint_f32", nbody._ptr(ctx.p), n, ctx.mode, nbody._ptr(prb[c]), 1, 0.0, ctx.read_order, nbody._ptr(plb[c]), 0)
+                plan.call("mcpm_paint_f32", ctx.p, n, ctx.mode, prb[c], 1, 0.0, ctx.read_order, plb[c], 0)
     if not ctx.gcs:
         for c in range(4):       # adjoint of a read w.r.t. its mesh = a weighted paint
-            plan.call("mcpm_paint_f32", nbody._ptr(ctx.p), n, ctx.mode, nbody._ptr(rb[c]), 1, 0.0, ctx.read_order, nbody._ptr(fb[c]), 0)
-        plan.call("mcpm_paint3_f32", nbody._ptr(ctx.p), n, ctx.mode, nbody._ptr(grb), ctx.read_order, nbody._ptr(fb[4]), 0)
+            plan.call("mcpm_paint_f32", ctx.p, n, ctx.mode, rb[c], 1, 0.0, ctx.read_order, fb[c], 0)
+        plan.call("mcpm_paint3_f32", ctx.p, n, ctx.mode, grb, ctx.read_order, fb[4], 0)
     out = torch.empty(tuple(ctx.spec.shape), dtype=torch.complex64, device=dev)
     if getattr(ctx, "hess6", None) is not None:
-        plan.call("mcpm_bias_fields_vjp_saved_f32", ctx.kphys[0], ctx.kphys[1], ctx.kphys[2], nbody._ptr(ctx.hess6), nbody._ptr(fb), nbody._ptr(out))
+        plan.call("mcpm_bias_fields_vjp_saved_f32", ctx.kphys[0], ctx.kphys[1], ctx.kphys[2], ctx.hess6, fb, out)
     else:
-        plan.call("mcpm_bias_fields_vjp_f32", nbody._ptr(ctx.spec), ctx.kphys[0], ctx.kphys[1], ctx.kphys[2], nbody._ptr(fb), nbody._ptr(out))
+        plan.call("mcpm_bias_fields_vjp_f32", ctx.spec, ctx.kphys[0], ctx.kphys[1], ctx.kphys[2], fb, out)
     s = scal.cpu().numpy()
     bias_bar = {k: float(s[i]) for i, k in enumerate(BIAS_KEYS)}
     # per-particle growth cotangents stay on the device; a scalar one comes back as a float64 array of the shape of a2g(a)
@@ -208,7 +200,6 @@ def trans_phi2delta_table(cosmo, a=1., kpow=None):
     with D_md = a2g(a_md) / a_md at z = 10.  P_lin is `kpow` (a (ks, pows) tabulation) or the Eisenstein & Hu table of
     `power.lin_power_table`; its amplitude cancels in T, so the table does not depend on sigma8.  The look-up is linear and 0
     outside the table (mcpm_png_add_f32 does it on the device).  Host float64."""
-    from . import nbody, power
     ks, pows = power.lin_power_table(cosmo) if kpow is None else kpow
     ks, pows = np.asarray(ks, dtype=np.float64), np.asarray(pows, dtype=np.float64)
     pow_large = ks ** cosmo.n_s
@@ -225,7 +216,6 @@ _PNG_TABLES = {}
 def png_table_dev(cosmo, kpow, device):
     """(device float64 tensor [ks, trans], n): the table of `trans_phi2delta_table` at a = 1, built once per cosmology and power
     source and kept on the device (a handful of entries: a sampler revisits the same cosmology for every call of one gradient)."""
-    import torch
     key = (float(cosmo.Omega_c), float(cosmo.Omega_b), float(cosmo.h), float(cosmo.n_s), float(cosmo.Omega_k), float(cosmo.w0),
            float(cosmo.wa), None if kpow is None else id(kpow[0]), str(device))
     hit = _PNG_TABLES.get(key)
@@ -237,11 +227,6 @@ def png_table_dev(cosmo, kpow, device):
     return hit[0], hit[1]
 
 
-class PngCtx:
-    def __init__(self, **kw):
-        self.__dict__.update(kw)
-
-
 def add_png(cosmo, fNL, lin_mesh, box_size, kpow=None, return_ctx=False, phi=None):
     """Add local primordial non-Gaussianity to the linear field (bricks.py:129-141):
         phi = irfftn(safe_div(lin_mesh, t(|k|))),  phi <- phi + fNL (phi^2 - <phi^2>),  returns t(|k|) rfftn(phi)
@@ -249,8 +234,6 @@ def add_png(cosmo, fNL, lin_mesh, box_size, kpow=None, return_ctx=False, phi=Non
     already holds it (the third return value of `lagrangian_bias` on the same mesh), which saves the divide and one transform.
     HIP: mcpm_png_add_f32 (png_div_kernel -> C2R -> png_moment_kernel + fold -> png_quad_kernel -> R2C -> png_mult_kernel);
     <phi^2> is a fixed-order float64 sum, so repeat calls are bitwise equal."""
-    import torch
-    from . import nbody
     spec = nbody._c64(lin_mesh)
     shape = nbody.ch2rshape(spec.shape)
     plan, dev = nbody.get_plan(shape), spec.device
@@ -259,8 +242,7 @@ def add_png(cosmo, fNL, lin_mesh, box_size, kpow=None, return_ctx=False, phi=Non
     phi_t = nbody._f32(phi, shape) if phi is not None else torch.empty(tuple(shape), dtype=torch.float32, device=dev)
     out = torch.empty(tuple(spec.shape), dtype=torch.complex64, device=dev)
     mean = torch.empty(1, dtype=torch.float64, device=dev)
-    plan.call("mcpm_png_add_f32", nbody._ptr(spec), kphys[0], kphys[1], kphys[2], nbody._ptr(tab), tab.data_ptr() + 8 * nt, nt, float(fNL),
-              int(phi is not None), nbody._ptr(phi_t), nbody._ptr(out), nbody._ptr(mean))
+    plan.call("mcpm_png_add_f32", spec, kphys[0], kphys[1], kphys[2], tab, tab[nt:], nt, float(fNL), int(phi is not None), phi_t, out, mean)
     if return_ctx:
         return out, PngCtx(plan=plan, spec=spec, out=out, phi=phi_t, mean=mean, kphys=kphys, tab=tab, nt=nt, fNL=float(fNL))
     return out
@@ -269,13 +251,10 @@ def add_png(cosmo, fNL, lin_mesh, box_size, kpow=None, return_ctx=False, phi=Non
 def png_phi_vjp(plan, spec, kphys, tab, nt, phi_bar, lap_phi_bar=None):
     """Adjoint of (phi, lap phi) = irfftn((1, -k^2) safe_div(lin_mesh, t)) alone: real-mesh cotangents -> (lin_mesh_bar [complex64,
     real-pair convention], trans_bar [float64 numpy]).  HIP: mcpm_png_add_vjp_f32 without a cotangent of add_png's output."""
-    import torch
-    from . import nbody
     lin_bar = torch.empty(tuple(spec.shape), dtype=torch.complex64, device=spec.device)
     scal = torch.empty(1 + nt, dtype=torch.float64, device=spec.device)
-    plan.call("mcpm_png_add_vjp_f32", nbody._ptr(spec), None, None, None, kphys[0], kphys[1], kphys[2], nbody._ptr(tab), tab.data_ptr() + 8 * nt, nt,
-              0.0, None, nbody._ptr(nbody._f32(phi_bar)), nbody._ptr(None if lap_phi_bar is None else nbody._f32(lap_phi_bar)),
-              nbody._ptr(lin_bar), nbody._ptr(scal), scal.data_ptr() + 8)
+    plan.call("mcpm_png_add_vjp_f32", spec, None, None, None, kphys[0], kphys[1], kphys[2], tab, tab[nt:], nt, 0.0, None, nbody._f32(phi_bar),
+              None if lap_phi_bar is None else nbody._f32(lap_phi_bar), lin_bar, scal, scal[1:])
     return lin_bar, scal[1:].cpu().numpy()
 
 
@@ -287,16 +266,13 @@ def add_png_vjp(ctx, out_bar, phi_bar=None, lap_phi_bar=None, sync=True):
     bias weights, `lagrangian_bias_vjp(..., defer_phi=True)`); they are folded in before the divide by t.  `sync=False` returns the
     last two outputs as one device float64 tensor [fNL_bar, trans_bar...] instead of blocking on a copy to the host.
     HIP: mcpm_png_add_vjp_f32; every sum is order-independent, so repeat calls are bitwise equal."""
-    import torch
-    from . import nbody
     dev = ctx.spec.device
     ob = nbody._c64(out_bar, tuple(ctx.spec.shape))
     lin_bar = torch.empty(tuple(ctx.spec.shape), dtype=torch.complex64, device=dev)
     scal = torch.empty(1 + ctx.nt, dtype=torch.float64, device=dev)
-    ctx.plan.call("mcpm_png_add_vjp_f32", nbody._ptr(ctx.spec), nbody._ptr(ctx.out), nbody._ptr(ctx.phi), nbody._ptr(ctx.mean), ctx.kphys[0],
-                  ctx.kphys[1], ctx.kphys[2], nbody._ptr(ctx.tab), ctx.tab.data_ptr() + 8 * ctx.nt, ctx.nt, ctx.fNL, nbody._ptr(ob),
-                  nbody._ptr(None if phi_bar is None else nbody._f32(phi_bar)), nbody._ptr(None if lap_phi_bar is None else nbody._f32(lap_phi_bar)),
-                  nbody._ptr(lin_bar), nbody._ptr(scal), scal.data_ptr() + 8)
+    ctx.plan.call("mcpm_png_add_vjp_f32", ctx.spec, ctx.out, ctx.phi, ctx.mean, ctx.kphys[0], ctx.kphys[1], ctx.kphys[2], ctx.tab, ctx.tab[ctx.nt:],
+                  ctx.nt, ctx.fNL, ob, None if phi_bar is None else nbody._f32(phi_bar), None if lap_phi_bar is None else nbody._f32(lap_phi_bar),
+                  lin_bar, scal, scal[1:])
     if not sync:
         return lin_bar, scal
     s = scal.cpu().numpy()
@@ -423,14 +399,8 @@ def isoap2parperp(alpha_iso, alpha_ap):
     return alpha_par, alpha_perp
 
 
-class ObsCtx:
-    def __init__(self, **kw):
-        self.__dict__.update(kw)
-
-
 def _ap_args(ctx):
-    from . import nbody
-    return (ctx.ap_mode, ctx.alpha_iso, ctx.alpha_ap, nbody._ptr(ctx.ap_tables), ctx.nap, ctx.nfid)
+    return (ctx.ap_mode, ctx.alpha_iso, ctx.alpha_ap, ctx.ap_tables, ctx.nap, ctx.nfid)
 
 
 def observe_pos(cosmo, pos, vel, box_center, box_rot, box_size, evol_shape, paint_shape, a_obs=None, curved_sky=True,
@@ -442,9 +412,6 @@ def observe_pos(cosmo, pos, vel, box_center, box_rot, box_size, evol_shape, pain
     Alcock-Paczynski (model.py:787-794): ap_auto=None none (nothing new runs); True: positions scaled by
     a2chi(cosmo_fid, chi2a(cosmo, r)) / r (bricks.py:795-814; `cosmo_fid` required); False: by the parameters of
     `ap` = {'alpha_iso', 'alpha_ap'} (missing = 1; bricks.py:848-857)."""
-    import ctypes as C
-    import torch
-    from . import nbody, _lib
     evol_shape = tuple(int(s) for s in evol_shape)
     paint_shape = tuple(int(s) for s in paint_shape)
     plan, p, n, mode = nbody._pos_args(pos, evol_shape)
@@ -463,8 +430,7 @@ def observe_pos(cosmo, pos, vel, box_center, box_rot, box_size, evol_shape, pain
     out = torch.empty((n, 3), dtype=torch.float32, device=p.device)
     apkw = dict(ap_mode=_lib.AP_NONE, alpha_iso=1.0, alpha_ap=1.0, ap_tables=None, nap=0, nfid=0)
     if ap_auto is None:
-        plan.call("mcpm_observe_pos_f32", nbody._ptr(p), nbody._ptr(v), nbody._ptr(dv), n, mode, geom, flags, nbody._ptr(tables), nchi,
-                  ngrow, nbody._ptr(out))
+        plan.call("mcpm_observe_pos_f32", p, v, dv, n, mode, geom, flags, tables, nchi, ngrow, out)
     else:
         if ap_auto:
             if cosmo_fid is None:
@@ -475,9 +441,8 @@ def observe_pos(cosmo, pos, vel, box_center, box_rot, box_size, evol_shape, pain
         else:
             ap = ap or {}
             apkw.update(ap_mode=_lib.AP_PARAM, alpha_iso=float(ap.get("alpha_iso", 1.0)), alpha_ap=float(ap.get("alpha_ap", 1.0)))
-        plan.call("mcpm_observe_pos_ap_f32", nbody._ptr(p), nbody._ptr(v), nbody._ptr(dv), n, mode, geom, flags, nbody._ptr(tables), nchi,
-                  ngrow, apkw["ap_mode"], apkw["alpha_iso"], apkw["alpha_ap"], nbody._ptr(apkw["ap_tables"]), apkw["nap"], apkw["nfid"],
-                  nbody._ptr(out))
+        plan.call("mcpm_observe_pos_ap_f32", p, v, dv, n, mode, geom, flags, tables, nchi, ngrow, apkw["ap_mode"], apkw["alpha_iso"],
+                  apkw["alpha_ap"], apkw["ap_tables"], apkw["nap"], apkw["nfid"], out)
     res = nbody.LatticePos(out, paint_shape, pos.ptcl_shape) if isinstance(pos, nbody.LatticePos) else out
     if return_ctx:
         return res, ObsCtx(plan=plan, p=p, v=v, dv=dv, n=n, mode=mode, geom=geom, flags=flags, tables=tables, nchi=nchi, ngrow=ngrow, **apkw)
@@ -489,8 +454,6 @@ def observe_pos_vjp(ctx, out_bar):
     gf_bar is the cotangent of the scalar a2g(a_obs) a2f(a_obs) (0.0 on the light cone).  With Alcock-Paczynski (ap_auto not None)
     a fifth output follows: {'alpha_iso': ..., 'alpha_ap': ...}, the cotangents of the two parameters (0 for ap_auto=True, whose
     cosmology dependence is a table cotangent: `observe_pos_tables_vjp`; alpha_ap's is 0 on a curved sky)."""
-    import torch
-    from . import nbody, _lib
     n, dev = ctx.n, ctx.p.device
     ob = nbody._f32(out_bar, (n, 3))
     pb = torch.empty((n, 3), dtype=torch.float32, device=dev)
@@ -498,13 +461,12 @@ def observe_pos_vjp(ctx, out_bar):
     db = torch.empty((n, 3), dtype=torch.float32, device=dev) if ctx.dv is not None else None
     if getattr(ctx, "ap_mode", _lib.AP_NONE) == _lib.AP_NONE:
         gfb = torch.zeros(1, dtype=torch.float64, device=dev)
-        ctx.plan.call("mcpm_observe_pos_vjp_f32", nbody._ptr(ctx.p), nbody._ptr(ctx.v), nbody._ptr(ctx.dv), n, ctx.mode, ctx.geom, ctx.flags,
-                      nbody._ptr(ctx.tables), ctx.nchi, ctx.ngrow, nbody._ptr(ob), nbody._ptr(pb), nbody._ptr(vb), nbody._ptr(db), nbody._ptr(gfb))
+        ctx.plan.call("mcpm_observe_pos_vjp_f32", ctx.p, ctx.v, ctx.dv, n, ctx.mode, ctx.geom, ctx.flags, ctx.tables, ctx.nchi, ctx.ngrow, ob, pb, vb,
+                      db, gfb)
         return pb, vb, db, float(gfb.item())
     sc = torch.zeros(3, dtype=torch.float64, device=dev)      # gf_bar, alpha_iso_bar, alpha_ap_bar
-    ctx.plan.call("mcpm_observe_pos_ap_vjp_f32", nbody._ptr(ctx.p), nbody._ptr(ctx.v), nbody._ptr(ctx.dv), n, ctx.mode, ctx.geom, ctx.flags,
-                  nbody._ptr(ctx.tables), ctx.nchi, ctx.ngrow, *_ap_args(ctx), nbody._ptr(ob), nbody._ptr(pb), nbody._ptr(vb), nbody._ptr(db),
-                  nbody._ptr(sc), sc.data_ptr() + 8)
+    ctx.plan.call("mcpm_observe_pos_ap_vjp_f32", ctx.p, ctx.v, ctx.dv, n, ctx.mode, ctx.geom, ctx.flags, ctx.tables, ctx.nchi, ctx.ngrow,
+                  *_ap_args(ctx), ob, pb, vb, db, sc, sc[1:])
     s = sc.cpu().numpy()
     return pb, vb, db, float(s[0]), {"alpha_iso": float(s[1]), "alpha_ap": float(s[2])}
 
@@ -513,19 +475,17 @@ def observe_pos_tables_vjp(ctx, out_bar):
     """Cotangents of the look-up tables inside observe_pos (device float64): chi_bar[nchi], g_bar[ngrow], f_bar[ngrow] on the light
     cone (the growth look-ups at the evolved positions plus, with ap_auto=True, the chi2a(cosmo, r') of the Alcock-Paczynski
     step); at fixed a_obs with ap_auto=True chi_bar alone.  mcpm_observe_pos_tables_vjp_f32 / mcpm_observe_pos_ap_tables_vjp_f32."""
-    import torch
-    from . import nbody, _lib
     n, dev = ctx.n, ctx.p.device
     ob = nbody._f32(out_bar, (n, 3))
     if getattr(ctx, "ap_mode", _lib.AP_NONE) == _lib.AP_NONE:
         tb = torch.empty(ctx.nchi + 2 * ctx.ngrow, dtype=torch.float64, device=dev)
-        ctx.plan.call("mcpm_observe_pos_tables_vjp_f32", nbody._ptr(ctx.p), nbody._ptr(ctx.v), nbody._ptr(ctx.dv), n, ctx.mode, ctx.geom,
-                      ctx.flags, nbody._ptr(ctx.tables), ctx.nchi, ctx.ngrow, nbody._ptr(ob), nbody._ptr(tb))
+        ctx.plan.call("mcpm_observe_pos_tables_vjp_f32", ctx.p, ctx.v, ctx.dv, n, ctx.mode, ctx.geom, ctx.flags, ctx.tables, ctx.nchi, ctx.ngrow, ob,
+                      tb)
         return tb
     lc = bool(ctx.flags & 2)
     tb = torch.empty((ctx.nchi + 2 * ctx.ngrow) if lc else ctx.nap, dtype=torch.float64, device=dev)
-    ctx.plan.call("mcpm_observe_pos_ap_tables_vjp_f32", nbody._ptr(ctx.p), nbody._ptr(ctx.v), nbody._ptr(ctx.dv), n, ctx.mode, ctx.geom,
-                  ctx.flags, nbody._ptr(ctx.tables), ctx.nchi, ctx.ngrow, *_ap_args(ctx), nbody._ptr(ob), nbody._ptr(tb))
+    ctx.plan.call("mcpm_observe_pos_ap_tables_vjp_f32", ctx.p, ctx.v, ctx.dv, n, ctx.mode, ctx.geom, ctx.flags, ctx.tables, ctx.nchi, ctx.ngrow,
+                  *_ap_args(ctx), ob, tb)
     return tb
 
 
@@ -535,8 +495,6 @@ def samp2base_mesh(init: dict, precond, transfer, inv=False, temp=1.) -> dict:
     """Transform the sample mesh into the base mesh, i.e. the initial wavevector coefficients (bricks.py:290-320):
     'real': rfftn(mesh) * transfer; 'fourier' / 'kaiser': rg2cgh(mesh) * transfer; and the inverse.  `transfer` is the
     model's (fiducial, fixed) real k-space array; the permutation runs in mcpm_rg2cgh_f32 / mcpm_cgh2rg_f32."""
-    import torch
-    from . import nbody, utils
     assert len(init) <= 1, "init dict should only have one or zero key"
     for in_name, mesh in init.items():
         out_name = in_name + '_' if inv else in_name[:-1]
@@ -555,8 +513,6 @@ def samp2base_mesh(init: dict, precond, transfer, inv=False, temp=1.) -> dict:
 def samp2base_mesh_vjp(base_bar, precond, transfer, temp=1.):
     """VJP of samp2base_mesh (forward direction): cotangent of the base mesh (complex, real-pair convention) -> cotangent
     of the real sample mesh."""
-    import torch
-    from . import nbody, utils
     tr = torch.as_tensor(np.asarray(transfer, dtype=np.float32) * temp ** .5, device=nbody._device())
     kb = nbody._c64(base_bar) * tr
     return nbody.rfftn_vjp(kb) if precond == 'real' else utils.rg2cgh_vjp(kb)

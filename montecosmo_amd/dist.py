@@ -24,15 +24,18 @@ from __future__ import annotations
 
 import ctypes as C
 import math
+import os
 
 import numpy as np
 import torch
 
-from . import nbody
-from ._lib import lib, check, POS_LATTICE
+from . import nbody, _lib
+from ._lib import lib, check, Ctx, McpmError, POS_LATTICE
 
 
 def _p(t):
+    """Unchecked pointer.  The four step generators (force_meshes[_vjp]_gen, step[_vjp]_gen) pass these and `_interior` / `_spec` offsets:
+    with tensors and slices there the Python-issued step took 0.447 ms of host time against 0.368 .. 0.400 (profiles/call_marshal_ab.txt)."""
     return C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
 
 
@@ -386,23 +389,21 @@ class SlabPM(HaloMixin, PlaneHalo):
         self.shape, self.P, self.rank = (nx, ny, nz), P, r
         self.nxl, self.nyl, self.G = nx // P, ny // P, int(ghost)
         self.nxe = self.nxl + 2 * self.G
-        self.device = device if device is not None else nbody._device()
+        dev = nbody._device() if device is None else torch.device(device)      # indexed, as tensors report theirs
+        self.device = dev if dev.index is not None else torch.device(dev.type, torch.cuda.current_device())
         self.stream = torch.cuda.current_stream(self.device)
-        h = C.c_void_p()
-        check(lib.mcpm_plan_create_slab(nx, ny, nz, P, r, self.G, C.c_void_p(self.stream.cuda_stream), C.byref(h)), None,
-              "mcpm_plan_create_slab")
-        self.h = h
+        self.h = C.c_void_p()
+        _lib.call("mcpm_plan_create_slab", nx, ny, nz, P, r, self.G, C.c_void_p(self.stream.cuda_stream), C.byref(self.h))
         if chunks is None:
-            import os
             chunks = int(os.environ.get("MCPM_SLAB_CHUNKS", "1" if P == 1 else ("4" if self.nxl >= 128 else "2")))
         while chunks > 1 and (self.nxl % chunks or self.nxl // chunks < 2 * self.G):    # a chunk holds at most one edge
             chunks //= 2
         self.chunks = max(1, int(chunks))
-        check(lib.mcpm_slab_set_chunks(h, self.chunks), h, "mcpm_slab_set_chunks")
+        self.call("mcpm_slab_set_chunks", self.chunks)
         self.Nl = self.nxl * ny * nz                   # local particles
         self.Me = self.nxe * ny * nz                   # ghost-extended local mesh
         self.plane = ny * nz
-        ss = self.ss = lib.mcpm_slab_spec_elems(h)
+        ss = self.ss = self.call("mcpm_slab_spec_elems")
         f32 = dict(dtype=torch.float32, device=self.device)
         c64 = dict(dtype=torch.complex64, device=self.device)
         self.rho = torch.zeros((self.nxe, ny, nz), **f32)
@@ -414,7 +415,7 @@ class SlabPM(HaloMixin, PlaneHalo):
         # torch version counter; kick-drift generation of this plan).  Anything else falls back to a reduction pass.
         self._dmax_token = None
         self._kd_gen = 0
-        check(lib.mcpm_plan_track_dmax(h, C.c_void_p(self.dmax.data_ptr())), h, "mcpm_plan_track_dmax")
+        self.call("mcpm_plan_track_dmax", self.dmax)
         self.s1a, self.s1b = torch.empty(ss, **c64), torch.empty(ss, **c64)
         self.s6a, self.s6b = torch.empty(6 * ss, **c64), torch.empty(6 * ss, **c64)     # lpt: 6 Hessian spectra
         self.s3a, self.s3b = self.s6a[:3 * ss], self.s6b[:3 * ss]
@@ -424,7 +425,6 @@ class SlabPM(HaloMixin, PlaneHalo):
         # `native` (default: MCPM_SLAB_NATIVE, else on): step / step_vjp are ONE library call each (csrc/slab.hip issues the
         # kernels AND the exchanges, on a plan-owned RCCL communicator when the torch communicator is RCCL); off: the
         # exchanges are issued from here through torch.distributed, kernel by kernel (the reference both are tested against).
-        import os
         asked = native is not None or "MCPM_SLAB_NATIVE" in os.environ
         if native is None:
             # Default: on wherever the library's transport has been exercised (one rank; several ranks through host callbacks),
@@ -444,6 +444,7 @@ class SlabPM(HaloMixin, PlaneHalo):
         err = None
         try:
             self._init_native_transport()
+            # (looked up on this module's `lib` at the call, so that a test can stand a failing transport in for it)
             check(lib.mcpm_slab_comm_selftest(self.h), self.h, "mcpm_slab_comm_selftest")
         except Exception as e:              # MCPM_E_RCCL, a missing librccl, a failing callback
             if self._host_ops is not None and self._host_ops.error is not None:
@@ -461,14 +462,14 @@ class SlabPM(HaloMixin, PlaneHalo):
         self.native_fallback = repr(err) if err is not None else "another rank's transport failed"
 
     def _init_native_transport(self):
-        h, comm = self.h, self.comm
+        comm = self.comm
         self._halo = torch.empty(6 * self.G * self.plane, dtype=torch.float32, device=self.device)
         self._host_ops = None
         if isinstance(comm, LocalComm):
-            check(lib.mcpm_slab_comm_init_local(h), h, "mcpm_slab_comm_init_local")
+            self.call("mcpm_slab_comm_init_local")
         elif getattr(comm, "stage", False):                    # gloo: the host carries the bytes (tests)
             self._host_ops = HostStagedOps(comm)
-            check(lib.mcpm_slab_comm_init_ops(h, C.byref(self._host_ops.struct)), h, "mcpm_slab_comm_init_ops")
+            self.call("mcpm_slab_comm_init_ops", C.byref(self._host_ops.struct))
         else:                                                   # RCCL: the plan gets its own communicator
             # Ordering against torch's communicator: every torch collective this class issues is waited for by the CURRENT
             # stream before anything else is enqueued on it (all_reduce_sum is stream-synchronous; all_reduce_max_async
@@ -490,9 +491,8 @@ class SlabPM(HaloMixin, PlaneHalo):
             idt = dev_id.cpu()
             if int(idt[128]) != 1:
                 raise RuntimeError("mcpm_slab_rccl_unique_id failed on rank 0 (librccl missing or unusable: MCPM_E_RCCL)")
-            check(lib.mcpm_slab_comm_init_rccl(h, C.c_void_p(idt.data_ptr())), h, "mcpm_slab_comm_init_rccl")
-        check(lib.mcpm_slab_bind_workspace(h, _p(self.rho), _p(self.f3), _p(self.s1a), _p(self.s1b), _p(self.s6a), _p(self.s6b),
-                                           _p(self.Fb), _p(self._halo)), h, "mcpm_slab_bind_workspace")
+            self.call("mcpm_slab_comm_init_rccl", C.c_void_p(idt.data_ptr()))
+        self.call("mcpm_slab_bind_workspace", self.rho, self.f3, self.s1a, self.s1b, self.s6a, self.s6b, self.Fb, self._halo)
 
     def __del__(self):
         h, self.h = getattr(self, "h", None), None
@@ -506,14 +506,16 @@ class SlabPM(HaloMixin, PlaneHalo):
         if name.startswith("mcpm_kick_drift"):     # every such call re-zeroes and refills the plan's dmax slots
             self._kd_gen += 1
             self._dmax_token = None
-        check(getattr(lib, name)(self.h, *args), self.h, name)
+        return _lib.call(name, self.h, *args, device=self.device)
 
     def _native_call(self, name, *args):
-        rc = getattr(lib, name)(self.h, *args)
-        if rc != 0 and self._host_ops is not None and self._host_ops.error is not None:
+        try:
+            _lib.call(name, self.h, *args, device=self.device)
+        except McpmError:      # a transport callback that raised is the cause: hand its exception over instead of the code
+            if self._host_ops is None or self._host_ops.error is None:
+                raise
             err, self._host_ops.error = self._host_ops.error, None
-            raise err
-        check(rc, self.h, name)
+            raise err from None
 
     def out_of_ghost(self):
         """Cumulative count of deposits that fell beyond this rank's ghost planes (must stay 0)."""
@@ -521,12 +523,9 @@ class SlabPM(HaloMixin, PlaneHalo):
         self.call("mcpm_plan_slab_oob", C.byref(n))
         return n.value
 
-    def _interior(self, ext, c=None):
+    def _interior(self, ext, c=None, ncomp=1):
         base = ext if c is None else ext[c]
-        return C.c_void_p(base.data_ptr() + 4 * self.G * self.plane)
-
-    def _interior_il(self, ext_il):
-        return C.c_void_p(ext_il.data_ptr() + 4 * 3 * self.G * self.plane)
+        return C.c_void_p(base.data_ptr() + 4 * ncomp * self.G * self.plane)
 
     def force_mesh_il(self):
         """Scratch interleaved force mesh (nxe, ny, nz, 3)."""
@@ -642,7 +641,7 @@ class SlabPM(HaloMixin, PlaneHalo):
         def zinv(win):
             self._win(win)
             if il:
-                self.call("mcpm_slab_zinv3_il", _p(dst), self._interior_il(f3_ext))
+                self.call("mcpm_slab_zinv3_il", _p(dst), self._interior(f3_ext, ncomp=3))
             else:
                 for c in range(3):
                     self.call("mcpm_slab_zinv", self._spec(dst, c), self._interior(f3_ext[c]), self.Me, 1)
@@ -749,25 +748,25 @@ class SlabPM(HaloMixin, PlaneHalo):
     # ---- lpt on slabs (nbody.py:634-667 at the lattice, read_order = 1) -------------------------------------
     def spec_to_meshes(self, spec_full, out_ext, nc):
         """Replicated plain half-spectrum -> nc = 3 force meshes or nc = 6 Hessian meshes (interiors of out_ext[c])."""
-        ss = self.ss
-        self.call("mcpm_slab_xfused", _p(spec_full), _p(self.s6a), 2 if nc == 3 else 3)
-        a2a = [self._a2a_all(self.s6b[c * ss:(c + 1) * ss], self.s6a[c * ss:(c + 1) * ss]) for c in range(nc)]
+        s6a, s6b = self.s6a.view(6, self.ss), self.s6b.view(6, self.ss)
+        self.call("mcpm_slab_xfused", spec_full, self.s6a, 2 if nc == 3 else 3)
+        a2a = [self._a2a_all(s6b[c], s6a[c]) for c in range(nc)]
         for c in range(nc):
             a2a[c].wait()
-            self.call("mcpm_slab_ycol", self._spec(self.s6b, c), self._spec(self.s6a, c), 1, +1, 1, 0)
-            self.call("mcpm_slab_zinv", self._spec(self.s6a, c), self._interior(out_ext, c), self.Me, 1)
+            self.call("mcpm_slab_ycol", s6b[c], s6a[c], 1, +1, 1, 0)
+            self.call("mcpm_slab_zinv", s6a[c], out_ext[c, self.G:], self.Me, 1)
 
     def meshes_to_spec_bar(self, meshes_ext, spec_bar_full, nc):
         """Adjoint of spec_to_meshes: writes (nc = 3) or accumulates (nc = 6) this rank's y rows of spec_bar_full."""
-        ss = self.ss
+        s6a, s6b = self.s6a.view(6, self.ss), self.s6b.view(6, self.ss)
         a2a = []
         for c in range(nc):
-            self.call("mcpm_slab_zfwd", self._interior(meshes_ext, c), self.Me, self._spec(self.s6a, c), 1)
-            self.call("mcpm_slab_ycol", self._spec(self.s6a, c), self._spec(self.s6b, c), 1, -1, 0, 1)
-            a2a.append(self._a2a_all(self.s6a[c * ss:(c + 1) * ss], self.s6b[c * ss:(c + 1) * ss]))
+            self.call("mcpm_slab_zfwd", meshes_ext[c, self.G:], self.Me, s6a[c], 1)
+            self.call("mcpm_slab_ycol", s6a[c], s6b[c], 1, -1, 0, 1)
+            a2a.append(self._a2a_all(s6a[c], s6b[c]))
         for h in a2a:
             h.wait()
-        self.call("mcpm_slab_xfused", _p(self.s6a), _p(spec_bar_full), 4 if nc == 3 else 5)
+        self.call("mcpm_slab_xfused", self.s6a, spec_bar_full, 4 if nc == 3 else 5)
 
     def _h6(self):
         if self.h6 is None:
@@ -777,13 +776,13 @@ class SlabPM(HaloMixin, PlaneHalo):
     def lpt(self, spec, lpt_order, g, g2, dg2dg, dpos, vel):
         """dpos, vel (Nl,3) of this rank's particles from the replicated half-spectrum `spec`."""
         self.spec_to_meshes(spec, self.f3, 3)
-        self.call("mcpm_lpt_accum_f32", _p(self.f3), float(g), 1.0, 1, _p(dpos), _p(vel))
+        self.call("mcpm_lpt_accum_f32", self.f3, float(g), 1.0, 1, dpos, vel)
         if lpt_order == 2:
             h6 = self._h6()
             self.spec_to_meshes(spec, h6, 6)
-            self.call("mcpm_hessian_combine_f32", _p(h6), _p(self.rho))
+            self.call("mcpm_hessian_combine_f32", h6, self.rho)
             self.force_meshes(self.rho, self.f3, fill_ghosts=False)
-            self.call("mcpm_lpt_accum_f32", _p(self.f3), -float(g2), -float(dg2dg), 0, _p(dpos), _p(vel))
+            self.call("mcpm_lpt_accum_f32", self.f3, -float(g2), -float(dg2dg), 0, dpos, vel)
 
     def lpt_vjp(self, spec, lpt_order, g, g2, dg2dg, xb, vb):
         """Cotangents (xb, vb) of this rank's (dpos, vel) -> (init_mesh_bar, [g_bar, g2_bar, dg2dg_bar]), both
@@ -791,18 +790,18 @@ class SlabPM(HaloMixin, PlaneHalo):
         out = torch.zeros(tuple(spec.shape), dtype=torch.complex64, device=spec.device)
         sbar = torch.zeros(3, dtype=torch.float64, device=spec.device)
         self.spec_to_meshes(spec, self.f3, 3)
-        self.call("mcpm_lattice_dot_f32", _p(self.f3), _p(xb), None, _p(sbar))
-        self.call("mcpm_lattice_scatter_f32", _p(xb), _p(vb), float(g), 1.0, _p(self.f3))
+        self.call("mcpm_lattice_dot_f32", self.f3, xb, None, sbar)
+        self.call("mcpm_lattice_scatter_f32", xb, vb, float(g), 1.0, self.f3)
         self.meshes_to_spec_bar(self.f3, out, 3)
         if lpt_order == 2:
             h6 = self._h6()
             self.spec_to_meshes(spec, h6, 6)
-            self.call("mcpm_hessian_combine_f32", _p(h6), _p(self.rho))
+            self.call("mcpm_hessian_combine_f32", h6, self.rho)
             self.force_meshes(self.rho, self.f3, fill_ghosts=False)
-            self.call("mcpm_lattice_dot_f32", _p(self.f3), _p(xb), _p(vb), C.c_void_p(sbar.data_ptr() + 8))
-            self.call("mcpm_lattice_scatter_f32", _p(xb), _p(vb), -float(g2), -float(dg2dg), _p(self.f3))
+            self.call("mcpm_lattice_dot_f32", self.f3, xb, vb, sbar[1:])
+            self.call("mcpm_lattice_scatter_f32", xb, vb, -float(g2), -float(dg2dg), self.f3)
             self.force_meshes_vjp(self.f3, self.rho)
-            self.call("mcpm_hessian_combine_vjp_f32", _p(h6), _p(self.rho), _p(h6))
+            self.call("mcpm_hessian_combine_vjp_f32", h6, self.rho, h6)
             self.meshes_to_spec_bar(h6, out, 6)
         out = self.comm.all_reduce_sum(out)
         sb = self.comm.all_reduce_sum(sbar).cpu().numpy()
@@ -947,9 +946,7 @@ class SlabPM(HaloMixin, PlaneHalo):
                   float(tau), paint_order, _p(xb), _p(vb), abar_ptr, bbar_ptr, float(dtau_ddg), dgbar_ptr)
 
 
-class SlabCtx:
-    def __init__(self, **kw):
-        self.__dict__.update(kw)
+SlabCtx = Ctx
 
 
 def nbody_bf_slab(cosmo, init_mesh, a0=0., a1=1., n_steps=5, paint_order=2, lpt_order=2, comm=None, ghost=16,
@@ -993,8 +990,7 @@ def nbody_bf_slab_vjp(ctx, disp_bar, vel_bar):
     for i in reversed(range(K)):
         tau = ctx.dg / 2 if i == K - 1 else ctx.dg
         pm.step_vjp(ctx.states[i, 0], ctx.states[i, 1], ctx.f3s[i], ctx.alphas[i], ctx.betas[i], tau, xb, vb,
-                    C.c_void_p(sbar.data_ptr() + 8 * i), C.c_void_p(sbar.data_ptr() + 8 * (K + i)),
-                    0.5 if i == K - 1 else 1.0, C.c_void_p(sbar.data_ptr() + 8 * 2 * K), ctx.paint_order, depth=ctx.depths[i],
+                    sbar[i:], sbar[K + i:], 0.5 if i == K - 1 else 1.0, sbar[2 * K:], ctx.paint_order, depth=ctx.depths[i],
                     next_beta_tau=(ctx.betas[i - 1], ctx.dg) if i > 0 else None)
     sbar[2 * K] += 0.5 * (xb.double() * ctx.states[0, 1].double()).sum()    # initial half drift x'_0 = x_0 + v_0 dg/2
     vb += xb * (ctx.dg / 2)

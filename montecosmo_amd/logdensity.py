@@ -37,13 +37,12 @@ particle operators through their `*_vjp` twins -- no autodiff framework.
 """
 from __future__ import annotations
 
+import ctypes as C
 import math
 from types import SimpleNamespace
 
 import numpy as np
 import torch
-
-import ctypes as C
 
 from . import nbody, bricks, _lib
 from .utils import r2chshape, chreshape, chreshape_vjp, rg2cgh, rg2cgh_vjp, cgh2rg
@@ -408,8 +407,8 @@ class FieldLevelLogDensity:
             Y = nbody.rfftn(cm)
             Yb = torch.empty_like(Y)
             box, los = [float(v) for v in self.fwd.box_size], [float(v) for v in self.los_fid]
-            plan.call("mcpm_lik_fourier_f32", nbody._ptr(Y), nbody._ptr(self.obs_rg), *box, *los, float(selec), float(base["s_e"]),
-                      float(base["s_k2e"]), float(base["s_kmu2e"]), nbody._ptr(Yb), nbody._ptr(sums))
+            plan.call("mcpm_lik_fourier_f32", Y, self.obs_rg, *box, *los, float(selec), float(base["s_e"]), float(base["s_k2e"]),
+                      float(base["s_kmu2e"]), Yb, sums)
             keys = ("s_e", "s_k2e", "s_kmu2e")
         else:
             if mesh_sel:      # the selection made safe outside the mask
@@ -418,9 +417,8 @@ class FieldLevelLogDensity:
             cm_bar = torch.empty_like(cm)
             qb = torch.empty_like(cm) if (want_sqsel and mesh_sel) else None
             st = [float(base[k]) if shash else 0.0 for k in self.STOCH]
-            plan.call("mcpm_lik_real_f32", _lib.LIK_SHASH if shash else _lib.LIK_POISSON, C.c_int64(cm.numel()), nbody._ptr(self.count_obs),
-                      nbody._ptr(cm), nbody._ptr(selec if mesh_sel else None), 1.0 if mesh_sel else float(selec), nbody._ptr(self.mask), *st,
-                      nbody._ptr(cm_bar), nbody._ptr(qb), nbody._ptr(sums))
+            plan.call("mcpm_lik_real_f32", _lib.LIK_SHASH if shash else _lib.LIK_POISSON, C.c_int64(cm.numel()), self.count_obs, cm,
+                      selec if mesh_sel else None, 1.0 if mesh_sel else float(selec), self.mask, *st, cm_bar, qb, sums)
             keys = self.STOCH if shash else ()
         v = sums.cpu().numpy()
         if not need_grad:

@@ -17,8 +17,7 @@ import ctypes as C
 import numpy as np
 import torch
 
-from . import nbody
-from ._lib import lib, check
+from . import nbody, _lib
 from .utils import safe_div, ch2rshape
 
 MAX_EDGES = 4096               # MCPM_SPECTRUM_MAX_EDGES
@@ -106,7 +105,7 @@ def _to_spec(t, real, shape, dev):
         return t.to(device=dev, dtype=torch.complex64).contiguous()
     x = t.to(device=dev, dtype=torch.float32).contiguous()
     out = torch.empty((x.shape[0],) + tuple(nbody.r2chshape(shape)), dtype=torch.complex64, device=dev)
-    nbody.get_plan(shape).call("mcpm_fft_r2c", nbody._ptr(x), nbody._ptr(out), int(x.shape[0]))
+    nbody.get_plan(shape).call("mcpm_fft_r2c", x, out, int(x.shape[0]))
     return out
 
 
@@ -147,7 +146,7 @@ def _bin_sums(mesh0, mesh1, box_size, box_center, ells, kedges, include_corners,
     if n_bins < 1:      # fewer than two edges: no bin, as in the reference
         return edges, batched, out, np.asarray(shape), box_size, ell_list, two
     ws1 = C.c_int64()
-    check(lib.mcpm_spectrum_workspace(nx, ny, nz, len(edges), n_ells, int(two), 1, C.byref(ws1)), None, "mcpm_spectrum_workspace")
+    _lib.call("mcpm_spectrum_workspace", nx, ny, nz, len(edges), n_ells, int(two), 1, C.byref(ws1))
     mh = nx * ny * (nz // 2 + 1)
     per_row = ws1.value + (16 * mh if two else 8 * mh) + 8 * nx * ny * nz
     chunk = int(max(1, min(batch, CHUNK_BYTES // per_row)))
@@ -161,14 +160,11 @@ def _bin_sums(mesh0, mesh1, box_size, box_center, ells, kedges, include_corners,
         s0 = _to_spec(t0[lo:hi], real0, shape, dev) if bat0 else s0_fixed
         s1 = (_to_spec(t1[lo:hi], real1, shape, dev) if bat1 else s1_fixed) if two else None
         ws = C.c_int64()
-        check(lib.mcpm_spectrum_workspace(nx, ny, nz, len(edges), n_ells, int(two), hi - lo, C.byref(ws)), None,
-              "mcpm_spectrum_workspace")
+        _lib.call("mcpm_spectrum_workspace", nx, ny, nz, len(edges), n_ells, int(two), hi - lo, C.byref(ws))
         work = torch.empty(ws.value, dtype=torch.uint8, device=dev)
         res = torch.empty((hi - lo, n_acc, n_bins), dtype=torch.float64, device=dev)
-        rc = lib.mcpm_spectrum_bins_c64(stream, nx, ny, nz, nbody._ptr(s0), mh if bat0 else 0, nbody._ptr(s1),
-                                        mh if bat1 else 0, hi - lo, _f64p(ktab), _f64p(dc0), _f64p(dc1), _f64p(edges), len(edges),
-                                        _f64p(los_c), ells_c, n_ells, nbody._ptr(work), ws.value, nbody._ptr(res))
-        check(rc, None, "mcpm_spectrum_bins_c64")
+        _lib.call("mcpm_spectrum_bins_c64", stream, nx, ny, nz, s0, mh if bat0 else 0, s1, mh if bat1 else 0, hi - lo, ktab, dc0, dc1, edges,
+                  len(edges), los_c, ells_c, n_ells, work, ws.value, res)
         out[lo:hi] = res.cpu().numpy()
     return edges, batched, out, np.asarray(shape), box_size, ell_list, two
 

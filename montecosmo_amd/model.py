@@ -25,12 +25,8 @@ import numpy as np
 import torch
 
 from . import nbody, bricks, metrics
+from ._lib import Ctx as EvolveCtx
 from .utils import scale_shape, r2chshape, chreshape, chreshape_vjp
-
-
-class EvolveCtx:
-    def __init__(self, **kw):
-        self.__dict__.update(kw)
 
 
 class FieldLevelForward:
@@ -115,8 +111,7 @@ class FieldLevelForward:
         plan = nbody.get_plan(self.init_shape)
         out = torch.empty_like(spec)
         kp = self._kphys(self.init_shape)
-        plan.call("mcpm_power_mult_f32", nbody._ptr(spec), kp[0], kp[1], kp[2], float(cosmo.sigma8 if sigma8 is None else sigma8) ** 2, nbody._ptr(tab),
-                  nbody.C.c_void_p(tab.data_ptr() + 8 * nt), nt, nbody._ptr(out))
+        plan.call("mcpm_power_mult_f32", spec, kp[0], kp[1], kp[2], float(cosmo.sigma8 if sigma8 is None else sigma8) ** 2, tab, tab[nt:], nt, out)
         return out
 
     def los_cell(self):
@@ -160,8 +155,7 @@ class FieldLevelForward:
         """scale * safe_div(spec, t(|k|)) on the evolution mesh, t from `lin_kpow` as the reference's Kaiser model takes it."""
         tab, nt = bricks.png_table_dev(cosmo, self.lin_kpow, spec.device)
         out, kp = torch.empty_like(spec), self._kphys(self.evol_shape)
-        nbody.get_plan(self.evol_shape).call("mcpm_png_div_f32", nbody._ptr(spec), kp[0], kp[1], kp[2], nbody._ptr(tab), tab.data_ptr() + 8 * nt, nt,
-                                             float(scale), nbody._ptr(out))
+        nbody.get_plan(self.evol_shape).call("mcpm_png_div_f32", spec, kp[0], kp[1], kp[2], tab, tab[nt:], nt, float(scale), out)
         return out
 
     def _kaiser(self, cosmo, bias, white, evol_k, return_ctx, png=None):
@@ -432,8 +426,7 @@ class FieldLevelForward:
         gB = (nbody._f32(grads["bias_growth"]).reshape(-1) + nbody._f32(g["g"]).reshape(-1)).contiguous()
         g2B, dB = nbody._f32(g["g2"]).reshape(-1).contiguous(), nbody._f32(g["dg2dg"]).reshape(-1).contiguous()
         tbL = torch.empty(nchi + 4 * ng, dtype=torch.float64, device=dev)
-        plan.call("mcpm_lightcone_tables_vjp_f32", nbody._ptr(self._r0), n, nbody._ptr(tabs), nchi, ng, nbody._ptr(gB), nbody._ptr(g2B),
-                  nbody._ptr(dB), nbody._ptr(tbL))
+        plan.call("mcpm_lightcone_tables_vjp_f32", self._r0, n, tabs, nchi, ng, gB, g2B, dB, tbL)
         o = ctx.octx
         tbO = bricks.observe_pos_tables_vjp(o, grads["obs_bar"])      # with ap_auto=True the Alcock-Paczynski look-up arrives in its chi bar
         L, O = tbL.cpu().numpy(), tbO.cpu().numpy()

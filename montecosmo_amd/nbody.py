@@ -19,7 +19,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import lib, check, POS_ABSOLUTE, POS_LATTICE
+from ._lib import lib, Ctx, POS_ABSOLUTE, POS_LATTICE
 from .utils import safe_div, ch2rshape, r2chshape, scale_shape, chreshape, chreshape_vjp  # noqa: F401 (re-exported like the reference)
 
 __all__ = [
@@ -62,10 +62,8 @@ class Plan:
         self.Mh = mesh_shape[0] * mesh_shape[1] * (mesh_shape[2] // 2 + 1)
         self.N = int(np.prod(ptcl_shape))
         self.stream = torch.cuda.current_stream(self.device)
-        h = C.c_void_p()
-        rc = lib.mcpm_plan_create(*mesh_shape, *ptcl_shape, C.c_void_p(self.stream.cuda_stream), C.byref(h))
-        check(rc, None, "mcpm_plan_create")
-        self.h = h
+        self.h = C.c_void_p()
+        _lib.call("mcpm_plan_create", *mesh_shape, *ptcl_shape, C.c_void_p(self.stream.cuda_stream), C.byref(self.h))
 
     def __del__(self):
         h, self.h = getattr(self, "h", None), None
@@ -76,7 +74,7 @@ class Plan:
             pass
 
     def call(self, name, *args):
-        check(getattr(lib, name)(self.h, *args), self.h, name)
+        return _lib.call(name, self.h, *args, device=self.device)
 
     def last_bucketed(self):
         n = C.c_int64()
@@ -335,9 +333,9 @@ def paint(pos, shape: tuple, weights=1., order: int = 2, kernel_type='rectangula
     w, ws, wsc = _weights_args(weights, n)
     mesh = torch.empty(shape, dtype=torch.float32, device=p.device)
     if kernel_type == "kaiser_bessel":
-        plan.call("mcpm_paint_kb_f32", _ptr(p), n, mode, _ptr(w), ws, wsc, order, float(optim_kcut(oversamp)), _ptr(mesh), 0)
+        plan.call("mcpm_paint_kb_f32", p, n, mode, w, ws, wsc, order, float(optim_kcut(oversamp)), mesh, 0)
     else:
-        plan.call("mcpm_paint_f32", _ptr(p), n, mode, _ptr(w), ws, wsc, order, _ptr(mesh), 0)
+        plan.call("mcpm_paint_f32", p, n, mode, w, ws, wsc, order, mesh, 0)
     return mesh
 
 
@@ -348,9 +346,9 @@ def read(pos, mesh, order: int = 2, kernel_type='rectangular', oversamp=1.):
     plan, p, n, mode = _pos_args(pos, mesh.shape)
     out = torch.empty((n,), dtype=torch.float32, device=p.device)
     if kernel_type == "kaiser_bessel":
-        plan.call("mcpm_read_kb_f32", _ptr(p), n, mode, _ptr(mesh), order, float(optim_kcut(oversamp)), _ptr(out), None, 1, 0.0, None)
+        plan.call("mcpm_read_kb_f32", p, n, mode, mesh, order, float(optim_kcut(oversamp)), out, None, 1, 0.0, None)
     else:
-        plan.call("mcpm_read_f32", _ptr(p), n, mode, _ptr(mesh), 1, order, _ptr(out))
+        plan.call("mcpm_read_f32", p, n, mode, mesh, 1, order, out)
     return out
 
 
@@ -364,10 +362,9 @@ def paint_vjp(pos, shape, weights, mesh_bar, order: int = 2, kernel_type='rectan
     pos_bar = torch.empty((n, 3), dtype=torch.float32, device=p.device)
     w_bar = torch.empty((n,), dtype=torch.float32, device=p.device)
     if kernel_type == "kaiser_bessel":
-        plan.call("mcpm_read_kb_f32", _ptr(p), n, mode, _ptr(mb), order, float(optim_kcut(oversamp)), _ptr(w_bar), _ptr(w), ws, wsc,
-                  _ptr(pos_bar))
+        plan.call("mcpm_read_kb_f32", p, n, mode, mb, order, float(optim_kcut(oversamp)), w_bar, w, ws, wsc, pos_bar)
     else:
-        plan.call("mcpm_paint_vjp_f32", _ptr(p), n, mode, _ptr(w), ws, wsc, order, _ptr(mb), _ptr(pos_bar), _ptr(w_bar))
+        plan.call("mcpm_paint_vjp_f32", p, n, mode, w, ws, wsc, order, mb, pos_bar, w_bar)
     return pos_bar, (w_bar if w is not None else w_bar.double().sum())
 
 
@@ -381,11 +378,11 @@ def read_vjp(pos, mesh, out_bar, order: int = 2, kernel_type='rectangular', over
     mesh_bar = torch.empty(tuple(mesh.shape), dtype=torch.float32, device=p.device)
     if kernel_type == "kaiser_bessel":
         kc = float(optim_kcut(oversamp))
-        plan.call("mcpm_read_kb_f32", _ptr(p), n, mode, _ptr(mesh), order, kc, None, _ptr(ob), 1, 0.0, _ptr(pos_bar))
-        plan.call("mcpm_paint_kb_f32", _ptr(p), n, mode, _ptr(ob), 1, 0.0, order, kc, _ptr(mesh_bar), 0)
+        plan.call("mcpm_read_kb_f32", p, n, mode, mesh, order, kc, None, ob, 1, 0.0, pos_bar)
+        plan.call("mcpm_paint_kb_f32", p, n, mode, ob, 1, 0.0, order, kc, mesh_bar, 0)
     else:
-        plan.call("mcpm_read_vjp_pos_f32", _ptr(p), n, mode, _ptr(mesh), 1, order, _ptr(ob), _ptr(pos_bar))
-        plan.call("mcpm_paint_f32", _ptr(p), n, mode, _ptr(ob), 1, 0.0, order, _ptr(mesh_bar), 0)
+        plan.call("mcpm_read_vjp_pos_f32", p, n, mode, mesh, 1, order, ob, pos_bar)
+        plan.call("mcpm_paint_f32", p, n, mode, ob, 1, 0.0, order, mesh_bar, 0)
     return pos_bar, mesh_bar
 
 
@@ -394,7 +391,7 @@ def cell_index(pos, shape, order: int = 2):
     shape = tuple(int(s) for s in shape)
     plan, p, n, mode = _pos_args(pos, shape)
     idx = torch.empty((n, 3), dtype=torch.int16, device=p.device)
-    plan.call("mcpm_cell_index", _ptr(p), n, mode, order, _ptr(idx))
+    plan.call("mcpm_cell_index", p, n, mode, order, idx)
     return idx
 
 
@@ -404,7 +401,7 @@ def rfftn(mesh):
     mesh = _f32(mesh)
     plan = get_plan(mesh.shape)
     out = torch.empty(r2chshape(mesh.shape), dtype=torch.complex64, device=mesh.device)
-    plan.call("mcpm_fft_r2c", _ptr(mesh), _ptr(out), 1)
+    plan.call("mcpm_fft_r2c", mesh, out, 1)
     return out
 
 
@@ -413,7 +410,7 @@ def irfftn(spec):
     shape = ch2rshape(spec.shape)
     plan = get_plan(shape)
     out = torch.empty(shape, dtype=torch.float32, device=spec.device)
-    plan.call("mcpm_fft_c2r", _ptr(spec), _ptr(out), 1)
+    plan.call("mcpm_fft_c2r", spec, out, 1)
     return out / plan.M
 
 
@@ -426,7 +423,7 @@ def rfftn_vjp(spec_bar, overwrite=False):
     shape = ch2rshape(spec.shape)
     spec[..., 1:shape[-1] // 2] *= 0.5
     out = torch.empty(shape, dtype=torch.float32, device=spec.device)
-    get_plan(shape).call("mcpm_fft_c2r", _ptr(spec), _ptr(out), 1)
+    get_plan(shape).call("mcpm_fft_c2r", spec, out, 1)
     return out
 
 
@@ -461,11 +458,11 @@ def deconv_paint(mesh, order: int = 2, kernel_type='rectangular', oversamp=1.):
     if not t.is_complex():
         spec = rfftn(t)
         plan = get_plan(tuple(t.shape))
-        plan.call("mcpm_kspace_phase_f32", _ptr(spec), _ptr(spec), 1.0, 0.0, int(order), 0, 0, 0)
+        plan.call("mcpm_kspace_phase_f32", spec, spec, 1.0, 0.0, int(order), 0, 0, 0)
         return irfftn(spec)
     spec = _c64(t)
     out = torch.empty_like(spec)
-    get_plan(ch2rshape(spec.shape)).call("mcpm_kspace_phase_f32", _ptr(spec), _ptr(out), 1.0, 0.0, int(order), 0, 0, 0)
+    get_plan(ch2rshape(spec.shape)).call("mcpm_kspace_phase_f32", spec, out, 1.0, 0.0, int(order), 0, 0, 0)
     return out
 
 
@@ -481,8 +478,8 @@ def interlace(pos, shape: tuple, weights=1., paint_order: int = 2, interlace_ord
     for j in range(int(interlace_order)):
         s = j / interlace_order
         mesh = paint(_shift_pos(pos, s), shape, weights, paint_order, kernel_type=kernel_type, oversamp=paint_oversamp)
-        plan.call("mcpm_fft_r2c", _ptr(mesh), _ptr(tmp), 1)
-        plan.call("mcpm_kspace_phase_f32", _ptr(tmp), _ptr(out), 1.0 / interlace_order, float(s), 0, 0, 0, 1)
+        plan.call("mcpm_fft_r2c", mesh, tmp, 1)
+        plan.call("mcpm_kspace_phase_f32", tmp, out, 1.0 / interlace_order, float(s), 0, 0, 0, 1)
     return out
 
 
@@ -558,8 +555,8 @@ def nufft_vjp(pos, final_shape: tuple, weights, mesh_bar, paint_order: int = 2, 
     for j in range(int(interlace_order)):
         s = j / interlace_order
         # adjoint of (x phase / deconv / interlace_order) then of rfftn: C2R(conj(mult) * bar / multiplicity)
-        plan.call("mcpm_kspace_phase_f32", _ptr(mb), _ptr(tmp), jac / interlace_order, float(s), int(paint_order) if (paint_deconv and not kb) else 0, 1, 1, 0)
-        plan.call("mcpm_fft_c2r", _ptr(tmp), _ptr(real), 1)
+        plan.call("mcpm_kspace_phase_f32", mb, tmp, jac / interlace_order, float(s), int(paint_order) if (paint_deconv and not kb) else 0, 1, 1, 0)
+        plan.call("mcpm_fft_c2r", tmp, real, 1)
         pb, wb = paint_vjp(_shift_pos(ppos, s), shape, weights, real, paint_order, kernel_type=kernel_type, oversamp=paint_oversamp)
         pos_bar = pb if pos_bar is None else pos_bar + pb
         w_bar = wb if w_bar is None else w_bar + wb
@@ -578,13 +575,13 @@ def pm_forces(pos, mesh, read_order: int = 2, paint_deconv: bool = False, grad_f
         shape = tuple(int(s) for s in mesh)
         plan, p, n, mode = _pos_args(pos, shape)
         out = torch.empty((n, 3), dtype=torch.float32, device=p.device)
-        plan.call("mcpm_pm_forces_f32", _ptr(p), n, mode, read_order, int(bool(paint_deconv)), _fd(lap_fd), _fd(grad_fd), kc, _ptr(out))
+        plan.call("mcpm_pm_forces_f32", p, n, mode, read_order, int(bool(paint_deconv)), _fd(lap_fd), _fd(grad_fd), kc, out)
         return out
     spec = _c64(mesh)
     shape = ch2rshape(spec.shape)
     plan, p, n, mode = _pos_args(pos, shape)
     out = torch.empty((n, 3), dtype=torch.float32, device=p.device)
-    plan.call("mcpm_pm_forces_spec_f32", _ptr(spec), _ptr(p), n, mode, read_order, _fd(lap_fd), _fd(grad_fd), kc, _ptr(out))
+    plan.call("mcpm_pm_forces_spec_f32", spec, p, n, mode, read_order, _fd(lap_fd), _fd(grad_fd), kc, out)
     return out
 
 
@@ -601,7 +598,7 @@ def pm_forces_vjp(pos, mesh, forces_bar, read_order: int = 2):
     fb = _f32(forces_bar, (n, 3))
     pos_bar = torch.empty((n, 3), dtype=torch.float32, device=p.device)
     spec_bar = torch.empty(tuple(spec.shape), dtype=torch.complex64, device=p.device) if spec is not None else None
-    plan.call("mcpm_pm_forces_vjp_f32", _ptr(spec), _ptr(p), n, mode, int(read_order), _ptr(fb), _ptr(pos_bar), _ptr(spec_bar))
+    plan.call("mcpm_pm_forces_vjp_f32", spec, p, n, mode, int(read_order), fb, pos_bar, spec_bar)
     return pos_bar, spec_bar
 
 
@@ -611,7 +608,7 @@ def pm_forces2(pos, mesh, read_order: int = 2, grad_fd=np.inf, lap_fd=np.inf):
     shape = ch2rshape(spec.shape)
     plan, p, n, mode = _pos_args(pos, shape)
     out = torch.empty((n, 3), dtype=torch.float32, device=p.device)
-    plan.call("mcpm_pm_forces2_f32", _ptr(spec), _ptr(p), n, mode, read_order, _fd(lap_fd), _fd(grad_fd), _ptr(out))
+    plan.call("mcpm_pm_forces2_f32", spec, p, n, mode, read_order, _fd(lap_fd), _fd(grad_fd), out)
     return out
 
 
@@ -621,7 +618,7 @@ def interp_dev(x, xp, fp, scale=1.0):
     tab = torch.from_numpy(np.concatenate([np.asarray(xp, dtype=np.float64), np.asarray(fp, dtype=np.float64)])).to(x.device)
     out = torch.empty_like(x)
     nt = len(xp)
-    get_plan((8, 8, 8)).call("mcpm_interp_f32", _ptr(x), x.numel(), _ptr(tab), C.c_void_p(tab.data_ptr() + 8 * nt), nt, float(scale), _ptr(out))
+    get_plan((8, 8, 8)).call("mcpm_interp_f32", x, x.numel(), tab, tab[nt:], nt, float(scale), out)
     return out
 
 
@@ -656,12 +653,9 @@ def _growth_tab3(cosmo, a, n):
     return _f32(np.stack([a2g(cosmo, a), a2g2(cosmo, a), a2dg2dg(cosmo, a)], axis=-1))
 
 
-class LptCtx:
+class LptCtx(Ctx):
     """What `lpt(..., return_ctx=True)` keeps for `lpt_vjp(..., ctx=...)`: the force / Hessian meshes of the forward pass (`save`) and, on the
     light cone, the per-particle force arrays F1, F2 -- the adjoint then recomputes neither (2.9 of 22.5 ms per gradient at 256^3)."""
-
-    def __init__(self, **kw):
-        self.__dict__.update(kw)
 
 
 def lpt(cosmo, init_mesh, pos, a, lpt_order: int = 2, read_order: int = 2, grad_fd=np.inf, lap_fd=np.inf, return_ctx=False):
@@ -685,9 +679,9 @@ def lpt(cosmo, init_mesh, pos, a, lpt_order: int = 2, read_order: int = 2, grad_
 
         def run(g, g2, dg2dg, d_out, v_out):
             if keep:
-                plan.call("mcpm_lpt_save_f32", _ptr(spec), int(lpt_order), g, g2, dg2dg, _ptr(d_out), _ptr(v_out), _ptr(save))
+                plan.call("mcpm_lpt_save_f32", spec, int(lpt_order), g, g2, dg2dg, d_out, v_out, save)
             else:
-                plan.call("mcpm_lpt_f32", _ptr(spec), int(lpt_order), g, g2, dg2dg, _fd(lap_fd), _fd(grad_fd), _ptr(d_out), _ptr(v_out))
+                plan.call("mcpm_lpt_f32", spec, int(lpt_order), g, g2, dg2dg, _fd(lap_fd), _fd(grad_fd), d_out, v_out)
 
         if scalar_a:
             run(float(a2g(cosmo, a)), float(a2g2(cosmo, a)), float(a2dg2dg(cosmo, a)), dpos, vel)
@@ -696,7 +690,7 @@ def lpt(cosmo, init_mesh, pos, a, lpt_order: int = 2, read_order: int = 2, grad_
         run(0.0, -1.0, 0.0, F2, F1)
         gt = _growth_tab3(cosmo, a, n)
         dpos, vel = torch.empty_like(F1), torch.empty_like(F1)
-        plan.call("mcpm_lpt_combine_f32", _ptr(F1), _ptr(F2) if lpt_order == 2 else None, _ptr(gt), n, _ptr(dpos), _ptr(vel))
+        plan.call("mcpm_lpt_combine_f32", F1, F2 if lpt_order == 2 else None, gt, n, dpos, vel)
         return ((dpos, vel), LptCtx(save=save, F1=F1, F2=F2)) if return_ctx else (dpos, vel)
     force1 = pm_forces(pos, init_mesh, read_order, grad_fd=grad_fd, lap_fd=lap_fd)
     force2 = pm_forces2(pos, init_mesh, read_order, grad_fd=grad_fd, lap_fd=lap_fd) if lpt_order == 2 else None
@@ -710,7 +704,7 @@ def lpt(cosmo, init_mesh, pos, a, lpt_order: int = 2, read_order: int = 2, grad_
     gt = _growth_tab3(cosmo, a, n)
     dpos, vel = torch.empty_like(force1), torch.empty_like(force1)
     plan = get_plan(ch2rshape(init_mesh.shape), pos.ptcl_shape if isinstance(pos, LatticePos) else None)
-    plan.call("mcpm_lpt_combine_f32", _ptr(force1), _ptr(force2), _ptr(gt), n, _ptr(dpos), _ptr(vel))
+    plan.call("mcpm_lpt_combine_f32", force1, force2, gt, n, dpos, vel)
     return dpos, vel
 
 
@@ -731,9 +725,7 @@ def _growth_cache(cosmo, log10_amin=growth_log10_amin, steps=growth_steps):
     if key not in cosmo._workspace:
         names = ["a", "g", "f", "h", "g2", "f2", "h2"]
         arrs = [np.zeros(steps) for _ in names]
-        rc = lib.mcpm_growth_table(*_cosmo_params(cosmo), float(log10_amin), int(steps),
-                                   *[x.ctypes.data_as(C.POINTER(C.c_double)) for x in arrs])
-        check(rc, None, "mcpm_growth_table")
+        _lib.call("mcpm_growth_table", *_cosmo_params(cosmo), float(log10_amin), int(steps), *arrs)
         cosmo._workspace[key] = dict(zip(names, arrs))
     return cosmo._workspace[key]
 
@@ -796,9 +788,7 @@ def _dist_cache(cosmo, log10_amin=dist_log10_amin, steps=dist_steps):
     key = "background.radial_comoving_distance"
     if key not in cosmo._workspace:
         a, chi = np.zeros(steps), np.zeros(steps)
-        rc = lib.mcpm_distance_table(*_cosmo_params(cosmo), float(log10_amin), int(steps),
-                                     a.ctypes.data_as(C.POINTER(C.c_double)), chi.ctypes.data_as(C.POINTER(C.c_double)))
-        check(rc, None, "mcpm_distance_table")
+        _lib.call("mcpm_distance_table", *_cosmo_params(cosmo), float(log10_amin), int(steps), a, chi)
         cosmo._workspace[key] = {"a": a, "chi": chi}
     return cosmo._workspace[key]
 
@@ -878,11 +868,8 @@ def bullfrog_vf(cosmo, dg, mesh_shape: tuple, paint_order: int = 2, paint_deconv
     return vector_field
 
 
-class NbodyCtx:
+class NbodyCtx(Ctx):
     """What `nbody_bf_vjp` needs: the plan, host scalars and the device checkpoint buffer."""
-
-    def __init__(self, **kw):
-        self.__dict__.update(kw)
 
     def state(self, i):
         """Checkpoint i of the composite path as (x'_i, v_i) views: x'_i = x_i + v_i dg / 2, the position offsets the step's paint
@@ -976,7 +963,7 @@ def nbody_bf(cosmo, init_mesh, pos, a0=0., a1=1., n_steps=5, paint_order: int = 
     v = torch.empty((N, 3), dtype=torch.float32, device=spec.device)
     ckpt = None
     if return_ctx or want_snaps:
-        nck = lib.mcpm_nbody_ckpt_floats(plan.h, n_steps, lpt_order)
+        nck = plan.call("mcpm_nbody_ckpt_floats", n_steps, lpt_order)
         ckpt = torch.empty((nck,), dtype=torch.float32, device=spec.device)
         if not getattr(plan, "_pitch_probed", False):
             # once per plan: the library times its adjoint particle kernel on THIS buffer for three layouts of the checkpoint
@@ -986,12 +973,11 @@ def nbody_bf(cosmo, init_mesh, pos, a0=0., a1=1., n_steps=5, paint_order: int = 
             if os.environ.get("MCPM_PARTICLE_PITCH") is not None:
                 plan.call("mcpm_plan_set_particle_pitch", int(os.environ["MCPM_PARTICLE_PITCH"]))
             else:
-                plan.call("mcpm_plan_probe_particle_pitch", _ptr(ckpt), nck, None)
+                plan.call("mcpm_plan_probe_particle_pitch", ckpt, nck, None)
     pitch = C.c_int64()
     plan.call("mcpm_plan_particle_pitch", C.byref(pitch))
     pitch = int(pitch.value)
-    plan.call("mcpm_nbody_bf_f32", _ptr(spec), n_steps, _dptr(alphas), _dptr(betas), float(dg), _dptr(lpt_s),
-              int(lpt_order), int(paint_order), _ptr(x), _ptr(v), _ptr(ckpt))
+    plan.call("mcpm_nbody_bf_f32", spec, n_steps, alphas, betas, float(dg), lpt_s, int(lpt_order), int(paint_order), x, v, ckpt)
     lp = LatticePos(x, mesh_shape, ptcl_shape)
     if want_snaps:
         if lattice_out:
@@ -1002,10 +988,8 @@ def nbody_bf(cosmo, init_mesh, pos, a0=0., a1=1., n_steps=5, paint_order: int = 
     if fn is not None:
         out = _apply_fn(fn, out, lattice_out)
     if return_ctx:
-        ctx = NbodyCtx(plan=plan, init_mesh=spec, n_steps=n_steps, dg=dg, alphas=alphas, betas=betas, lpt_s=lpt_s,
-                       lpt_order=int(lpt_order), paint_order=int(paint_order), ckpt=ckpt, cosmo=cosmo, a0=a0, a1=a1,
-                       integrator=integrator, pitch=pitch)
-        return out, ctx
+        return out, NbodyCtx(plan=plan, init_mesh=spec, n_steps=n_steps, dg=dg, alphas=alphas, betas=betas, lpt_s=lpt_s, lpt_order=int(lpt_order),
+                             paint_order=int(paint_order), ckpt=ckpt, cosmo=cosmo, a0=a0, a1=a1, integrator=integrator, pitch=pitch)
     return out
 
 
@@ -1040,10 +1024,10 @@ def _nbody_bf_opts_vjp(ctx, xb, vb):
         vt = vb + tau * xb
         abar[i] = float((vt.double() * v.double()).sum())
         bbar[i] = float((vt.double() * F.double()).sum())
-        Fb = (float(ctx.betas[i]) * vt).contiguous()
+        Fb = float(ctx.betas[i]) * vt
         pb = torch.empty((N, 3), dtype=torch.float32, device=x.device)
-        plan.call("mcpm_pm_forces_vjp_opts_f32", _ptr(x), N, POS_LATTICE, ctx.paint_order, int(o["paint_deconv"]), _fd(o["lap_fd"]),
-                  _fd(o["grad_fd"]), _ptr(Fb), _ptr(pb))
+        plan.call("mcpm_pm_forces_vjp_opts_f32", x, N, POS_LATTICE, ctx.paint_order, int(o["paint_deconv"]), _fd(o["lap_fd"]), _fd(o["grad_fd"]),
+                  Fb, pb)
         xb = xb + pb
         vb = float(ctx.alphas[i]) * vt
     v0 = ctx.states[0, 1]
@@ -1051,8 +1035,8 @@ def _nbody_bf_opts_vjp(ctx, xb, vb):
     vb = vb + xb * (dg / 2)
     out = torch.empty(tuple(ctx.init_mesh.shape), dtype=torch.complex64, device=xb.device)
     sb = np.zeros(3)
-    plan.call("mcpm_lpt_vjp_opts_f32", _ptr(ctx.init_mesh), ctx.lpt_order, _dptr(np.asarray(ctx.lpt_s, dtype=np.float64)), _fd(o["lap_fd"]),
-              _fd(o["grad_fd"]), _ptr(xb.contiguous()), _ptr(vb.contiguous()), _ptr(out), _dptr(sb))
+    plan.call("mcpm_lpt_vjp_opts_f32", ctx.init_mesh, ctx.lpt_order, np.asarray(ctx.lpt_s, dtype=np.float64), _fd(o["lap_fd"]), _fd(o["grad_fd"]),
+              xb, vb, out, sb)
     return out, {"alpha": abar, "beta": bbar, "g": sb[0], "g2": sb[1], "dg2dg": sb[2], "dg": dgbar}
 
 
@@ -1102,8 +1086,8 @@ def nbody_bf_vjp(ctx, pos_bar, vel_bar):
     out = torch.empty(tuple(ctx.init_mesh.shape), dtype=torch.complex64, device=xb.device)
     sb = np.zeros(2 * n + 4)
     plan.call("mcpm_plan_set_particle_pitch", 0 if ctx.pitch == 3 * plan.N else ctx.pitch)      # the layout this checkpoint was written in
-    plan.call("mcpm_nbody_bf_vjp_f32", _ptr(ctx.init_mesh), n, _dptr(ctx.alphas), _dptr(ctx.betas), float(ctx.dg),
-              _dptr(ctx.lpt_s), ctx.lpt_order, ctx.paint_order, _ptr(ctx.ckpt), _ptr(xb), _ptr(vb), _ptr(out), _dptr(sb))
+    plan.call("mcpm_nbody_bf_vjp_f32", ctx.init_mesh, n, ctx.alphas, ctx.betas, float(ctx.dg), ctx.lpt_s, ctx.lpt_order, ctx.paint_order,
+              ctx.ckpt, xb, vb, out, sb)
     bars = {"alpha": sb[:n].copy(), "beta": sb[n:2 * n].copy(), "g": sb[2 * n], "g2": sb[2 * n + 1], "dg2dg": sb[2 * n + 2],
             "dg": sb[2 * n + 3]}
     return out, bars
@@ -1146,12 +1130,15 @@ def lpt_vjp(cosmo, init_mesh, pos, a, dpos_bar, vel_bar, lpt_order: int = 2, ctx
     out = torch.empty(tuple(spec.shape), dtype=torch.complex64, device=spec.device)
     sb = np.zeros(3)
     saved = ctx.save if ctx is not None else None
-    if not isinstance(a, torch.Tensor) and (np.ndim(a) == 0 or np.size(a) == 1):
-        sc = np.array([float(a2g(cosmo, a)), float(a2g2(cosmo, a)), float(a2dg2dg(cosmo, a))])
+
+    def adjoint(sc, xb, vb):
         if saved is not None:
-            plan.call("mcpm_lpt_vjp_saved_f32", _ptr(spec), int(lpt_order), _dptr(sc), _ptr(saved), _ptr(xb), _ptr(vb), _ptr(out), _dptr(sb))
+            plan.call("mcpm_lpt_vjp_saved_f32", spec, int(lpt_order), sc, saved, xb, vb, out, sb)
         else:
-            plan.call("mcpm_lpt_vjp_f32", _ptr(spec), int(lpt_order), _dptr(sc), _ptr(xb), _ptr(vb), _ptr(out), _dptr(sb))
+            plan.call("mcpm_lpt_vjp_f32", spec, int(lpt_order), sc, xb, vb, out, sb)
+
+    if not isinstance(a, torch.Tensor) and (np.ndim(a) == 0 or np.size(a) == 1):
+        adjoint(np.array([float(a2g(cosmo, a)), float(a2g2(cosmo, a)), float(a2dg2dg(cosmo, a))]), xb, vb)
         return out, {"g": sb[0], "g2": sb[1], "dg2dg": sb[2]}
     # light cone: (F2, F1) = mcpm_lpt_f32 with (g, g2, dg2dg) = (0, -1, 0); the per-particle combination is adjointed by
     # mcpm_lpt_combine_vjp_f32, the rest by the scalar LPT adjoint with the same three scalars
@@ -1161,15 +1148,11 @@ def lpt_vjp(cosmo, init_mesh, pos, a, dpos_bar, vel_bar, lpt_order: int = 2, ctx
     else:
         F2 = torch.empty((plan.N, 3), dtype=torch.float32, device=spec.device)
         F1 = torch.empty((plan.N, 3), dtype=torch.float32, device=spec.device)
-        plan.call("mcpm_lpt_f32", _ptr(spec), int(lpt_order), 0.0, -1.0, 0.0, 0, 0, _ptr(F2), _ptr(F1))
+        plan.call("mcpm_lpt_f32", spec, int(lpt_order), 0.0, -1.0, 0.0, 0, 0, F2, F1)
     xb, vb = xb.clone(), vb.clone()
     gtb = torch.empty((plan.N, 3), dtype=torch.float32, device=spec.device)
-    plan.call("mcpm_lpt_combine_vjp_f32", _ptr(F1), _ptr(F2) if lpt_order == 2 else None, _ptr(gt), plan.N, _ptr(xb), _ptr(vb), _ptr(gtb))
-    sc = np.array([0.0, -1.0, 0.0])
-    if saved is not None:
-        plan.call("mcpm_lpt_vjp_saved_f32", _ptr(spec), int(lpt_order), _dptr(sc), _ptr(saved), _ptr(xb), _ptr(vb), _ptr(out), _dptr(sb))
-    else:
-        plan.call("mcpm_lpt_vjp_f32", _ptr(spec), int(lpt_order), _dptr(sc), _ptr(xb), _ptr(vb), _ptr(out), _dptr(sb))
+    plan.call("mcpm_lpt_combine_vjp_f32", F1, F2 if lpt_order == 2 else None, gt, plan.N, xb, vb, gtb)
+    adjoint(np.array([0.0, -1.0, 0.0]), xb, vb)
     return out, {"g": gtb[:, 0], "g2": gtb[:, 1], "dg2dg": gtb[:, 2]}      # per-particle cotangents stay on the device
 
 

@@ -1,6 +1,11 @@
 """Host helpers with the names of montecosmo/utils.py that the PM path uses (utils.py:21-29, :769-782,
 :1163-1168)."""
+import ctypes as C
+
 import numpy as np
+import torch
+
+from . import _lib
 
 
 def safe_div(x, y):
@@ -27,41 +32,33 @@ def scale_shape(shape, scale=1.):
     return tuple(int(2 * np.rint(s * scale / 2)) for s in shape)
 
 
+def _dev(x, dtype):
+    # `nbody` imports this module (it re-exports the helpers above, as the reference does), so it can only be imported here at call time
+    from . import nbody
+    return nbody._c64(x) if dtype is torch.complex64 else nbody._f32(x)
+
+
+def _stream_of(t):
+    return C.c_void_p(torch.cuda.current_stream(t.device).cuda_stream)
+
+
 def chreshape(mesh, shape):
     """Reshape a complex Hermitian tensor to the half-spectrum shape `shape`, truncating or padding so that the
     Hermitian symmetry and the mean (hence the average power) are preserved (utils.py:981-1013).  HIP kernel
     `mcpm_chreshape_c64`; returns a complex64 device tensor."""
-    import ctypes as C
-    import torch
-    from . import nbody
-    from ._lib import lib, check
-    x = nbody._c64(mesh)
-    ishape, oshape = ch2rshape(x.shape), ch2rshape(shape)
+    x = _dev(mesh, torch.complex64)
     out = torch.empty(tuple(int(v) for v in shape), dtype=torch.complex64, device=x.device)
-    check(lib.mcpm_chreshape_c64(C.c_void_p(torch.cuda.current_stream(x.device).cuda_stream), nbody._ptr(x), *ishape,
-                                 nbody._ptr(out), *oshape), None, "mcpm_chreshape_c64")
+    _lib.call("mcpm_chreshape_c64", _stream_of(x), x, *ch2rshape(x.shape), out, *ch2rshape(shape))
     return out
 
 
 def chreshape_vjp(out_bar, in_shape):
     """VJP of `chreshape`: cotangent of the reshaped spectrum -> cotangent of the input of half-spectrum shape
     `in_shape` (real-pair convention dL = Re sum conj(bar) dz)."""
-    import ctypes as C
-    import torch
-    from . import nbody
-    from ._lib import lib, check
-    ob = nbody._c64(out_bar)
-    ishape, oshape = ch2rshape(in_shape), ch2rshape(ob.shape)
+    ob = _dev(out_bar, torch.complex64)
     ib = torch.empty(tuple(int(v) for v in in_shape), dtype=torch.complex64, device=ob.device)
-    check(lib.mcpm_chreshape_vjp_c64(C.c_void_p(torch.cuda.current_stream(ob.device).cuda_stream), nbody._ptr(ob), *oshape,
-                                     nbody._ptr(ib), *ishape), None, "mcpm_chreshape_vjp_c64")
+    _lib.call("mcpm_chreshape_vjp_c64", _stream_of(ob), ob, *ch2rshape(ob.shape), ib, *ch2rshape(in_shape))
     return ib
-
-
-def _stream_of(t):
-    import ctypes as C
-    import torch
-    return C.c_void_p(torch.cuda.current_stream(t.device).cuda_stream)
 
 
 def _norm_factor(norm, shape):
@@ -78,24 +75,18 @@ def _norm_factor(norm, shape):
 def rg2cgh(mesh, norm="backward"):
     """Permute and reweight a real Gaussian tensor (3D, even sizes) into a complex Gaussian Hermitian tensor
     distributed as rfftn of a real Gaussian tensor (utils.py:892-906).  HIP kernel mcpm_rg2cgh_f32."""
-    import torch
-    from . import nbody
-    from ._lib import lib, check
-    x = nbody._f32(mesh)
+    x = _dev(mesh, torch.float32)
     out = torch.empty(r2chshape(x.shape), dtype=torch.complex64, device=x.device)
-    check(lib.mcpm_rg2cgh_f32(_stream_of(x), nbody._ptr(x), *x.shape, nbody._ptr(out)), None, "mcpm_rg2cgh_f32")
+    _lib.call("mcpm_rg2cgh_f32", _stream_of(x), x, *x.shape, out)
     return out * _norm_factor(norm, x.shape) if norm != "backward" else out
 
 
 def rg2cgh_vjp(meshk_bar):
     """VJP of rg2cgh: cotangent of the complex tensor (real-pair convention) -> cotangent of the real tensor."""
-    import torch
-    from . import nbody
-    from ._lib import lib, check
-    kb = nbody._c64(meshk_bar)
+    kb = _dev(meshk_bar, torch.complex64)
     shape = ch2rshape(kb.shape)
     out = torch.empty(shape, dtype=torch.float32, device=kb.device)
-    check(lib.mcpm_rg2cgh_vjp_f32(_stream_of(kb), nbody._ptr(kb), *shape, nbody._ptr(out)), None, "mcpm_rg2cgh_vjp_f32")
+    _lib.call("mcpm_rg2cgh_vjp_f32", _stream_of(kb), kb, *shape, out)
     return out
 
 
@@ -103,12 +94,8 @@ def cgh2rg(meshk, norm="backward"):
     """Permute and reweight a complex Gaussian Hermitian tensor into a real Gaussian tensor (utils.py:909-921): the
     inverse of rg2cgh.  norm="amp" lays a per-mode amplitude (the real part of `meshk`) out like the real tensor.
     HIP kernels mcpm_cgh2rg_f32 / mcpm_cgh2rg_amp_f32."""
-    import torch
-    from . import nbody
-    from ._lib import lib, check
-    k = nbody._c64(meshk)
+    k = _dev(meshk, torch.complex64)
     shape = ch2rshape(k.shape)
     out = torch.empty(shape, dtype=torch.float32, device=k.device)
-    fn = "mcpm_cgh2rg_amp_f32" if norm == "amp" else "mcpm_cgh2rg_f32"
-    check(getattr(lib, fn)(_stream_of(k), nbody._ptr(k), *shape, nbody._ptr(out)), None, fn)
+    _lib.call("mcpm_cgh2rg_amp_f32" if norm == "amp" else "mcpm_cgh2rg_f32", _stream_of(k), k, *shape, out)
     return out / _norm_factor(norm, shape) if norm not in ("backward", "amp") else out
