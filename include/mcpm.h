@@ -67,7 +67,7 @@ int mcpm_plan_slab_oob(mcpm_plan *plan, int64_t *count);
 int mcpm_plan_destroy(mcpm_plan *plan);
 const char *mcpm_last_error(const mcpm_plan *plan); /* plan may be NULL: last error of a failed create */
 /* ABI revision string; the Python loader (montecosmo_amd/_lib.py) refuses a library that reports another one. */
-#define MCPM_ABI_VERSION "mcpm 0.10 (gfx950)"
+#define MCPM_ABI_VERSION "mcpm 0.11 (gfx950)"
 const char *mcpm_version(void);
 /* Tiled CIC paints (montecosmo_amd/csrc/paint_tiled.hip).  A tile's window is a box of lattice points per axis -- chosen on the device
    for every input and every tile from the displacement field around it, or (16 + 2 halo + 1)^3 around the tile's bulk displacement when a
@@ -553,6 +553,26 @@ int mcpm_png_phi_f32(mcpm_plan *plan, const float *lin_mesh, float kphys_x, floa
 /* out = scale * safe_div(in, t(|k|)) on the half-spectrum: the PNG term of the Kaiser boost (bricks.py:181-183); self-adjoint. */
 int mcpm_png_div_f32(mcpm_plan *plan, const float *in, float kphys_x, float kphys_y, float kphys_z, const double *ks,
                      const double *trans, int ntab, float scale, float *out);
+/* Kaiser model on the curved sky and / or the light cone (montecosmo/bricks.py:200-231; the flat-sky, fixed-a branch is diagonal in k and needs no
+   kernel): one pass over the cells of the plan's mesh.  flags: bit 0 = curved sky, bit 1 = light cone.  geom (HOST, 9 doubles) = box_size[3],
+   R^T box_center[3], the flat-sky line of sight in cell axes [3]; the cell (i, j, k) sits at x = (i, j, k) box_size / shape - box_size / 2 + R^T centre.
+   curved sky: meshes = the six real meshes irfftn(k_a k_b / k^2 lin), ab = 00 01 02 11 12 22 (k in cell units; mcpm_kspace_hessian_f32 with
+               lap_fd = grad_fd = inf), M floats apart;  r = |x|, l = safe_div(x, r),
+               out = 1 + g [ b1E (T_00 + T_11 + T_22) + f sum_ab l_a l_b T_ab ] + fNL_bp phi.  The trace stands for irfftn(lin): lin must have no k = 0 mode.
+   flat sky:   meshes = irfftn(lin), irfftn(mu^2 lin);  r = |x . los|,  out = 1 + g [ b1E meshes[0] + f meshes[1] ] + fNL_bp phi.
+   g, f = g_obs, f_obs, or on the light cone a2g, a2f at a = chi2a(r) per cell from `tables` (DEVICE float64, as mcpm_observe_pos_f32 takes them:
+   chi ascending [nchi], a(chi) [nchi], a [ngrow], g [ngrow], f [ngrow]; clamped linear interpolation).  phi (M floats) may be NULL.
+   VJP: out_bar -> meshes_bar (as many meshes as `meshes`, OVERWRITTEN), phi_bar (NULL exactly when phi is) and scalars_out (DEVICE, 4 doubles):
+   cotangents of b1E, fNL_bp, g_obs, f_obs (the last two 0 on the light cone).  Tables VJP (light cone only): table_bar (DEVICE float64,
+   OVERWRITTEN) = chi_bar[nchi], g_bar[ngrow], f_bar[ngrow], the layout of mcpm_observe_pos_tables_vjp_f32.  Every sum is made in a fixed order or
+   in integers: repeat calls are bitwise equal.  Slab plans: MCPM_E_UNSUPPORTED. */
+int mcpm_kaiser_sky_f32(mcpm_plan *plan, const float *meshes, const float *phi, const double *geom, int flags, const double *tables, int nchi,
+                        int ngrow, double g_obs, double f_obs, double b1E, double fNL_bp, float *out);
+int mcpm_kaiser_sky_vjp_f32(mcpm_plan *plan, const float *meshes, const float *phi, const double *geom, int flags, const double *tables,
+                            int nchi, int ngrow, double g_obs, double f_obs, double b1E, double fNL_bp, const float *out_bar,
+                            float *meshes_bar, float *phi_bar, double *scalars_out);
+int mcpm_kaiser_sky_tables_vjp_f32(mcpm_plan *plan, const float *meshes, const double *geom, int flags, const double *tables, int nchi,
+                                   int ngrow, double b1E, const float *out_bar, double *table_bar);
 /* The five PNG terms of the Lagrangian bias weights (bricks.py:413-441), ADDED to `weights` (the output of mcpm_bias_weights_f32 on
    the same reads): dr, s2r raw reads of delta and s^2, ph, lp reads of phi and lap phi, png5 = {fNL_bp, fNL_bpd, fNL_bpd2, fNL_bps2,
    fNL_bn2p} (host).  <d^2> and <ph d> are fixed-order float64 sums; moments_out (device, 2 doubles, may be NULL) receives them. */

@@ -4,8 +4,9 @@ and the initial particle lattice (bricks.py:593-603).
 
 Primordial non-Gaussianity (png_type 'fNL' / 'bias'): the transfer table, `add_png`, the five PNG terms of `lagrangian_bias` and
 the `fNL_bias` reparametrisation, each with its VJP.  Alcock-Paczynski: `scale_pos`, `parperp2isoap`, `isoap2parperp` on the host and
-the `ap_auto` / `ap_param` remapping inside `observe_pos` (bricks.py:708-732, :795-857).  Out of scope: Eulerian bias, the stochastic term s_ep * phi of the likelihood
-(model.py:894) and PNG on the light-cone and curved-sky forms of the Kaiser model."""
+the `ap_auto` / `ap_param` remapping inside `observe_pos` (bricks.py:708-732, :795-857).  Kaiser model off the flat sky at fixed a (`kaiser_sky`,
+bricks.py:200-231: curved sky and / or light cone, with the PNG term fNL_bp phi) and its VJP.  Out of scope: Eulerian bias and the stochastic
+term s_ep * phi of the likelihood (model.py:894)."""
 import ctypes as C
 import os
 
@@ -487,6 +488,134 @@ def observe_pos_tables_vjp(ctx, out_bar):
     ctx.plan.call("mcpm_observe_pos_ap_tables_vjp_f32", ctx.p, ctx.v, ctx.dv, n, ctx.mode, ctx.geom, ctx.flags, ctx.tables, ctx.nchi, ctx.ngrow,
                   *_ap_args(ctx), ob, tb)
     return tb
+
+
+# ------------------------------------------------------------------------------------------------
+# Kaiser model on the curved sky and on the light cone (bricks.py:186-231 kaiser_model, :760-778 los_scalefactor_mesh)
+_KAISER_MU2 = {}
+
+
+def kaiser_mu2(shape, box_size, los):
+    """mu^2 = (k . los)^2 / k^2 on the half-spectrum of `shape`, k in h/Mpc (bricks.py:201-204), as irfftn sees it: on the kz = 0 and
+    kz = Nyquist planes a mode and its mirror image are both stored, and irfftn keeps the Hermitian part of the product mu^2 lin.  For a
+    real field's spectrum that drops the terms k_a k_b with exactly one of a, b on its Nyquist index (k_a keeps its sign -pi under the
+    mirror image, k_b does not) -- the rule of the Hessian kernel (kspace.hip).  Off those planes it is the plain mu^2.  Host float64."""
+    shape = tuple(int(s) for s in shape)
+    kvec = nbody.rfftk(shape, box_size)
+    kk = sum(k ** 2 for k in kvec)
+    nyq = [np.zeros(k.shape, bool) for k in kvec]
+    for a in range(3):
+        if shape[a] % 2 == 0:
+            nyq[a].reshape(-1)[shape[a] // 2] = True
+    special = np.zeros(kvec[2].shape, bool)
+    special.reshape(-1)[[0, shape[2] // 2]] = True
+    num = 0.
+    for a in range(3):
+        for b in range(3):
+            num = num + np.where(special & (nyq[a] != nyq[b]), 0., los[a] * los[b] * kvec[a] * kvec[b])
+    return nbody.safe_div(num, kk)
+
+
+def _kaiser_mu2_dev(shape, box_size, los, device):
+    key = (tuple(shape), tuple(float(b) for b in box_size), tuple(float(l) for l in los), str(device))
+    hit = _KAISER_MU2.get(key)
+    if hit is None:
+        if len(_KAISER_MU2) > 4:
+            _KAISER_MU2.clear()
+        hit = _KAISER_MU2[key] = torch.from_numpy(np.ascontiguousarray(kaiser_mu2(shape, box_size, los), dtype=np.float32)).to(device)
+    return hit
+
+
+def kaiser_sky(cosmo, lin_mesh, box_size, box_center, box_rot, b1E, fNL_bp=None, a_obs=None, curved_sky=True, kpow=None, return_ctx=False):
+    """The two branches of `kaiser_model` that are not diagonal in k (bricks.py:200-231), with the geometry of `los_scalefactor_mesh` on the
+    mesh of `lin_mesh`: the cell (i, j, k) sits at x = (i, j, k) box_size / shape - box_size / 2 + R^T box_center in cell axes, and
+        curved sky:  r = |x|, l = safe_div(x, r);  out = 1 + g(a) [ b1E delta + f(a) sum_ab l_a l_b irfftn(k_a k_b / k^2 lin) ] + fNL_bp phi
+        flat sky:    r = |x . los|;                out = 1 + g(a) [ b1E delta + f(a) irfftn(mu^2 lin) ] + fNL_bp phi
+    with a = a_obs or chi2a(cosmo, r) per cell (a_obs = None, the light cone), delta = irfftn(lin), phi = irfftn(safe_div(lin, t(|k|)))
+    (only when `fNL_bp` is not None; t from `kpow`, as the reference's Kaiser model takes it).  On the curved sky k is in cell units
+    (metrics.py:422, rfftk without a box) and the sum is the tensor form of the reference's delta / 3 + 8 pi / 15 sum_m Y_2m(l) irfftn(Y_2m(k) lin)
+    (the addition theorem); delta is taken as the trace of the six meshes, so `lin_mesh` MUST have a zero k = 0 mode (white2lin leaves
+    none).  On the flat sky k is in h/Mpc (bricks.py:201-204).  At r = 0 the direction is 0 and a the clamped end of the table: finite.
+    HIP: mcpm_kspace_hessian_f32 (or the mu^2 multiply) -> batched C2R -> mcpm_kaiser_sky_f32.  Returns the real mesh (float32)."""
+    spec = nbody._c64(lin_mesh)
+    shape = nbody.ch2rshape(spec.shape)
+    plan, dev = nbody.get_plan(shape), spec.device
+    curved, lightcone = bool(curved_sky), a_obs is None
+    c = rot_matrix(box_rot).T @ np.asarray(box_center, dtype=np.float64)
+    los = nbody.safe_div(c, np.linalg.norm(c))
+    geom = np.ascontiguousarray(np.concatenate([np.asarray(box_size, dtype=np.float64), c, los]))
+    flags = (1 if curved else 0) | (2 if lightcone else 0)
+    tables, nchi, ngrow, g, f = None, 0, 0, 0., 0.
+    if lightcone:
+        d, gtab = nbody._dist_cache(cosmo), nbody._growth_cache(cosmo)
+        nchi, ngrow = len(d["chi"]), len(gtab["a"])
+        tables = torch.from_numpy(np.concatenate([d["chi"][::-1], d["a"][::-1], gtab["a"], gtab["g"], gtab["f"]])).to(dev)
+    else:
+        g, f = float(nbody.a2g(cosmo, a_obs)), float(nbody.a2f(cosmo, a_obs))
+    nm = 6 if curved else 2
+    specs = torch.empty((nm,) + tuple(spec.shape), dtype=torch.complex64, device=dev)
+    mu2 = None
+    if curved:
+        plan.call("mcpm_kspace_hessian_f32", spec, specs, 1.0 / plan.M, _lib.FD_INF, _lib.FD_INF)
+    else:
+        mu2 = _kaiser_mu2_dev(shape, box_size, los, dev)
+        torch.mul(spec, 1.0 / plan.M, out=specs[0])
+        torch.mul(specs[0], mu2, out=specs[1])
+    meshes = torch.empty((nm,) + tuple(shape), dtype=torch.float32, device=dev)
+    plan.call("mcpm_fft_c2r", specs, meshes, nm)
+    phi = kphys = tab = nt = None
+    if fNL_bp is not None:
+        kphys = [float(s) / float(b) for s, b in zip(shape, box_size)]
+        tab, nt = png_table_dev(cosmo, kpow, dev)
+        plan.call("mcpm_png_div_f32", spec, kphys[0], kphys[1], kphys[2], tab, tab[nt:], nt, 1.0 / plan.M, specs[0])
+        phi = torch.empty(tuple(shape), dtype=torch.float32, device=dev)
+        plan.call("mcpm_fft_c2r", specs[0], phi, 1)
+    del specs
+    out = torch.empty(tuple(shape), dtype=torch.float32, device=dev)
+    args = (geom, flags, tables, nchi, ngrow, g, f, float(b1E), 0.0 if fNL_bp is None else float(fNL_bp))
+    plan.call("mcpm_kaiser_sky_f32", meshes, phi, *args, out)
+    if return_ctx:
+        return out, _lib.Ctx(plan=plan, spec=spec, shape=tuple(shape), meshes=meshes, phi=phi, args=args, curved=curved, lightcone=lightcone,
+                             mu2=mu2, kphys=kphys, tab=tab, nt=nt)
+    return out
+
+
+def kaiser_sky_vjp(ctx, out_bar):
+    """VJP of kaiser_sky: cotangent of the returned mesh -> dict with 'lin_mesh' (complex64, real-pair convention), 'b1E', 'fNL_bp' (floats;
+    0.0 without phi), at fixed a_obs 'g', 'f' (cotangents of a2g(a_obs), a2f(a_obs)), on the light cone 'tables': {'chi', 'g', 'f'}
+    (float64 numpy cotangents of the chi nodes of chi2a and of the growth tables, for `cosmo_vjp`), and with phi 'trans_bar' (cotangent of
+    the transfer table's entries).  HIP: mcpm_kaiser_sky_vjp_f32 -> batched R2C -> mcpm_kspace_hessian_vjp_f32 (or the mu^2 multiply),
+    mcpm_png_add_vjp_f32 for phi, mcpm_kaiser_sky_tables_vjp_f32.  Every sum is order-independent: repeat calls are bitwise equal."""
+    plan, shape, dev = ctx.plan, ctx.shape, ctx.spec.device
+    ob = nbody._f32(out_bar, shape)
+    nm = 6 if ctx.curved else 2
+    mb = torch.empty((nm,) + shape, dtype=torch.float32, device=dev)
+    pb = torch.empty(shape, dtype=torch.float32, device=dev) if ctx.phi is not None else None
+    scal = torch.empty(4, dtype=torch.float64, device=dev)
+    plan.call("mcpm_kaiser_sky_vjp_f32", ctx.meshes, ctx.phi, *ctx.args, ob, mb, pb, scal)
+    specs = torch.empty((nm,) + tuple(ctx.spec.shape), dtype=torch.complex64, device=dev)
+    plan.call("mcpm_fft_r2c", mb, specs, nm)
+    if ctx.curved:
+        lin_bar = torch.empty(tuple(ctx.spec.shape), dtype=torch.complex64, device=dev)
+        plan.call("mcpm_kspace_hessian_vjp_f32", specs, lin_bar, 1.0 / plan.M, _lib.FD_INF, _lib.FD_INF, 1, 0)
+    else:      # the adjoint of irfftn (rfftn / M, the modes 1 : nz // 2 doubled) behind the two real multipliers
+        lin_bar = (specs[0] + specs[1] * ctx.mu2) * (1.0 / plan.M)
+        lin_bar[..., 1:shape[-1] // 2] *= 2.0
+    res = {"trans_bar": None}
+    if ctx.phi is not None:
+        lb, res["trans_bar"] = png_phi_vjp(plan, ctx.spec, ctx.kphys, ctx.tab, ctx.nt, pb)
+        lin_bar = lin_bar + lb
+    if ctx.lightcone:
+        geom, flags, tables, nchi, ngrow, _, _, b1E, _ = ctx.args
+        tb = torch.empty(nchi + 2 * ngrow, dtype=torch.float64, device=dev)
+        plan.call("mcpm_kaiser_sky_tables_vjp_f32", ctx.meshes, geom, flags, tables, nchi, ngrow, b1E, ob, tb)
+        t = tb.cpu().numpy()
+        res["tables"] = {"chi": t[:nchi].copy(), "g": t[nchi:nchi + ngrow].copy(), "f": t[nchi + ngrow:].copy()}
+    s = scal.cpu().numpy()
+    res.update({"lin_mesh": lin_bar, "b1E": float(s[0]), "fNL_bp": float(s[1]) if ctx.phi is not None else 0.0})
+    if not ctx.lightcone:
+        res.update({"g": float(s[2]), "f": float(s[3])})
+    return res
 
 
 # ------------------------------------------------------------------------------------------------

@@ -1,0 +1,126 @@
+// Table look-ups shared by the kernels that read the growth / distance tables per particle or per cell (observe.hip, kaiser.hip):
+// clamped linear interpolation in float64 with its bracket and slope, and the order-independent integer sums that contract per-element
+// cotangents into the small cotangents of the tables.
+#pragma once
+#include <hip/hip_runtime.h>
+
+namespace {
+
+// np.interp (clamped) and its slope
+__device__ __forceinline__ double interp1(double x, const double *xp, const double *fp, int n, double &slope) {
+    if (x <= xp[0]) { slope = 0.; return fp[0]; }
+    if (x >= xp[n - 1]) { slope = 0.; return fp[n - 1]; }
+    int lo = 0, hi = n - 1;
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if (xp[mid] <= x) lo = mid; else hi = mid;
+    }
+    slope = (fp[hi] - fp[lo]) / (xp[hi] - xp[lo]);
+    return fp[lo] + slope * (x - xp[lo]);
+}
+
+// ---- cotangents of the look-up TABLES (light cone: how the cosmology enters; model.py:740, :781, bricks.py:750-768) -----------
+// y = np.interp(x, xp, fp) = fp[lo] + (fp[lo+1] - fp[lo]) t,  t = (x - xp[lo]) / (xp[lo+1] - xp[lo]):
+//   dy/dfp[lo] = 1 - t, dy/dfp[lo+1] = t;   dy/dxp[lo] = -slope (1 - t), dy/dxp[lo+1] = -slope t;   dy/dx = slope
+// (clamped ends: y = fp[0] or fp[n-1], slope 0).  The kernels below contract those with per-particle cotangents into small
+// table cotangents (integer accumulators, see ORDER-INDEPENDENT SUMS below); the host then contracts them with the tables'
+// finite-difference Jacobian w.r.t. the cosmological parameters (model.py cosmo_vjp).
+struct Interp {
+    int lo;
+    bool clamped;
+    double t, slope, y;
+};
+__device__ __forceinline__ Interp interp_idx(double x, const double *xp, const double *fp, int n) {
+    Interp r;
+    r.clamped = true;
+    if (x <= xp[0]) { r.lo = 0, r.t = 0., r.slope = 0., r.y = fp[0]; return r; }
+    if (x >= xp[n - 1]) { r.lo = n - 2, r.t = 1., r.slope = 0., r.y = fp[n - 1]; return r; }
+    r.clamped = false;
+    int lo = 0, hi = n - 1;
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if (xp[mid] <= x) lo = mid; else hi = mid;
+    }
+    const double dx = xp[hi] - xp[lo];
+    r.lo = lo;
+    r.t = (x - xp[lo]) / dx;
+    r.slope = (fp[hi] - fp[lo]) / dx;
+    r.y = fp[lo] + r.slope * (x - xp[lo]);
+    return r;
+}
+// same bracket, another value table on the same nodes
+__device__ __forceinline__ void interp_at(const Interp &b, const double *xp, const double *fp, double &y, double &slope) {
+    const double dx = xp[b.lo + 1] - xp[b.lo];
+    const double d = fp[b.lo + 1] - fp[b.lo];
+    y = fp[b.lo] + d * b.t;
+    slope = b.clamped ? 0. : d / dx;
+}
+// ORDER-INDEPENDENT SUMS.  The table cotangents end up in d logp / d Omega_m, and every gradient of this build is bitwise the same
+// call after call; float64 atomics are not (the first version of these kernels changed the last bits of Omega_m's gradient between
+// two calls).  So the contributions are summed as INTEGERS: pass 0 takes the maximum |contribution| of every table (order-independent
+// by nature), pass 1 rounds each contribution to 2^(e - 30) units (2^e >= that maximum, so a contribution is below 2^30 and a table
+// entry holds 2^32 of them) and adds it with 64-bit integer LDS / global atomics, and a last kernel scales the integers back.
+// Resolution: 10^-9 of the largest contribution per term.  A non-finite maximum makes the whole table NaN.
+#define LC_KINDS 5
+struct Acc {      // PASS 0: per-thread maxima;  PASS 1: integer accumulators in LDS
+    double mx[LC_KINDS];
+    unsigned long long *sh;
+    double scale[LC_KINDS];
+};
+template <int PASS>
+__device__ __forceinline__ void acc_add(Acc &A, int kind, int off, int idx, double v) {
+    if (PASS == 0) A.mx[kind] = fmax(A.mx[kind], fabs(v));      // (fmax drops a NaN operand: the callers' `bad` flag catches it)
+    else if (v != 0.) atomicAdd(A.sh + off + idx, (unsigned long long)__double2ll_rn(v * A.scale[kind]));
+}
+template <int PASS>
+__device__ __forceinline__ void scatter_fp(Acc &A, int kind, int off, const Interp &b, double ybar) {
+    acc_add<PASS>(A, kind, off, b.lo, ybar * (1. - b.t));
+    acc_add<PASS>(A, kind, off, b.lo + 1, ybar * b.t);
+}
+// ... and, for a look-up whose NODES move with the cosmology (chi -> a), into the node table's accumulator
+template <int PASS>
+__device__ __forceinline__ void scatter_xp(Acc &A, int kind, int off, const Interp &b, double ybar) {
+    acc_add<PASS>(A, kind, off, b.lo, -ybar * b.slope * (1. - b.t));
+    acc_add<PASS>(A, kind, off, b.lo + 1, -ybar * b.slope * b.t);
+}
+// mxbits: float bits (rounded up) of the maxima, one per kind; a NaN / inf contribution sets 0x7f800000 or above
+__device__ __forceinline__ void acc_begin(Acc &A, unsigned long long *sh, int ntot, const unsigned *mxbits, int pass) {
+    A.sh = sh;
+    for (int k = 0; k < LC_KINDS; ++k) {
+        A.mx[k] = 0.;
+        const int be = pass ? (int)(mxbits[k] >> 23) : 0;                 // biased exponent of the maximum: max < 2^(be - 126)
+        A.scale[k] = (be == 0 || be >= 255) ? 0. : __longlong_as_double((long long)(1023 + 30 - (be - 126)) << 52);      // 2^(30 - e)
+    }
+    if (pass) {
+        for (int i = threadIdx.x; i < ntot; i += blockDim.x) sh[i] = 0ull;
+        __syncthreads();
+    }
+}
+template <int PASS>
+__device__ __forceinline__ void acc_end(Acc &A, int ntot, unsigned *mxbits, unsigned long long *out, bool bad) {
+    if (PASS == 0) {
+        for (int k = 0; k < LC_KINDS; ++k) {
+            unsigned b = bad ? 0x7fc00000u : __float_as_uint(__double2float_ru(A.mx[k]));
+            if (!(A.mx[k] < 3.0e38)) b = 0x7fc00000u;
+#pragma unroll
+            for (int o = 32; o > 0; o >>= 1) b = max(b, (unsigned)__shfl_xor((int)b, o));
+            if ((threadIdx.x & 63) == 0 && b) atomicMax(mxbits + k, b);
+        }
+    } else {
+        __syncthreads();
+        for (int i = threadIdx.x; i < ntot; i += blockDim.x)
+            if (A.sh[i] != 0ull) atomicAdd(out + i, A.sh[i]);
+    }
+}
+// out[i] = integer sum scaled back; kind_end[k]: one past the last entry of kind k
+__global__ void lc_scale_kernel(const unsigned long long *__restrict__ acc, const unsigned *__restrict__ mxbits, int ntot, int e0, int e1,
+                                int e2, int e3, double *__restrict__ out) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= ntot) return;
+    const int k = i < e0 ? 0 : (i < e1 ? 1 : (i < e2 ? 2 : (i < e3 ? 3 : 4)));
+    const int be = (int)(mxbits[k] >> 23);
+    if (be >= 255) { out[i] = __longlong_as_double(0x7ff8000000000000ll); return; }
+    out[i] = be == 0 ? 0. : (double)(long long)acc[i] * __longlong_as_double((long long)(1023 - 30 + (be - 126)) << 52);
+}
+
+}  // namespace

@@ -1,12 +1,12 @@
 """`FieldLevelModel.evolve` (montecosmo/model.py:686-838) on the HIP path, with its hand-written reverse sweep.
 
 Built branch: bias_type 'lagrangian', evolution 'lpt' (scalar a_obs or light cone), 'nbody' (scalar a_obs, as the
-reference asserts) or 'kaiser' (flat sky, scalar a_obs: bricks.py:170-198), png_type None, 'fNL' or 'bias' (local primordial
+reference asserts) or 'kaiser' (any sky, scalar a_obs or light cone: bricks.py:170-231), png_type None, 'fNL' or 'bias' (local primordial
 non-Gaussianity: `evolve(..., png={'fNL': ..., ...})`, model.py:688, :751-758), ap_auto None, True or False (Alcock-Paczynski:
 model.py:64, :787-794; `evolve(..., ap={'alpha_iso': ..., 'alpha_ap': ...})` for False), kernel_type 'rectangular', linear power from a table (`lin_kpow`,
 bricks.py:75-77) or, with lin_kpow = None, from the Eisenstein-Hu fit of the current cosmology (bricks.py:72-74; power.py).
 Priors, likelihood and samplers: logdensity.py, samplers.py.  Not built: Eulerian bias, the stochastic term s_ep * phi of the
-likelihood (model.py:894), PNG on the light-cone / curved-sky Kaiser forms, Alcock-Paczynski in the Kaiser model (model.py:703-729
+likelihood (model.py:894), Alcock-Paczynski in the Kaiser model (model.py:703-729
 computes the moved positions and discards them), `ap_auto_absdetjac` and `rsd_ap_auto` (no live call site in the reference).
 
     fwd = FieldLevelForward(final_shape=(64, 64, 64), cell_length=20., box_center=(0, 0, 2000.), evolution='nbody',
@@ -36,9 +36,6 @@ class FieldLevelForward:
                  a_obs=None, curved_sky=True, lin_kpow=None, png_type=None, ap_auto=None, cosmo_fid=None):
         if evolution not in ('kaiser', 'lpt', 'nbody'):
             raise ValueError("evolution must be 'kaiser', 'lpt' or 'nbody'")
-        if evolution == 'kaiser' and (curved_sky or a_obs is None):
-            raise NotImplementedError("the Kaiser model is built for the flat sky at fixed a_obs (bricks.py:194-198); "
-                                      "its curved-sky / light-cone forms (bricks.py:200-231) are not")
         if png_type not in (None, 'fNL', 'bias'):
             raise ValueError("png_type must be None, 'fNL' or 'bias'")
         self.png_type = png_type
@@ -141,7 +138,8 @@ class FieldLevelForward:
         d = nbody._dist_cache(cosmo)
         return nbody.interp_dev(self._r0, d["chi"][::-1], d["a"][::-1]).reshape(-1, 1)
 
-    # ---- Kaiser model (bricks.py:170-198, flat sky, fixed a): growth, Eulerian linear bias and RSD, diagonal in k -------
+    # ---- Kaiser model: growth, Eulerian linear bias and RSD.  Flat sky at fixed a (bricks.py:170-198): diagonal in k, `_kaiser`;
+    # curved sky and / or light cone (bricks.py:200-231): a real-space pass with a line of sight and a growth factor per cell, `_kaiser_sky` ----
     def _mu2_mesh(self, device):
         """(k . los)^2 / k^2 on the half-spectrum of the evolution mesh, los = the box centre's direction in cell axes."""
         if getattr(self, "_mu2", None) is None:
@@ -159,6 +157,8 @@ class FieldLevelForward:
         return out
 
     def _kaiser(self, cosmo, bias, white, evol_k, return_ctx, png=None):
+        if self.curved_sky or self.a_obs is None:
+            return self._kaiser_sky(cosmo, bias, white, evol_k, return_ctx, png=png)
         D, f = float(nbody.a2g(cosmo, self.a_obs)), float(nbody.a2f(cosmo, self.a_obs))
         mu2 = self._mu2_mesh(evol_k.device)
         boost = D * ((1.0 + float(bias["b1"])) + f * mu2)                 # b1E = 1 + b1 (bricks.py:454)
@@ -171,7 +171,39 @@ class FieldLevelForward:
             return gxy, EvolveCtx(cosmo=cosmo, white=white, evol_k=evol_k, kaiser=(D, f, float(bias["b1"]), boost), png=png, bias=bias)
         return gxy
 
+    def _kaiser_sky(self, cosmo, bias, white, evol_k, return_ctx, png=None):
+        """bricks.kaiser_sky on the evolution mesh (model.py:690-695); the PNG term fNL_bp phi with the table of `lin_kpow`."""
+        gxy, sky = bricks.kaiser_sky(cosmo, evol_k, self.box_size, self.box_center, self.box_rotvec, 1.0 + float(bias["b1"]),
+                                     fNL_bp=None if png is None else png["fNL_bp"], a_obs=self.a_obs, curved_sky=self.curved_sky,
+                                     kpow=self.lin_kpow, return_ctx=True)
+        # the growth-table Jacobian of cosmo_vjp at fixed a_obs: host work done while the device runs the forward pass (see `evolve`)
+        fd = self._cosmo_scalar_fd(cosmo, self.cosmo_fd_params) if (return_ctx and self.a_obs is not None and getattr(self, "cosmo_fd_params", None)) else None
+        cosmo._workspace = {}
+        if return_ctx:
+            return gxy, EvolveCtx(cosmo=cosmo, white=white, evol_k=evol_k, sky=sky, scalar_fd=fd, png=png, bias=bias)
+        return gxy
+
+    def _kaiser_sky_vjp(self, ctx, gxy_bar):
+        cosmo = ctx.cosmo
+        r = bricks.kaiser_sky_vjp(ctx.sky, nbody._f32(gxy_bar, self.evol_shape))
+        evol_b, extra = r["lin_mesh"], {}
+        bias_bar = {k: 0.0 for k in bricks.BIAS_KEYS}
+        bias_bar["b1"] = r["b1E"]
+        if ctx.png is not None:
+            png_bar, bb = bricks.fNL_bias_vjp(ctx.png_in, ctx.bias, {"fNL_bp": r["fNL_bp"]}, p=1., png_type=self.png_type)
+            bias_bar["b1"] += bb["b1"]
+            bias_bar["b2"] += bb["b2"]
+            extra = {"png": png_bar, "trans_bar": r["trans_bar"]}
+        init_b = chreshape_vjp(evol_b, r2chshape(self.init_shape))
+        white_b = self._power_mult(init_b, cosmo)
+        s8b = float((init_b.conj() * self._power_mult(ctx.white, cosmo, sigma8=1.0)).real.sum().item())
+        # fixed a_obs: cotangents of a2g(a_obs), a2f(a_obs); light cone: of the chi nodes of chi2a and of the growth tables (cosmo_vjp)
+        kaiser = {"g": r["g"], "f": r["f"]} if self.a_obs is not None else r["tables"]
+        return {"white_mesh": white_b, "bias": bias_bar, "sigma8": s8b, "init_bar": init_b, "kaiser": kaiser, **extra}
+
     def _kaiser_vjp(self, ctx, gxy_bar):
+        if getattr(ctx, "sky", None) is not None:
+            return self._kaiser_sky_vjp(ctx, gxy_bar)
         cosmo = ctx.cosmo
         D, f, b1, boost = ctx.kaiser
         gb = nbody._f32(gxy_bar, self.evol_shape)
@@ -261,6 +293,8 @@ class FieldLevelForward:
         """Cotangent of gxy_mesh (real, paint_shape) -> {'white_mesh': complex64 cotangent (real-pair convention),
         'bias': dict, 'sigma8': float, 'growth': cotangents of the growth scalars (see nbody.lpt_vjp / nbody_bf_vjp),
         'bias_growth': cotangent(s) of a2g(a) through the bias weights, 'gf': cotangent of a2g(a_obs) a2f(a_obs) through rsd}.
+        evolution 'kaiser': 'white_mesh', 'bias', 'sigma8' and 'kaiser': {'g', 'f'}, the cotangents of a2g(a_obs), a2f(a_obs), or on the light cone
+        {'chi', 'g', 'f'}, the cotangents of the chi nodes of chi2a and of the growth tables (float64 arrays).
         With ap_auto also 'ap': {'alpha_iso', 'alpha_ap'} cotangents (0 for ap_auto=True), and for ap_auto=True at fixed a_obs 'ap_chi_bar':
         the cotangent of the chi nodes of chi2a(cosmo, r') (device float64; cosmo_vjp).
         With png_type also 'png': cotangents of the six entries of the `png` dict given to evolve (the fNL_bias reparametrisation
@@ -436,18 +470,19 @@ class FieldLevelForward:
 
     def _cosmo_vjp_lightcone(self, ctx, grads, params, rel_eps):
         """cosmo_vjp on the light cone (a_obs = None, the reference's default configuration, model.py:45, :62): dL/dtheta =
-        sum over the five tables of <table_bar, d table / d theta>, the table Jacobian by central differences of the host
+        sum over the five tables (three for 'kaiser') of <table_bar, d table / d theta>, the table Jacobian by central differences of the host
         float64 RK4 tables (256-point distance table, 128-point growth tables), plus the Eisenstein-Hu term as at fixed a_obs."""
-        if self.evolution != 'lpt':
-            raise NotImplementedError("light cone is built for evolution='lpt' (model.py:770 asserts the same for 'nbody')")
+        if self.evolution == 'nbody':
+            raise NotImplementedError("light cone is built for evolution='lpt' and 'kaiser' (model.py:770 asserts the same for 'nbody')")
         cosmo = ctx.cosmo
-        bars = self.lightcone_table_bars(ctx, grads)
+        # 'kaiser': the per-cell look-ups a = chi2a(r), a2g(a), a2f(a) of bricks.kaiser_sky, already contracted by evolve_vjp (chi, g, f)
+        bars = grads["kaiser"] if self.evolution == 'kaiser' else self.lightcone_table_bars(ctx, grads)
         out = {}
         for name in params:
             h, pair = self._cosmo_fd_pair(cosmo, name, rel_eps)
             tabs = [self._lightcone_tables(c) for c in pair]
             inits = [self._power_mult(ctx.white, c) for c in pair] if self.lin_kpow is None else []
-            out[name] = float(sum(np.dot(bars[k], (tabs[0][k] - tabs[1][k]) / (2 * h)) for k in self._LC_TABLES))
+            out[name] = float(sum(np.dot(bars[k], (tabs[0][k] - tabs[1][k]) / (2 * h)) for k in self._LC_TABLES if k in bars))
             out[name] += self._trans_term(grads, pair, h)
             if inits:
                 out[name] += float((grads["init_bar"].conj() * (inits[0] - inits[1])).real.sum().item()) / (2 * h)
