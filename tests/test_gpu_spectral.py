@@ -23,6 +23,7 @@ INF = np.inf
 P1, P2, P3 = (64, 64, 64), (128, 64, 256), (64, 256, 128)
 P4, P5, P6 = (1024, 64, 64), (64, 1024, 64), (64, 64, 1024)
 G1, G2 = (48, 40, 24), (96, 64, 128)
+O1, O2 = (9, 15, 8), (15, 10, 12)      # odd nx / ny (no Nyquist plane on that axis), rocFFT at odd lengths
 PATH_AB = [P1, P2, P3, P4, P5, P6]
 ALL = PATH_AB + [G1, G2]
 A_OBS = 0.7
@@ -436,7 +437,7 @@ HESS_CASES = [(INF, INF), (2, 2), (4, 4), (2, 4), (4, INF)]
 HESS_VJP_FLAGS = [(0, 0), (1, 1), (1, 0), (0, 1), (1, 1)]
 
 
-@pytest.mark.parametrize("shape", [P1, P4, P6, G1], ids=sid)
+@pytest.mark.parametrize("shape", [P1, P4, P6, G1, O1, O2], ids=sid)
 def test_kspace_kernels_abi(nb, shape):
     """mcpm_kspace_force_f32 / _vjp_f32 and mcpm_kspace_hessian_f32 / _vjp_f32 mode by mode against numpy products of
     the oracle's kernels, over the FD orders (same and mixed), kcut, deconv_order, zweights, hermitian and accumulate
@@ -540,7 +541,7 @@ def test_kspace_kernels_abi(nb, shape):
 
 
 # ------------------------------------------------------------------------------------------------ (h) R2C / C2R batches
-@pytest.mark.parametrize("shape", [P2, P4, P5, P6, G1], ids=sid)
+@pytest.mark.parametrize("shape", [P2, P4, P5, P6, G1, O1, O2], ids=sid)
 def test_fft_batches_abi(nb, shape):
     """mcpm_fft_r2c / mcpm_fft_c2r at batch 1, 3 and 6 (xplain_kernel + batched y / z passes, or rocFFT) against numpy;
     the C2R gets a NON-Hermitian half-spectrum, which it must project as numpy's irfftn does."""
