@@ -67,7 +67,7 @@ int mcpm_plan_slab_oob(mcpm_plan *plan, int64_t *count);
 int mcpm_plan_destroy(mcpm_plan *plan);
 const char *mcpm_last_error(const mcpm_plan *plan); /* plan may be NULL: last error of a failed create */
 /* ABI revision string; the Python loader (montecosmo_amd/_lib.py) refuses a library that reports another one. */
-#define MCPM_ABI_VERSION "mcpm 0.11 (gfx950)"
+#define MCPM_ABI_VERSION "mcpm 0.12 (gfx950)"
 const char *mcpm_version(void);
 /* Tiled CIC paints (montecosmo_amd/csrc/paint_tiled.hip).  A tile's window is a box of lattice points per axis -- chosen on the device
    for every input and every tile from the displacement field around it, or (16 + 2 halo + 1)^3 around the tile's bulk displacement when a
@@ -553,6 +553,20 @@ int mcpm_png_phi_f32(mcpm_plan *plan, const float *lin_mesh, float kphys_x, floa
 /* out = scale * safe_div(in, t(|k|)) on the half-spectrum: the PNG term of the Kaiser boost (bricks.py:181-183); self-adjoint. */
 int mcpm_png_div_f32(mcpm_plan *plan, const float *in, float kphys_x, float kphys_y, float kphys_z, const double *ks,
                      const double *trans, int ntab, float scale, float *out);
+/* Posterior of the initial field under the fiducial flat-sky Kaiser model, given the observed contrast (montecosmo/bricks.py:234-247, :159-164;
+   model.py:1444-1477): one streaming pass over the plan's half-spectrum, batched over n_chains.  delta_obs: half-spectrum of the observed
+   contrast (one, shared by the chains); noise: n_chains half-spectra, rg2cgh of unit normal meshes (may be NULL when temp = 0); (ks, pows,
+   ntab), amp, kphys as mcpm_power_mult_f32 takes them; los: the line of sight in cell axes; g, f = a2g, a2f at the fiducial scale factor;
+   cell_power = prod(mesh_shape / box_size).  Per mode, scalars in float64:
+     mu = safe_div(k . los, |k|),  P = amp interp(|k|),  p = P cell_power,  boost = g (b1E + f mu^2),
+     stds^2 = p / (1 + boost^2 / var_noise p),  means = stds^2 boost / var_noise delta_obs,
+     white[b] = scale_field safe_div(sqrt(temp) stds noise[b] + means, sqrt(P))        (exactly 0 where P = 0)
+   white (n_chains half-spectra), means (one half-spectrum) and stds (Mh floats) may each be NULL, not all three.  No reduction: repeat calls
+   are bitwise equal.  Slab plans: MCPM_E_UNSUPPORTED. */
+int mcpm_kaiser_post_c64(mcpm_plan *plan, const float *delta_obs, const float *noise, int n_chains, float kphys_x, float kphys_y, float kphys_z,
+                         double amp, const double *ks, const double *pows, int ntab, double los_x, double los_y, double los_z, double g,
+                         double f, double b1E, double var_noise, double temp, double scale_field, double cell_power, float *white,
+                         float *means, float *stds);
 /* Kaiser model on the curved sky and / or the light cone (montecosmo/bricks.py:200-231; the flat-sky, fixed-a branch is diagonal in k and needs no
    kernel): one pass over the cells of the plan's mesh.  flags: bit 0 = curved sky, bit 1 = light cone.  geom (HOST, 9 doubles) = box_size[3],
    R^T box_center[3], the flat-sky line of sight in cell axes [3]; the cell (i, j, k) sits at x = (i, j, k) box_size / shape - box_size / 2 + R^T centre.

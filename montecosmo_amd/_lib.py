@@ -94,6 +94,8 @@ SIGNATURES = {
     "mcpm_png_weights_f32": (C.c_int, [_plan, C.c_int64, _f32p, _f32p, _f32p, _f32p, _f32p, C.c_float, C.POINTER(C.c_float), _f32p, _d64p]),
     "mcpm_png_weights_vjp_f32": (C.c_int, [_plan, C.c_int64, _f32p, _f32p, _f32p, _f32p, _f32p, C.c_float, C.POINTER(C.c_float), _f32p,
                                            _f32p, _f32p, _f32p, _f32p, _f32p, _d64p]),
+    "mcpm_kaiser_post_c64": (C.c_int, [_plan, _f32p, _f32p, C.c_int, C.c_float, C.c_float, C.c_float, C.c_double, _d64p, _d64p, C.c_int]
+                                      + [C.c_double] * 10 + [_f32p, _f32p, _f32p]),
     "mcpm_kaiser_sky_f32": (C.c_int, [_plan, _f32p, _f32p, _f64p, C.c_int, _d64p, C.c_int, C.c_int] + [C.c_double] * 4 + [_f32p]),
     "mcpm_kaiser_sky_vjp_f32": (C.c_int, [_plan, _f32p, _f32p, _f64p, C.c_int, _d64p, C.c_int, C.c_int] + [C.c_double] * 4
                                          + [_f32p, _f32p, _f32p, _d64p]),
@@ -189,7 +191,7 @@ SIGNATURES = {
 }
 
 
-ABI_VERSION = "mcpm 0.11 (gfx950)"   # must equal mcpm_version() of the loaded library (include/mcpm.h MCPM_ABI_VERSION)
+ABI_VERSION = "mcpm 0.12 (gfx950)"   # must equal mcpm_version() of the loaded library (include/mcpm.h MCPM_ABI_VERSION)
 
 
 def _load():

@@ -619,6 +619,89 @@ def kaiser_sky_vjp(ctx, out_bar):
 
 
 # ------------------------------------------------------------------------------------------------
+# Posterior of the initial field under the fiducial linear Kaiser model (bricks.py:234-247), lin2white (bricks.py:159-164) and
+# count2delta (bricks.py:927-937): what `FieldLevelLogDensity.kaiser_post` starts chains from
+_KPOW_TABLES = {}
+
+
+def _kpow_table_dev(cosmo, kpow, device):
+    """(device float64 tensor [ks, pows], n): the linear-power table normalised to sigma8 = 1 as mcpm_power_mult_f32 takes it -- `kpow`, or
+    the Eisenstein & Hu table of this cosmology; uploaded once per source."""
+    key = (None if kpow is None else (id(kpow[0]), id(kpow[1])), float(cosmo.Omega_c), float(cosmo.Omega_b), float(cosmo.h), float(cosmo.n_s),
+           str(device))
+    hit = _KPOW_TABLES.get(key)
+    if hit is None or (kpow is not None and (hit[2] is not kpow[0] or hit[3] is not kpow[1])):
+        if len(_KPOW_TABLES) > 8:
+            _KPOW_TABLES.clear()
+        ks, pows = power.lin_power_table(cosmo) if kpow is None else kpow
+        tab = np.concatenate([np.asarray(ks, dtype=np.float64), np.asarray(pows, dtype=np.float64)])
+        hit = _KPOW_TABLES[key] = (torch.from_numpy(tab).to(device), len(tab) // 2, None if kpow is None else kpow[0],
+                                   None if kpow is None else kpow[1])
+    return hit[0], hit[1]
+
+
+def kaiser_post_white(delta_obs, noise, cosmo, a, box_size, var_noise, b1E, los=(0., 0., 0.), kpow=None, temp=1., scale_field=1.,
+                      moments=False):
+    """The one call of mcpm_kaiser_post_c64 (csrc/kaiser_post.hip).  delta_obs: half-spectrum of the observed contrast; noise: None (no
+    white field is formed), or rg2cgh of unit normal meshes with a leading chain axis, (n_chains, *half-spectrum shape).  Returns
+    (white, means, stds): white = scale_field * lin2white(sqrt(temp) stds noise + means) per chain (None without noise), means / stds the
+    posterior moments (None unless `moments`)."""
+    spec = nbody._c64(delta_obs)
+    shape = nbody.ch2rshape(spec.shape)
+    plan, dev = nbody.get_plan(shape), spec.device
+    kphys = [float(s) / float(b) for s, b in zip(shape, box_size)]
+    tab, nt = _kpow_table_dev(cosmo, kpow, dev)
+    white, n_chains = None, 1
+    if noise is not None:
+        noise = nbody._c64(noise)
+        if noise.ndim != 4 or tuple(noise.shape[1:]) != tuple(spec.shape):
+            raise ValueError(f"noise must have shape (n_chains, {tuple(spec.shape)}), got {tuple(noise.shape)}")
+        n_chains = int(noise.shape[0])
+        white = torch.empty_like(noise)
+    means = torch.empty_like(spec) if moments else None
+    stds = torch.empty(tuple(spec.shape), dtype=torch.float32, device=dev) if moments else None
+    plan.call("mcpm_kaiser_post_c64", spec, noise, n_chains, kphys[0], kphys[1], kphys[2], float(cosmo.sigma8) ** 2, tab, tab[nt:], nt,
+              *[float(l) for l in los], float(nbody.a2g(cosmo, a)), float(nbody.a2f(cosmo, a)), float(b1E), float(var_noise), float(temp),
+              float(scale_field), float(np.prod(kphys)), white, means, stds)
+    return white, means, stds
+
+
+def kaiser_posterior(delta_obs, cosmo, a, box_size, var_noise, b1E, los=(0., 0., 0.), kpow=None):
+    """Posterior mean and std of the linear matter field (at a = 1) given the observed contrast `delta_obs` (half-spectrum), under the
+    flat-sky Kaiser model at scale factor `a` (bricks.py:234-247); the power is `kpow` (sigma8 = 1) or Eisenstein & Hu, times cosmo.sigma8^2:
+        p = P(|k|) prod(shape / box_size),  boost = a2g (b1E + a2f mu^2),  stds = sqrt(p / (1 + boost^2 / var_noise p)),
+        means = stds^2 boost / var_noise delta_obs.
+    HIP: mcpm_kaiser_post_c64 with temp = 0 and its two optional outputs.  Returns (means complex64, stds float32), device tensors."""
+    _, means, stds = kaiser_post_white(delta_obs, None, cosmo, a, box_size, var_noise, b1E, los=los, kpow=kpow, temp=0., moments=True)
+    return means, stds
+
+
+def lin2white(cosmo, lin_mesh, init_shape, box_size, kpow=None):
+    """Linear matter mesh -> white noise mesh (bricks.py:159-164): safe_div(lin_mesh, sqrt(P(|k|))), 0 where P = 0 (k = 0 and the modes
+    outside the table).  The divisor is the multiplier of white2lin (mcpm_power_mult_f32 on a mesh of ones), its reciprocal made safe."""
+    spec = nbody._c64(lin_mesh, utils.r2chshape(init_shape))
+    plan, dev = nbody.get_plan(init_shape), spec.device
+    kphys = [float(s) / float(b) for s, b in zip(init_shape, box_size)]
+    tab, nt = _kpow_table_dev(cosmo, kpow, dev)
+    t = torch.empty_like(spec)
+    plan.call("mcpm_power_mult_f32", torch.ones_like(spec), kphys[0], kphys[1], kphys[2], float(cosmo.sigma8) ** 2, tab, tab[nt:], nt, t)
+    t = t.real
+    ok = t != 0
+    return torch.where(ok, spec / torch.where(ok, t, torch.ones_like(t)), torch.zeros_like(spec))
+
+
+def count2delta(mesh, selec_mesh):
+    """Count mesh -> contrast mesh under the global integral constraint (bricks.py:927-937):
+        alpha = selec_mesh mean(mesh) / mean(selec_mesh),   delta = (mesh - alpha) / sqrt(mean(alpha^2))
+    `selec_mesh`: a mesh of the same shape, or a scalar (then delta = (mesh - mean) / |mean|).  Means in float64; float32 device tensor."""
+    m = nbody._f32(mesh).double()
+    sel = nbody._f32(selec_mesh).double() if (torch.is_tensor(selec_mesh) or np.ndim(selec_mesh) > 0) else \
+        torch.full((), float(selec_mesh), dtype=torch.float64, device=m.device)
+    alpha = sel * (m.mean() / sel.mean())
+    return ((m - alpha) / (alpha ** 2).mean() ** .5).float()
+
+
+# ------------------------------------------------------------------------------------------------
 # Sample mesh -> base mesh (bricks.py:290-320)
 def samp2base_mesh(init: dict, precond, transfer, inv=False, temp=1.) -> dict:
     """Transform the sample mesh into the base mesh, i.e. the initial wavevector coefficients (bricks.py:290-320):

@@ -164,6 +164,40 @@ def latent_log_prob_and_grad(x, c):
     return -0.5 * LOG2PI - math.log(sd) - 0.5 * ((x - mu) / sd) ** 2, -(x - mu) / sd ** 2, x * c["scale_fid"] + c["loc_fid"], c["scale_fid"]
 
 
+def trunc2std(y, loc, scale, low, high):
+    """Inverse of `std2trunc_and_derivs` (utils.py:229-264: invbody, invlowtail, invhightail), host float64.  As in the reference the branch
+    is chosen from the standardised y: beyond 12 sigma, with the bound on that side beyond 12 sigma too, the inverse of the soft maximum /
+    minimum, x = T log(e^(y/T) - e^(low/T)) and x = -T log(e^(-y/T) - e^(-high/T)); else the body, Phi^-1 of the rescaled cdf."""
+    from scipy.special import ndtr, ndtri
+    y, lo, hi = (y - loc) / scale, (low - loc) / scale, (high - loc) / scale
+    T = _TAIL_TEMP
+    if y < -_TAIL_LIM and lo < -_TAIL_LIM:
+        return y + T * math.log1p(-math.exp((lo - y) / T)) if y > lo else -math.inf
+    if y > _TAIL_LIM and hi > _TAIL_LIM:
+        return y - T * math.log1p(-math.exp((y - hi) / T)) if y < hi else math.inf
+    if y < 0:
+        cl, ch = ndtr(lo), ndtr(hi)
+        return float(ndtri((ndtr(y) - cl) / (ch - cl)))
+    cnl, cnh = ndtr(-lo), ndtr(-hi)
+    return -float(ndtri((cnh - ndtr(-y)) / (cnh - cnl)))
+
+
+def latent_sample_value(y, c):
+    """Sample value of ONE latent at the base value `y`, by its config `c`: the inverse of the third output of `latent_log_prob_and_grad`
+    (bricks.py:277-283).  Uniform and truncated latents: trunc2std with the fiducial parameters; else (y - loc_fid) / scale_fid."""
+    if "loc" not in c or c["low"] != -math.inf or c["high"] != math.inf:
+        return trunc2std(float(y), c["loc_fid"], c["scale_fid"], c["low"], c["high"])
+    return (float(y) - c["loc_fid"]) / c["scale_fid"]
+
+
+def _elementwise(fn, v, c):
+    """fn(v, c) for a number, or element by element for an array (a leading chain axis)."""
+    v = np.asarray(v, dtype=np.float64)
+    if v.ndim == 0:
+        return fn(float(v), c)
+    return np.array([fn(float(x), c) for x in v.reshape(-1)]).reshape(v.shape)
+
+
 class FieldLevelLogDensity:
     """log p(sample params, observed counts) and its gradient.
 
@@ -308,6 +342,15 @@ class FieldLevelLogDensity:
         a = fwd.a_obs if fwd.a_obs is not None else nbody.chi2a(cosmo_fid, fwd.lattice_radius(self.final_shape))
         return float(nbody.g2a(cosmo_fid, np.mean(nbody.a2g(cosmo_fid, a))))
 
+    def _kaiser_fiducial(self):
+        """What the fiducial linear Kaiser model is made of, for the 'kaiser' preconditioning and for `kaiser_post` alike (model.py:602-609,
+        :1140, :1457-1458): fid, cosmo, a = a_fid, los (cell axes), b1E = 1 + b1 and var_noise = s_e / (mean count per cell * selec_fid)."""
+        fwd, fid = self.fwd, self.fiducial()
+        cosmo_fid = self.make_cosmo(fid)
+        a_fid = self._fiducial_scale_factor(cosmo_fid)
+        var_fid = float(fid.get("s_e", 1.0)) / (self.ngbar_mean * fwd.cell_length ** 3 * self.selec_fid)   # model.py:602, :609, :1140 ('poisson' reads no s_e: 1)
+        return SimpleNamespace(fid=fid, cosmo=cosmo_fid, a=a_fid, los=fwd.los_cell(), b1E=1.0 + float(fid["b1"]), var_noise=var_fid)
+
     def _precond_scale_and_transfer(self):
         """(scale, transfer) of the white-field preconditioning (model.py:1127-1148): `scale` is the prior std of
         white_mesh_ (None = 1), `transfer` the factor taking rg2cgh / rfftn of it to unit-power white noise (a float, or
@@ -317,17 +360,15 @@ class FieldLevelLogDensity:
         unit = float(np.divide(fwd.init_shape, fwd.box_size).prod() ** .5)
         if self.precond in ("real", "fourier"):
             return None, unit
-        fid = self.fiducial()
-        cosmo_fid = self.make_cosmo(fid)
-        a_fid = self._fiducial_scale_factor(cosmo_fid)
+        k = self._kaiser_fiducial()
+        fid, cosmo_fid, a_fid, var_fid = k.fid, k.cosmo, k.a, k.var_noise
         kvec = nbody.rfftk(fwd.init_shape, fwd.box_size)
         kmesh = sum(ki ** 2 for ki in kvec) ** .5
-        mu = nbody.safe_div(sum(ki * li for ki, li in zip(kvec, fwd.los_cell())), kmesh)
-        boost = float(nbody.a2g(cosmo_fid, a_fid)) * ((1.0 + float(fid["b1"])) + float(nbody.a2f(cosmo_fid, a_fid)) * mu ** 2)
+        mu = nbody.safe_div(sum(ki * li for ki, li in zip(kvec, k.los)), kmesh)
+        boost = float(nbody.a2g(cosmo_fid, a_fid)) * (k.b1E + float(nbody.a2f(cosmo_fid, a_fid)) * mu ** 2)
         ks, pows = fwd.kpow(cosmo_fid)
         pmesh = np.interp(kmesh.reshape(-1), ks, pows * float(fid["sigma8"]) ** 2, left=0., right=0.).reshape(kmesh.shape)
         pmesh *= unit ** 2                                                                # power in cell units
-        var_fid = float(fid.get("s_e", 1.0)) / (self.ngbar_mean * fwd.cell_length ** 3 * self.selec_fid)   # model.py:602, :609, :1140 ('poisson' reads no s_e: 1)
         scale_k = (1 + boost ** 2 / var_fid * pmesh) ** .5
         cosmo_fid._workspace = {}
         dev = self.count_obs.device
@@ -353,6 +394,103 @@ class FieldLevelLogDensity:
 
     def base_params(self, sample):
         return self._prior(sample)[1]
+
+    def sample_params(self, base):
+        """Inverse of `base_params` (bricks.py:255-287, :310-318 with inv=True): base values -> sample values, for every sampled latent found
+        in `base` (fixed keys are ignored).  Scalars by their kind (`latent_sample_value`), a per-shell ngbars element by element,
+        'white_mesh' (half-spectrum at init_shape) -> 'white_mesh_' = cgh2rg(white / transfer) ('fourier', 'kaiser') or irfftn(white / transfer)
+        ('real').  Every value may carry a leading chain axis."""
+        out = {}
+        for name, c in self.latents.items():
+            if name in base:
+                out[name + "_"] = _elementwise(latent_sample_value, base[name], c)
+        if self.ngb_lat is not None and "ngbars" in base:
+            v = np.asarray(base["ngbars"], dtype=np.float64)
+            v = np.broadcast_to(v, v.shape[:-1] + (self.n_rbins,)) if v.ndim else np.full(self.n_rbins, float(v))
+            x = np.empty(v.shape)
+            for i in range(self.n_rbins):
+                x[..., i] = _elementwise(latent_sample_value, v[..., i], self._ngb_elem(i))
+            out["ngbars_"] = x
+        if "white_mesh" in base:
+            w = nbody._c64(base["white_mesh"])
+            if tuple(w.shape[-3:]) != r2chshape(self.fwd.init_shape) or w.ndim not in (3, 4):
+                raise ValueError(f"white_mesh must be a half-spectrum at init_shape {r2chshape(self.fwd.init_shape)}, got {tuple(w.shape)}")
+            tr = self.transfer
+            if torch.is_tensor(tr):
+                w = torch.where(tr != 0, w / torch.where(tr != 0, tr, torch.ones_like(tr)), torch.zeros_like(w))      # safe_div
+            else:
+                w = w / tr
+            inv = nbody.irfftn if self.precond == "real" else cgh2rg
+            out["white_mesh_"] = inv(w) if w.ndim == 3 else torch.stack([inv(w[b].contiguous()) for b in range(w.shape[0])])
+        return out
+
+    def count2delta(self):
+        """The observed contrast on the final mesh under the global integral constraint (model.py:1271-1285): unobserved cells of the counts
+        set to 0; the selection brought to final_shape and zeroed outside the mask when its shape differs from the final mesh, used as given
+        when the shapes agree, and a scalar without a selection mesh."""
+        obs = self.count_obs if self.mask is None else torch.where(self.mask, self.count_obs, torch.zeros_like(self.count_obs))
+        if self.selec_mesh is None:
+            return bricks.count2delta(obs, 1.0)
+        selec = self.selec_mesh
+        if tuple(selec.shape) != self.final_shape:
+            selec = self.sel_down if self.mask is None else torch.where(self.mask, self.sel_down, torch.zeros_like(self.sel_down))
+        return bricks.count2delta(obs, selec)
+
+    def kaiser_post(self, seed, base=False, temp=1., scale_field=1., n_chains=None, noise=None):
+        """Start values for every sampled latent (model.py:1444-1477): the scalars at their fiducial values and the initial field drawn from
+        its posterior under the fiducial flat-sky Kaiser model given the observed counts,
+            white_mesh = scale_field * lin2white(sqrt(temp) stds rg2cgh(noise) + means),   (means, stds) = bricks.kaiser_posterior(delta_obs, ...)
+        with delta_obs = chreshape(rfftn(count2delta()), init_shape), b1E = 1 + b1_fid, var_noise = s_e_fid / (mean count per cell * selec_fid)
+        and a_fid, the cell line of sight and the fiducial cosmology of the 'kaiser' preconditioning -- whatever `evolution` is.  `noise`: unit
+        normal real mesh(es), init_shape or (n_chains, *init_shape); default: drawn on the device from `seed`.  base=True: base space
+        ('white_mesh', a half-spectrum); else through `sample_params` ('white_mesh_').  With `n_chains` every value has a leading chain axis.
+        HIP: one call of mcpm_kaiser_post_c64 for all chains (no reduction: the same seed gives the same bits)."""
+        fwd = self.fwd
+        dev, shape = self.count_obs.device, tuple(fwd.init_shape)
+        nc = 1 if n_chains is None else int(n_chains)
+        if nc < 1:
+            raise ValueError("n_chains must be at least 1")
+        if noise is None:
+            gen = torch.Generator(device=dev).manual_seed(int(seed))
+            noise = torch.randn((nc,) + shape, dtype=torch.float32, device=dev, generator=gen)
+        else:
+            noise = nbody._f32(noise)
+            if tuple(noise.shape) == shape:
+                noise = noise.expand((nc,) + shape)
+            if tuple(noise.shape) != (nc,) + shape:
+                raise ValueError(f"noise must have shape {shape} or {(nc,) + shape}, got {tuple(noise.shape)}")
+        noise_k = torch.stack([rg2cgh(noise[b].contiguous()) for b in range(nc)])
+        k = self._kaiser_fiducial()
+        delta_obs = chreshape(nbody.rfftn(self.count2delta()), r2chshape(shape))
+        white, _, _ = bricks.kaiser_post_white(delta_obs, noise_k, k.cosmo, k.a, fwd.box_size, k.var_noise, k.b1E, los=k.los, kpow=fwd.lin_kpow,
+                                               temp=temp, scale_field=scale_field)
+        k.cosmo._workspace = {}
+        start = {name: (k.fid[name] if n_chains is None else np.full(nc, k.fid[name])) for name in self.latents}
+        if self.ngb_lat is not None:
+            start["ngbars"] = k.fid["ngbars"] if n_chains is None else np.tile(k.fid["ngbars"], (nc, 1))
+        start["white_mesh"] = white[0] if n_chains is None else white
+        return start if base else self.sample_params(start)
+
+    def condition(self, values):
+        """A new log density in which the latents named in `values` are fixed at those BASE values (moved from `latents` to `fixed`); the
+        observation, selection, mask, shells, preconditioning and likelihood are shared with this one.  Conditioning on every scalar leaves
+        the field alone: the target of the reference's field-only warm-up (script.py:46-49).  The scalar priors of the conditioned latents
+        drop out of the value (constants)."""
+        import copy
+        unknown = set(values) - set(self.latents) - ({"ngbars"} if self.ngb_lat is not None else set())
+        if unknown:
+            raise ValueError(f"cannot condition on {sorted(unknown)}: not sampled latents of this log density")
+        new = copy.copy(self)
+        new.latents = {name: c for name, c in self.latents.items() if name not in values}
+        new.fixed = dict(self.fixed)
+        for name, v in values.items():
+            if name == "ngbars":
+                v = np.asarray(v, dtype=np.float64)
+                new.fixed[name] = np.broadcast_to(v, (self.n_rbins,)).copy()
+                new.ngb_lat = new._ngb_conf = None
+            else:
+                new.fixed[name] = float(v)
+        return new
 
     def _white_prior(self, w):
         """white_mesh_ ~ Normal(0, scale) per cell (model.py:666-672; scale None = 1)."""

@@ -6,6 +6,9 @@ diagonal mass matrix, samplers.py:44), several independent chains from dispersed
 sample sizes of the scalar latents.  The 256^3 run of tools/run_nuts_field.py stays what it is labelled: a throughput figure.
 
 usage: python tools/run_nuts_convergence.py [final_n=36] [chains: 4 | c2 | 0,1,2,3] [n_warmup=200] [n_samples=200] [max_depth=10] [out.json] [draws_dir]
+       [--start=prior|kaiser]
+--start=kaiser: every chain starts from its own `kaiser_post` draw (scale_field = 7/8 as montecosmo/script.py:33) with the scalars at fiducial,
+as the reference's drivers do; the default, `prior`, is the dispersed start described above.
 A gpurun call lasts 20 minutes at most and a chain about ten: with `draws_dir` every chain's draws are kept as <draws_dir>/chain<c>.npz,
 chains found there are not run again -- so "c0", "c1", "c2", "c3" and then "0,1,2,3" in five calls give the four-chain summary."""
 import json, sys, time
@@ -13,6 +16,10 @@ import numpy as np, torch
 sys.path.insert(0, ".")
 from montecosmo_amd import model, logdensity, samplers, bricks, utils, nbody
 
+start_kind = ([a.split("=", 1)[1] for a in sys.argv if a.startswith("--start=")] or ["prior"])[-1]
+if start_kind not in ("prior", "kaiser"):
+    raise SystemExit("--start must be 'prior' or 'kaiser'")
+sys.argv = [a for a in sys.argv if not a.startswith("--start=")]
 nf = int(sys.argv[1]) if len(sys.argv) > 1 else 36
 arg = sys.argv[2] if len(sys.argv) > 2 else "4"      # "4": chains 0..3; "c2": chain 2 alone; "0,1,2,3": these chains
 chains = [int(arg[1:])] if arg.startswith("c") else ([int(c) for c in arg.split(",")] if "," in arg else list(range(int(arg))))
@@ -94,6 +101,8 @@ for c in chains:
     g = torch.Generator(device="cuda").manual_seed(100 + c)
     start = {k + "_": float(2.0 * torch.randn(1, generator=g, device="cuda")) for k in lat}      # dispersed: 2 fiducial scales
     start["white_mesh_"] = 0.3 * torch.randn(fwd.init_shape, device="cuda", generator=g) * prior_std
+    if start_kind == "kaiser":
+        start = ld.kaiser_post(100 + c, scale_field=7 / 8)
     q0 = flat.pack(start)
     n0, t0 = flat.n_eval, time.perf_counter()
     res = samplers.nuts_sample(flat, q0, n_warmup=n_warm, n_samples=n_samp, max_tree_depth=depth, seed=1 + c,

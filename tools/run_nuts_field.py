@@ -1,10 +1,17 @@
 """End-to-end field-level NUTS on one MI355X (BASELINE config 5 in miniature or at size): synthetic truth -> observed
 counts -> `FieldLevelLogDensity` -> `samplers.nuts_sample`.
-usage: python tools/run_nuts_field.py [final_n=146] [n_warmup=200] [n_samples=200] [max_depth=6] [evolution=nbody] [out.json] [nuts|mclmc] [precond=fourier]"""
+usage: python tools/run_nuts_field.py [final_n=146] [n_warmup=200] [n_samples=200] [max_depth=6] [evolution=nbody] [out.json] [nuts|mclmc] [precond=fourier] [--start=prior|kaiser]
+--start=kaiser: the field starts from `kaiser_post` (the posterior of the fiducial linear Kaiser model given the counts, scale_field = 7/8 as
+montecosmo/script.py:33) instead of 0.1 randn prior_std; the default, `prior`, is the start this tool has always used."""
 import json, sys, time
 import numpy as np, torch
 sys.path.insert(0, ".")
 from montecosmo_amd import model, logdensity, samplers, bricks, utils, nbody
+
+start_kind = ([a.split("=", 1)[1] for a in sys.argv if a.startswith("--start=")] or ["prior"])[-1]
+if start_kind not in ("prior", "kaiser"):
+    raise SystemExit("--start must be 'prior' or 'kaiser'")
+sys.argv = [a for a in sys.argv if not a.startswith("--start=")]
 
 nf = int(sys.argv[1]) if len(sys.argv) > 1 else 146
 n_warm = int(sys.argv[2]) if len(sys.argv) > 2 else 200
@@ -42,6 +49,8 @@ ld = logdensity.FieldLevelLogDensity(fwd, obs, lat, fixed, precond=precond)
 flat = samplers.FlatLogDensity(ld)
 start = dict(truth)
 start["white_mesh_"] = 0.1 * torch.randn(fwd.init_shape, device="cuda") * prior_std     # away from the truth, near the prior mode
+if start_kind == "kaiser":
+    start["white_mesh_"] = ld.kaiser_post(1, scale_field=7 / 8)["white_mesh_"]
 q0 = flat.pack(start)
 lp_truth = ld(truth)
 t0 = time.perf_counter()
