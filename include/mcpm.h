@@ -695,6 +695,41 @@ int mcpm_spectrum_bins_c64(void *stream, int nx, int ny, int nz, const float *sp
                            const double *edges, int n_edges, const double *los, const int *ells, int n_ells, void *work,
                            int64_t work_bytes, double *out);
 
+/* ---- catalogue -> register (montecosmo/model.py:1287-1362 register_catalog, bricks.py:882-1103; catalog.hip) -----------------
+   Per-object passes over a galaxy catalogue (ra, dec in degrees, z: DEVICE float64 arrays of length n) or a simulation box, and
+   the reductions around them.  The plan lends its stream and reduction scratch (and, for the footprint, its mesh shape).  atab
+   (ascending) / chitab: the DEVICE float64 distance table of mcpm_distance_table, ntab >= 2.  geom18 (HOST) = box_center[3],
+   rot[9] (matrix of box_rot, row-major), box_size[3], mesh_shape[3].  n = 0 is a no-op (see each call); bad arguments return
+   MCPM_E_ARG.  Every output is bitwise the same call after call (fixed-order float64 sums, no floating-point atomic).
+
+   Sky to Cartesian, all float64 (bricks.py:882-890, utils.py:1186-1196): a = 1 / (1 + z), chi = max(interp(a; atab, chitab), 0)
+   with the clamped linear interpolation of nbody.a2chi, x = chi (cos dec cos ra, cos dec sin ra, sin dec).
+   Cartesian to cell units (phys2cell_pos, bricks.py:638-646): ((x - box_center) @ rot + box_size / 2) * (mesh_shape / box_size).
+
+   sky2cart_minmax: minmax6 (device) = min x, y, z then max x, y, z over the objects (minmax_box, bricks.py:993-1002; +inf / -inf for
+     n = 0); *wsum (device, may be NULL when weights is) = float64 sum of the optional DEVICE float64 weights (0 without them). */
+int mcpm_sky2cart_minmax_f64(mcpm_plan *plan, const double *ra, const double *dec, const double *z, int64_t n, const double *atab,
+                             const double *chitab, int ntab, const double *weights, double *minmax6, double *wsum);
+/* sky2cell: out[n][3] float32 = cell coordinates, formed in float64 and rounded once.  out2 (may be NULL) = out * (float)ratio3[a]
+     per axis as a float32 product: `pos *= mask_shape / selec_shape` of bricks.py:1049 applied to the float32 result (ratio3: HOST). */
+int mcpm_sky2cell_f32(mcpm_plan *plan, const double *ra, const double *dec, const double *z, int64_t n, const double *atab,
+                      const double *chitab, int ntab, const double *geom18, const double *ratio3, float *out, float *out2);
+/* box2cell (full sky, bricks.py:1090-1096): out[n][3] float32 = phys2cell(pos + vscale (vel . los) los).  pos, vel: DEVICE [n][3]
+     arrays, both float64 (is_f64 = 1) or both float32 (0); vel may be NULL (then los3 and vscale are not read).  los3 (HOST): the
+     unit line of sight; vscale = 1 / (a_obs 100 E(a_obs)) turns peculiar velocities into Mpc/h. */
+int mcpm_box2cell_f32(mcpm_plan *plan, const void *pos, const void *vel, int is_f64, int64_t n, const double *geom18,
+                      const double *los3, double vscale, float *out);
+/* footprint: mask[c] (bytes, the plan's mesh) = 1 iff some object with weight > 0 (weights NULL: every object) has a non-zero
+     assignment weight at cell c on every axis -- the stencil, id0 rule, float32 per-axis weights and periodic wrap of
+     mcpm_paint_f32 (MCPM_POS_ABSOLUTE), orders 1..4.  This is `paint(...) > 0` of bricks.py:1045 / :1050 made exact: the paints
+     deposit through integer accumulators, where a small positive deposit can round to zero.  Independent of the order of the
+     objects.  accumulate = 0 clears the mask first, 1 keeps it (chunks).  Objects with a non-finite coordinate or outside the
+     paints' range |pos| < 32767 mark nothing. */
+int mcpm_footprint_u8(mcpm_plan *plan, const float *pos, int64_t n, const float *weights, int order, unsigned char *mask,
+                      int accumulate);
+/* masked_sum: out2 (device, 2 doubles) = float64 sum of mesh[i] over mask[i] != 0, and the number of such cells; n cells. */
+int mcpm_masked_sum_f64(mcpm_plan *plan, const float *mesh, const unsigned char *mask, int64_t n, double *out2);
+
 /* RK4 on atab = logspace(log10_amin, 0, steps); writes seven host arrays of length `steps`. */
 int mcpm_growth_table(double Omega_m, double Omega_de, double Omega_k, double w0, double wa,
                       double log10_amin, int steps, double *a, double *g, double *f, double *h, double *g2,

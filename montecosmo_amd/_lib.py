@@ -33,9 +33,10 @@ _d64p = _kind("_d64p", "device double *: tables, reduction outputs")
 _i16p = _kind("_i16p", "device int16_t *")
 _u32p = _kind("_u32p", "device unsigned *: torch keeps such slots as int32")
 _u8p = _kind("_u8p", "device bytes: bool masks, untyped uint8 workspace")
+_realp = _kind("_realp", "device const void *: float32 or float64 data, told apart by a flag of the call")
 _f64p = C.POINTER(C.c_double)      # host double *: `call` takes a float64 numpy array there
 _DEVICE_DTYPES = {_f32p: (torch.float32, torch.complex64), _d64p: (torch.float64,), _i16p: (torch.int16,),
-                  _u32p: (torch.int32, torch.uint32), _u8p: (torch.uint8, torch.bool)}
+                  _u32p: (torch.int32, torch.uint32), _u8p: (torch.uint8, torch.bool), _realp: (torch.float32, torch.float64)}
 HOST_F64 = "host float64"
 
 # name -> (restype, argtypes); mirrors include/mcpm.h one to one
@@ -186,6 +187,11 @@ SIGNATURES = {
     "mcpm_spectrum_workspace": (C.c_int, [C.c_int] * 7 + [C.POINTER(C.c_int64)]),
     "mcpm_spectrum_bins_c64": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, _f32p, C.c_int64, _f32p, C.c_int64, C.c_int, _f64p, _f64p,
                                          _f64p, _f64p, C.c_int, _f64p, C.POINTER(C.c_int), C.c_int, _u8p, C.c_int64, _d64p]),
+    "mcpm_sky2cart_minmax_f64": (C.c_int, [_plan, _d64p, _d64p, _d64p, C.c_int64, _d64p, _d64p, C.c_int, _d64p, _d64p, _d64p]),
+    "mcpm_sky2cell_f32": (C.c_int, [_plan, _d64p, _d64p, _d64p, C.c_int64, _d64p, _d64p, C.c_int, _f64p, _f64p, _f32p, _f32p]),
+    "mcpm_box2cell_f32": (C.c_int, [_plan, _realp, _realp, C.c_int, C.c_int64, _f64p, _f64p, C.c_double, _f32p]),
+    "mcpm_footprint_u8": (C.c_int, [_plan, _f32p, C.c_int64, _f32p, C.c_int, _u8p, C.c_int]),
+    "mcpm_masked_sum_f64": (C.c_int, [_plan, _f32p, _u8p, C.c_int64, _d64p]),
     "mcpm_growth_table": (C.c_int, [C.c_double] * 6 + [C.c_int] + [_f64p] * 7),
     "mcpm_distance_table": (C.c_int, [C.c_double] * 6 + [C.c_int] + [_f64p] * 2),
 }

@@ -8,6 +8,7 @@ the `ap_auto` / `ap_param` remapping inside `observe_pos` (bricks.py:708-732, :7
 bricks.py:200-231: curved sky and / or light cone, with the PNG term fNL_bp phi) and its VJP.  Out of scope: Eulerian bias and the stochastic
 term s_ep * phi of the likelihood (model.py:894)."""
 import ctypes as C
+import math
 import os
 
 import numpy as np
@@ -728,3 +729,350 @@ def samp2base_mesh_vjp(base_bar, precond, transfer, temp=1.):
     tr = torch.as_tensor(np.asarray(transfer, dtype=np.float32) * temp ** .5, device=nbody._device())
     kb = nbody._c64(base_bar) * tr
     return nbody.rfftn_vjp(kb) if precond == 'real' else utils.rg2cgh_vjp(kb)
+
+
+# ------------------------------------------------------------------------------------------------
+# Catalogue -> count, selection and mask meshes (bricks.py:882-1103).  The per-object coordinate chains, the footprint and the
+# reductions are the HIP passes of csrc/catalog.hip; the paints are nbody.nufft.  A catalogue is a dict-like of equally long columns
+# (a dict, an open .npz, a structured array), or a list / tuple of them; objects go to the device at most `chunk` at a time, and
+# paints and footprints accumulate across chunks, so device memory is bounded by the meshes plus one chunk.
+CATALOG_CHUNK = 1 << 24
+
+
+def radecz2cart(cosmo, radecz):
+    """RA, DEC (degrees), Z dict-like -> cartesian array (N, 3) in Mpc/h (bricks.py:882-890); host float64."""
+    radius = nbody.a2chi(cosmo, 1 / (1 + np.asarray(radecz['Z'], dtype=np.float64)))
+    return utils.radecrad2cart(radecz['RA'], radecz['DEC'], radius)
+
+
+def cart2radecz(cosmo, cart):
+    """Cartesian array (Mpc/h) -> RA, DEC (degrees), Z dict (bricks.py:892-899); host float64."""
+    ra, dec, radius = utils.cart2radecrad(cart)
+    return {'RA': ra, 'DEC': dec, 'Z': 1 / nbody.chi2a(cosmo, radius) - 1}
+
+
+def minmax_box(pos):
+    """(size, center, rotvec) of the axis-aligned box spanned by the positions (bricks.py:993-1002); host float64."""
+    pos = np.asarray(pos, dtype=np.float64)
+    low_corner, high_corner = pos.min(0), pos.max(0)
+    return high_corner - low_corner, (low_corner + high_corner) / 2, np.zeros(pos.shape[-1])
+
+
+def get_mesh_shape(box_size, cell_budget, padding=0.):
+    """Mesh shape (even integers) and cell length for a box size and a cell budget, with an optional padded fraction
+    (bricks.py:1004-1012).  The input is not modified."""
+    box_size = np.multiply(box_size, 1 + padding)
+    cell_length = float((box_size.prod() / cell_budget) ** (1 / 3))
+    mesh_shape = 2 * np.rint(box_size / cell_length / 2).astype(int)
+    return tuple(map(int, mesh_shape)), cell_length
+
+
+def _is_table(d):
+    return hasattr(d, "keys") or getattr(getattr(d, "dtype", None), "names", None) is not None
+
+
+def _has(table, key):
+    return key in (table.keys() if hasattr(table, "keys") else table.dtype.names)
+
+
+def catalog_tables(data, what="data", iterable_ok=False):
+    """`data` as a sequence of dict-likes: a dict-like itself, a list or a tuple of them, or (iterable_ok: full sky, where one pass
+    is enough) any iterable of them.  A one-shot iterator is refused otherwise: a cut-sky catalogue is read more than once."""
+    if _is_table(data):
+        return [data]
+    if isinstance(data, (list, tuple)):
+        if not all(_is_table(d) for d in data):
+            raise TypeError(f"{what}: every chunk must be a dict-like of columns")
+        return list(data)
+    if iterable_ok and hasattr(data, "__iter__"):
+        return data
+    raise TypeError(f"{what} must be a dict-like of columns, or a list or tuple of them (it is read more than once, so a one-shot "
+                    f"iterator cannot serve), got {type(data).__name__}")
+
+
+def _column(table, key, what):
+    if not _has(table, key):
+        raise KeyError(f"{what}: column {key!r} is missing")
+    return np.asarray(table[key])
+
+
+def _checked_weights(w, what):
+    w = np.asarray(w, dtype=np.float64)
+    if w.ndim != 1:
+        raise ValueError(f"{what}: WEIGHT must be one-dimensional")
+    if not np.all(np.isfinite(w)) or np.any(w < 0):
+        raise ValueError(f"{what}: WEIGHT must be finite and non-negative")
+    return w
+
+
+def check_catalog(tables, keys, what="data", optional=()):
+    """Host checks of every chunk before anything is uploaded: the columns `keys` exist with one length and finite values (the
+    bounding box's fmin / fmax would pass over a NaN and the paint would then meet it), 'pos' is (N, 3), an `optional` column that
+    is there has the shape of the first one and finite values, weights are finite and >= 0."""
+    for t in tables:
+        if not _is_table(t):
+            raise TypeError(f"{what}: every chunk must be a dict-like of columns")
+        cols = [_column(t, k, what) for k in keys]
+        n = len(cols[0])
+        if any(len(c) != n for c in cols):
+            raise ValueError(f"{what}: columns {keys} differ in length")
+        if keys[0] == 'pos' and (cols[0].ndim != 2 or cols[0].shape[1] != 3):
+            raise ValueError(f"{what}: pos must have shape (N, 3)")
+        names = list(keys)
+        for k in optional:
+            if _has(t, k):
+                cols.append(np.asarray(t[k]))
+                names.append(k)
+                if cols[-1].shape != cols[0].shape:
+                    raise ValueError(f"{what}: {k} must have the shape of {keys[0]}, got {cols[-1].shape} against {cols[0].shape}")
+        for k, c in zip(names, cols):
+            if not np.all(np.isfinite(c)):
+                raise ValueError(f"{what}: {k} must be finite")
+        if _has(t, 'WEIGHT') and len(_checked_weights(t['WEIGHT'], what)) != n:
+            raise ValueError(f"{what}: WEIGHT and {keys[0]} differ in length")
+
+
+class _Checked(list):
+    """Catalogue tables that check_catalog has passed: the bricks below take them as they are."""
+
+
+def checked_tables(data, keys, what="data", optional=(), iterable_ok=False):
+    """catalog_tables(data) with every table checked ONCE, here, where the catalogue enters (check_catalog scans every column, which
+    at 1e8-1e9 objects is real host time): the passes over the tables then only slice.  A lazily consumed iterable (iterable_ok) is
+    checked table by table as it is read; tables already checked are returned as they are."""
+    if isinstance(data, _Checked):
+        return data
+    tables = catalog_tables(data, what, iterable_ok)
+    if not isinstance(tables, list):
+        return _checked_lazily(tables, keys, what, optional)
+    check_catalog(tables, keys, what, optional)
+    return _Checked(tables)
+
+
+def _checked_lazily(tables, keys, what, optional):
+    for t in tables:
+        check_catalog([t], keys, what, optional)
+        yield t
+
+
+SKY_KEYS = ('RA', 'DEC', 'Z')
+
+
+def _pieces(tables, keys, chunk, optional=()):
+    """Dicts of host columns of checked tables, at most `chunk` objects each, in catalogue order."""
+    chunk = int(chunk)
+    if chunk < 1:
+        raise ValueError("chunk must be a positive number of objects")
+    for t in tables:
+        cols = {k: np.asarray(t[k]) for k in keys + tuple(optional) + ('WEIGHT',) if k in keys or _has(t, k)}
+        n = len(cols[keys[0]])
+        for i in range(0, n, chunk):
+            yield {k: v[i:i + chunk] for k, v in cols.items()}
+
+
+def weighted_size(tables, key='RA'):
+    """Sum of the WEIGHT column over checked tables in host float64, an object without one counting 1 (the length of column `key`)."""
+    return math.fsum(float(np.sum(t['WEIGHT'], dtype=np.float64)) if _has(t, 'WEIGHT') else float(len(t[key])) for t in tables)
+
+
+def _up(x, dtype):
+    return torch.from_numpy(np.ascontiguousarray(x, dtype=dtype)).to(nbody._device())
+
+
+def _dist_table_dev(cosmo):
+    """(the distance table [a | chi] on the device, its length), uploaded once per cosmology: kept next to the host table in
+    `cosmo._workspace`, so the chunk loops do not copy it again."""
+    key = "catalog.distance_table_device"
+    if key not in cosmo._workspace:
+        d = nbody._dist_cache(cosmo)
+        cosmo._workspace[key] = (_up(np.concatenate([d["a"], d["chi"]]), np.float64), len(d["a"]))
+    return cosmo._workspace[key]
+
+
+def _cell_geom(box_center, box_rotvec, box_size, mesh_shape):
+    """geom18 of include/mcpm.h: box_center, the matrix of box_rotvec (row-major), box_size, mesh_shape."""
+    g = np.concatenate([np.asarray(box_center, dtype=np.float64).reshape(3), rot_matrix(box_rotvec).reshape(9),
+                        np.asarray(box_size, dtype=np.float64).reshape(3), np.asarray(mesh_shape, dtype=np.float64).reshape(3)])
+    if not np.all(np.isfinite(g)) or np.any(g[12:] <= 0):
+        raise ValueError("box_center, box_rotvec, box_size and mesh_shape must be finite, box_size and mesh_shape positive")
+    return g
+
+
+def _radecz_dev(radecz):
+    ra, dec, z = (_up(radecz[k], np.float64) for k in ('RA', 'DEC', 'Z'))
+    if ra.ndim != 1 or dec.shape != ra.shape or z.shape != ra.shape:
+        raise ValueError("RA, DEC and Z must be one-dimensional and equally long")
+    return ra, dec, z
+
+
+def sky_extent(cosmo, radecz, weights=None):
+    """(low corner (3,), high corner (3,), weight sum) of radecz2cart(cosmo, radecz), all float64, in one pass on the device
+    (mcpm_sky2cart_minmax_f64); no objects: (+inf, -inf, 0)."""
+    ra, dec, z = _radecz_dev(radecz)
+    tab, nt = _dist_table_dev(cosmo)
+    w = None if weights is None else _up(weights, np.float64)
+    if w is not None and w.shape != ra.shape:
+        raise ValueError("weights must be as long as RA")
+    out = torch.empty(7, dtype=torch.float64, device=ra.device)
+    nbody.get_plan((8, 8, 8)).call("mcpm_sky2cart_minmax_f64", ra, dec, z, ra.numel(), tab, tab[nt:], nt, w, out, out[6:])
+    out = out.cpu().numpy()
+    return out[:3], out[3:6], float(out[6])
+
+
+def sky2cell_pos(cosmo, radecz, box_center, box_rotvec, box_size, mesh_shape, ratio=None):
+    """phys2cell_pos(radecz2cart(cosmo, radecz), ...) as an (N, 3) float32 device tensor, formed in float64 and rounded once
+    (mcpm_sky2cell_f32).  With `ratio` (3,): also that tensor times float32(ratio), the positions at another mesh shape."""
+    ra, dec, z = _radecz_dev(radecz)
+    tab, nt = _dist_table_dev(cosmo)
+    geom = _cell_geom(box_center, box_rotvec, box_size, mesh_shape)
+    out = torch.empty((ra.numel(), 3), dtype=torch.float32, device=ra.device)
+    out2 = None if ratio is None else torch.empty_like(out)
+    ratio = None if ratio is None else np.ascontiguousarray(ratio, dtype=np.float64).reshape(3)
+    nbody.get_plan(mesh_shape).call("mcpm_sky2cell_f32", ra, dec, z, ra.numel(), tab, tab[nt:], nt, geom, ratio, out, out2)
+    return out if ratio is None else (out, out2)
+
+
+def box2cell_pos(pos, vel, los, vscale, box_center, box_rotvec, box_size, mesh_shape):
+    """phys2cell_pos(pos + vscale (vel . los) los, ...) as an (N, 3) float32 device tensor (mcpm_box2cell_f32); `vel` may be None.
+    float32 input stays float32 on the way to the device, anything else travels as float64; the arithmetic is float64."""
+    dt = np.float32 if np.asarray(pos).dtype == np.float32 else np.float64
+    p = _up(pos, dt)
+    if p.ndim != 2 or p.shape[1] != 3:
+        raise ValueError("pos must have shape (N, 3)")
+    v = None if vel is None else _up(vel, dt)
+    if v is not None and v.shape != p.shape:
+        raise ValueError("vel must have the shape of pos")
+    geom = _cell_geom(box_center, box_rotvec, box_size, mesh_shape)
+    out = torch.empty((p.shape[0], 3), dtype=torch.float32, device=p.device)
+    nbody.get_plan(mesh_shape).call("mcpm_box2cell_f32", p, v, int(dt is np.float64), p.shape[0], geom,
+                                    np.ascontiguousarray(los, dtype=np.float64).reshape(3), float(vscale), out)
+    return out
+
+
+def footprint(pos, shape, weights=None, order: int = 2, mask=None):
+    """Cells where an object of positive weight has a non-zero assignment weight: `paint(pos, shape, weights, order) > 0` of
+    bricks.py:1045 made exact (mcpm_footprint_u8; the paints here deposit through integer accumulators, where a small positive
+    deposit can round to zero).  uint8 device tensor of `shape`; `mask`: a previous result to add to (chunks)."""
+    shape = tuple(int(s) for s in shape)
+    plan, p, n, mode = nbody._pos_args(pos, shape)
+    if mode != _lib.POS_ABSOLUTE:
+        raise TypeError("footprint takes plain (N, 3) positions")
+    w = None if weights is None else nbody._f32(weights, (n,))
+    acc = mask is not None
+    if acc and (tuple(mask.shape) != shape or mask.dtype != torch.uint8):
+        raise ValueError("mask must be a uint8 tensor of the mesh shape")
+    mask = mask if acc else torch.empty(shape, dtype=torch.uint8, device=p.device)
+    plan.call("mcpm_footprint_u8", p, n, w, int(order), mask, int(acc))
+    return mask
+
+
+def masked_sum(mesh, mask):
+    """(float64 sum of `mesh` over mask != 0, number of such cells), in a fixed order (mcpm_masked_sum_f64)."""
+    m = nbody._f32(mesh)
+    k = torch.as_tensor(mask).to(device=m.device).contiguous()
+    if k.dtype not in (torch.uint8, torch.bool) or k.shape != m.shape:
+        raise ValueError("mask must be a bool or uint8 array of the mesh's shape")
+    out = torch.empty(2, dtype=torch.float64, device=m.device)
+    nbody.get_plan((8, 8, 8)).call("mcpm_masked_sum_f64", m, k, m.numel(), out)
+    s, c = out.cpu().numpy()
+    return float(s), int(c)
+
+
+def _catalog_extent(tables, cosmo, chunk=CATALOG_CHUNK):
+    """(low corner, high corner, weighted size) of checked sky tables, chunk by chunk; objects without WEIGHT count 1."""
+    lo, hi, wsum = np.full(3, np.inf), np.full(3, -np.inf), 0.
+    for piece in _pieces(tables, SKY_KEYS, chunk):
+        l, h, s = sky_extent(cosmo, piece, piece.get('WEIGHT'))
+        lo, hi = np.minimum(lo, l), np.maximum(hi, h)
+        wsum += s if 'WEIGHT' in piece else float(len(piece['RA']))
+    return lo, hi, wsum
+
+
+def _cutsky_box(data, cosmo, cell_budget, padding, box_size, box_center, box_rotvec, chunk, what="data"):
+    """cutsky2config's answer and the weighted size of the catalogue, which the same pass over it yields."""
+    lo, hi, wsum = _catalog_extent(checked_tables(data, SKY_KEYS, what), cosmo, chunk)
+    if not np.all(np.isfinite(lo)):
+        raise ValueError(f"the {what} catalogue is empty")
+    computed = (hi - lo, (lo + hi) / 2, np.zeros(3))
+    provided = (box_size, box_center, box_rotvec)
+    box_size, box_center, box_rotvec = (np.array(prov, dtype=np.float64) if prov is not None else comp
+                                        for prov, comp in zip(provided, computed))
+    final_shape, cell_length = get_mesh_shape(box_size, cell_budget, padding)
+    return final_shape, cell_length, box_center, box_rotvec, wsum
+
+
+def cutsky2config(data, cosmo, cell_budget: float, padding: float = 0., box_size=None, box_center=None, box_rotvec=None,
+                  chunk=CATALOG_CHUNK):
+    """(final_shape, cell_length, box_center, box_rotvec) of the box around a sky catalogue (bricks.py:1015-1026): what is not
+    given comes from the catalogue's bounding box.  box_size may change afterwards, to final_shape * cell_length."""
+    return _cutsky_box(data, cosmo, cell_budget, padding, box_size, box_center, box_rotvec, chunk)[:4]
+
+
+def _weights32(piece):
+    """The paints' weights: the float32 of the WEIGHT column, or the scalar 1."""
+    return _up(piece['WEIGHT'], np.float32) if 'WEIGHT' in piece else 1.
+
+
+def cutsky2selection(data, cosmo, mask_shape, selec_shape, paint_shape, box_size, box_center, box_rotvec, paint_order: int = 2,
+                     interlace_order: int = 2, paint_deconv: bool = True, chunk=CATALOG_CHUNK):
+    """(selec_mesh at selec_shape, mask_mesh at mask_shape) painted from a sky catalogue of randoms (bricks.py:1028-1051); device
+    tensors, float32 and bool.  The selection is normalised to unit mean over its own footprint at selec_shape
+    (mcpm_masked_sum_f64); the mask is the footprint of the same float32 positions scaled to mask_shape."""
+    mask_shape, selec_shape = tuple(int(s) for s in mask_shape), tuple(int(s) for s in selec_shape)
+    ratio = np.divide(mask_shape, selec_shape)
+    spec, fp_selec, fp_mask = None, None, None
+    for piece in _pieces(checked_tables(data, SKY_KEYS, "random"), SKY_KEYS, chunk):
+        pos, pos_mask = sky2cell_pos(cosmo, piece, box_center, box_rotvec, box_size, selec_shape, ratio)
+        w = _weights32(piece)
+        part = nbody.nufft(pos, selec_shape, paint_shape, weights=w, paint_order=paint_order, interlace_order=interlace_order,
+                           paint_deconv=paint_deconv)
+        spec = part if spec is None else spec + part
+        wf = w if torch.is_tensor(w) else None
+        fp_selec = footprint(pos, selec_shape, wf, paint_order, fp_selec)
+        fp_mask = footprint(pos_mask, mask_shape, wf, paint_order, fp_mask)
+    if spec is None:
+        raise ValueError("cutsky2selection: the catalogue is empty")
+    selec_mesh = nbody.irfftn(spec)
+    total, cells = masked_sum(selec_mesh, fp_selec)
+    if cells == 0:
+        raise ValueError("cutsky2selection: no object has a positive weight")
+    selec_mesh /= total / cells
+    return selec_mesh, fp_mask.bool()
+
+
+def cutsky2count(data, cosmo, count_shape, paint_shape, box_size, box_center, box_rotvec, paint_order: int = 2,
+                 interlace_order: int = 2, paint_deconv: bool = True, chunk=CATALOG_CHUNK):
+    """Count mesh at count_shape painted from a sky catalogue (bricks.py:1054-1069); float32 device tensor."""
+    count_shape = tuple(int(s) for s in count_shape)
+    spec = None
+    for piece in _pieces(checked_tables(data, SKY_KEYS), SKY_KEYS, chunk):
+        pos = sky2cell_pos(cosmo, piece, box_center, box_rotvec, box_size, count_shape)
+        part = nbody.nufft(pos, count_shape, paint_shape, weights=_weights32(piece), paint_order=paint_order,
+                           interlace_order=interlace_order, paint_deconv=paint_deconv)
+        spec = part if spec is None else spec + part
+    if spec is None:
+        raise ValueError("cutsky2count: the catalogue is empty")
+    return nbody.irfftn(spec)
+
+
+def fullsky2count(data, cosmo, a_obs: float, los, box_size, box_center, box_rotvec, final_shape, paint_shape, paint_order: int = 2,
+                  interlace_order: int = 2, paint_deconv: bool = True, chunk=CATALOG_CHUNK):
+    """Count mesh at final_shape from cartesian positions in a periodic box (bricks.py:1072-1103); float32 device tensor.  `data`: a
+    dict-like with 'pos' (and optional 'vel', 'WEIGHT'), or any iterable of them, accumulated in Fourier space.  With 'vel', redshift-
+    space distortion at `a_obs` along `los`.  RuntimeError if the mesh does not sum to the weighted number of objects to 1e-5."""
+    final_shape = tuple(int(s) for s in final_shape)
+    vscale = 1. / (a_obs * 100 * float(nbody._Esqr(cosmo, a_obs)) ** .5)      # peculiar velocity -> Mpc/h
+    spec, n_tracers = None, 0.
+    for piece in _pieces(checked_tables(data, ('pos',), optional=('vel',), iterable_ok=True), ('pos',), chunk, optional=('vel',)):
+        pos = box2cell_pos(piece['pos'], piece.get('vel'), los, vscale, box_center, box_rotvec, box_size, final_shape)
+        part = nbody.nufft(pos, final_shape, paint_shape, weights=_weights32(piece), paint_order=paint_order,
+                           interlace_order=interlace_order, paint_deconv=paint_deconv)
+        spec = part if spec is None else spec + part
+        n_tracers += float(np.sum(piece['WEIGHT'], dtype=np.float64)) if 'WEIGHT' in piece else float(len(piece['pos']))
+    if spec is None:
+        raise ValueError("fullsky2count: the catalogue is empty")
+    count_mesh = nbody.irfftn(spec)
+    total = float(count_mesh.sum(dtype=torch.float64))      # nufft applies the final -> paint jacobian: the mesh sums to n_tracers
+    if not abs(total - n_tracers) <= 1e-5 * n_tracers:
+        raise RuntimeError(f"Count mesh sum {total} does not match number of tracers {n_tracers}.")
+    return count_mesh

@@ -74,6 +74,12 @@ class FieldLevelForward:
                 "interlace_order", "lin_kpow")
         return {k: getattr(self, k) for k in keys}
 
+    @classmethod
+    def register_catalog(cls, cell_budget: float, cosmo_fid, data, random=None, **kwargs):
+        """register.register_catalog under the reference's name (model.py:1287-1362): catalogue -> register dict, no model instance needed."""
+        from .register import register_catalog
+        return register_catalog(cell_budget, cosmo_fid, data, random, **kwargs)
+
     # ---- metrics (model.py:1370-1379) ----------------------------------------------------------------------
     def spectrum(self, mesh0, mesh1=None, ells: int | list = 0, kedges: int | float | list = None, include_corners=True):
         """metrics.spectrum with the model's box_size and box_center."""

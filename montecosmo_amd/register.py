@@ -1,7 +1,8 @@
 """The on-disk "register" of a mock (reference: run/register.py:8-18 writes it, montecosmo/model.py:518-553 loads it): ONE
 self-describing file per mock from which `FieldLevelModel(register=path)` takes its geometry, painting parameters, meshes
 and fiducial cosmology.  This module reads and writes that schema and turns it into the arguments of this package's
-`FieldLevelForward` / `FieldLevelLogDensity`.
+`FieldLevelForward` / `FieldLevelLogDensity`.  `register_catalog` produces one here, from a galaxy catalogue and its randoms or from a
+simulation box (the reference's `FieldLevelModel.register_catalog`, model.py:1287-1362); `tools/register_catalog.py` is its command line.
 
 Schema (key: meaning; * = mandatory)
   * cell_length, box_center, box_rotvec      geometry (final_shape = count_mesh.shape)
@@ -157,3 +158,77 @@ def model_arguments(reg, **overrides):
     return dict(forward=fwd, density=density,
                 loc=dict(Omega_m=float(reg["cosmo_fid"]["Omega_m"]), sigma8=float(reg["cosmo_fid"]["sigma8"]), ngbars=ngbar),
                 white_mesh=None if white is None else np.asarray(white))
+
+
+def register_catalog(cell_budget: float, cosmo_fid, data, random=None, box_size=None, box_center=None, box_rotvec=None, a_obs=None,
+                     los=None, padding: float = 0., init_oversamp: float = 3 / 2, paint_oversamp: float = 7 / 4, paint_order: int = 2,
+                     interlace_order: int = 2, paint_deconv: bool = True, kernel_type: str = 'rectangular', chunk=None):
+    """Register a catalogue into the meshes and metadata an inference-ready model needs (model.py:1287-1362):
+
+    * cut sky (`random` given): `data` and `random` are (RA, DEC, Z, WEIGHT) dict-likes, or lists / tuples of them.  The geometry is
+      fitted to the randoms, the selection (painted at init_shape, reshaped to paint_shape) and the footprint mask (final_shape) come
+      from the randoms and the count from the data.  a_obs = None (light cone), curved sky.
+    * full sky (`random` None): `data` holds cartesian 'pos' (and optional 'vel', 'WEIGHT'), as a dict-like or any iterable of them;
+      `box_size` is the periodic box and there is no selection or mask.  With 'vel', redshift-space distortion at `a_obs` along `los`.
+
+    Objects go to the device at most `chunk` at a time (default 2^24).  Returns a dict in this module's schema (host numpy arrays,
+    the reference's keys) for `save_register`.  Wrong combinations, negative or non-finite weights, non-finite coordinates and a 'vel'
+    of another shape than 'pos' raise ValueError (the columns are scanned once, where the catalogue enters), a one-shot iterator on
+    the cut sky TypeError, another kernel_type NotImplementedError -- all before any device work (a lazily read full-sky iterator is
+    checked table by table as it is read)."""
+    from . import bricks, nbody, utils
+    cut_sky = random is not None
+    chunk = bricks.CATALOG_CHUNK if chunk is None else int(chunk)
+    if kernel_type != 'rectangular':
+        raise NotImplementedError("register_catalog paints with kernel_type='rectangular' (nbody.paint itself takes 'kaiser_bessel')")
+    if chunk < 1:
+        raise ValueError("chunk must be a positive number of objects")
+    if not cell_budget > 0 or padding < 0:
+        raise ValueError("cell_budget must be positive and padding non-negative")
+    if cut_sky:
+        if a_obs is not None or los is not None:
+            raise ValueError("For cut-sky catalog, a_obs and los must be None (light-cone, curved-sky)")
+        data, random = bricks.checked_tables(data, bricks.SKY_KEYS, "data"), bricks.checked_tables(random, bricks.SKY_KEYS, "random")
+        curved_sky = True
+        final_shape, cell_length, box_center, box_rotvec, n_randoms = bricks._cutsky_box(
+            random, cosmo_fid, cell_budget, padding, box_size, box_center, box_rotvec, chunk, "random")
+    else:
+        if a_obs is None or los is None or box_size is None or box_center is None:
+            raise ValueError("For full-sky catalog, a_obs, los, box_size, and box_center must be provided")
+        data = bricks.checked_tables(data, ('pos',), "data", optional=('vel',), iterable_ok=True)      # an iterator: checked as it is read
+        box_rotvec = np.zeros(3) if box_rotvec is None else np.asarray(box_rotvec, dtype=np.float64)
+        final_shape, cell_length = bricks.get_mesh_shape(box_size, cell_budget, padding=0.)
+        curved_sky = False
+    paint = dict(paint_order=paint_order, interlace_order=interlace_order, paint_deconv=paint_deconv, chunk=chunk)
+    box_size = np.multiply(final_shape, cell_length)      # box_size update due to rounding and padding
+    init_shape = utils.scale_shape(final_shape, init_oversamp)
+    paint_shape = utils.scale_shape(final_shape, paint_oversamp)
+
+    if cut_sky:
+        selec_mesh, mask_mesh = bricks.cutsky2selection(random, cosmo_fid, mask_shape=final_shape, selec_shape=init_shape,
+                                                        paint_shape=paint_shape, box_size=box_size, box_center=box_center,
+                                                        box_rotvec=box_rotvec, **paint)
+        selec_mesh = nbody.irfftn(utils.chreshape(nbody.rfftn(selec_mesh), utils.r2chshape(paint_shape)))
+        selec_mesh, mask_mesh = selec_mesh.cpu().numpy(), mask_mesh.cpu().numpy()
+        count_mesh = bricks.cutsky2count(data, cosmo_fid, final_shape, paint_shape, box_size=box_size, box_center=box_center,
+                                         box_rotvec=box_rotvec, **paint).cpu().numpy()
+        n_tracers = bricks.weighted_size(data)
+    else:
+        count_mesh = bricks.fullsky2count(data, cosmo_fid, a_obs, los=los, box_size=box_size, box_center=box_center,
+                                          box_rotvec=box_rotvec, final_shape=final_shape, paint_shape=paint_shape, **paint).cpu().numpy()
+        box_center = np.multiply(np.asarray(los, dtype=np.float64), nbody.a2chi(cosmo_fid, a_obs))      # real box_center, coherent with the los
+        n_tracers = float(count_mesh.sum(dtype=np.float64))
+        selec_mesh = mask_mesh = n_randoms = None
+
+    return validate({
+        'cell_length': float(cell_length), 'box_center': np.asarray(box_center), 'box_rotvec': np.asarray(box_rotvec),
+        'init_oversamp': float(init_oversamp), 'paint_oversamp': float(paint_oversamp),
+        'cosmo_fid': {'Omega_m': float(cosmo_fid.Omega_m), 'sigma8': float(cosmo_fid.sigma8)},
+        'count_mesh': count_mesh,
+        'selec_mesh': selec_mesh, 'mask_mesh': mask_mesh,
+        'n_tracers': n_tracers, 'n_randoms': n_randoms,
+        'a_obs': a_obs, 'curved_sky': curved_sky,
+        'paint_order': int(paint_order), 'interlace_order': int(interlace_order),
+        'paint_deconv': bool(paint_deconv), 'kernel_type': kernel_type,
+        'cell_budget': float(cell_budget), 'padding': float(padding),
+    })

@@ -1,5 +1,5 @@
 """Host helpers with the names of montecosmo/utils.py that the PM path uses (utils.py:21-29, :769-782,
-:1163-1168)."""
+:1163-1168, :1186-1210)."""
 import ctypes as C
 
 import numpy as np
@@ -30,6 +30,24 @@ def r2chshape(shape):
 def scale_shape(shape, scale=1.):
     """Valid (even) scaled mesh shape (utils.py:1163-1168)."""
     return tuple(int(2 * np.rint(s * scale / 2)) for s in shape)
+
+
+def radecrad2cart(ra, dec, radius):
+    """ra, dec (degrees) and radius -> cartesian coordinates (..., 3) (utils.py:1186-1196); host float64."""
+    ra, dec = np.deg2rad(np.asarray(ra, dtype=np.float64)), np.deg2rad(np.asarray(dec, dtype=np.float64))
+    x, y, z = np.cos(dec) * np.cos(ra), np.cos(dec) * np.sin(ra), np.sin(dec)
+    return np.moveaxis(np.asarray(radius, dtype=np.float64) * np.stack((x, y, z)), 0, -1)
+
+
+def cart2radecrad(cart):
+    """Cartesian coordinates (..., 3) -> ra in [0, 360], dec in [-90, 90] (degrees) and radius (utils.py:1199-1210); host float64.
+    The origin maps to (0, 0, 0) (safe_div)."""
+    cart = np.asarray(cart, dtype=np.float64)
+    radius = np.linalg.norm(cart, axis=-1)
+    x, y, z = np.moveaxis(cart, -1, 0)
+    ra = np.rad2deg(np.arctan2(y, x)) % 360.
+    dec = np.rad2deg(np.arcsin(np.clip(safe_div(z, radius), -1., 1.)))
+    return ra, dec, radius
 
 
 def _dev(x, dtype):
