@@ -466,6 +466,20 @@ int mcpm_nbody_bf_vjp_f32(mcpm_plan *plan, const float *init_mesh, int n_steps, 
 int mcpm_lik_real_f32(mcpm_plan *plan, int family, int64_t n, const float *obs, const float *count, const float *selec,
                       float selec_scalar, const unsigned char *mask, float s_e, float s_ed, float s_e2, float *count_bar,
                       float *sqsel_bar, double *sums_out);
+/* The same families with the primordial stochastic term and a temperature (model.py:873, :894-895, :905-906, :917-918), and
+   MCPM_LIK_TWO_QUAD: obs ~ TwoQuadGaussian(count, scale1, scale2) (utils.py:541-616), obs = count + scale1 eps1 + scale2 (eps2^2 - 1),
+                      eps2 integrated out by the Gauss-Hermite rule (quad_z, quad_logw): n_quad nodes z_i and log(w_i / sqrt(2 pi)) of
+                      numpy's hermegauss(n_quad) (DEVICE doubles, ascending z as numpy returns them, n_quad even: the rule's symmetry is
+                      used, the upper half is read).  The other families do not read the rule (NULL, 0).
+     scale1 = (|s_e + s_ed delta + s_ep phi| + 1e-9) sqrt(selec) sqrt(temp),  scale2 = s_e2 sqrt(selec);  Poisson rate |count|^(1 / temp).
+   phi (n floats) may be NULL: phi = 0, and phi_bar must be NULL too; else phi_bar (n floats) = d lp / d phi.  temp > 0.
+   sums_out (device, 6 doubles): the five of mcpm_lik_real_f32 and d lp / d s_ep.  With phi NULL and temp = 1 the families of
+   mcpm_lik_real_f32 return what it returns, bit for bit. */
+#define MCPM_LIK_TWO_QUAD 2
+int mcpm_lik_real_phi_f32(mcpm_plan *plan, int family, int64_t n, const float *obs, const float *count, const float *selec,
+                          float selec_scalar, const unsigned char *mask, const float *phi, float s_e, float s_ed, float s_e2, float s_ep,
+                          float temp, const double *quad_z, const double *quad_logw, int n_quad, float *count_bar, float *phi_bar,
+                          float *sqsel_bar, double *sums_out);
 /* 'fourier_gauss' on the plan's mesh (all sides even): obs_rg = cgh2rg(rfftn(count_obs)) (real layout, M floats),
    Y = rfftn(count) (plain half-spectrum); obs_rg[r] ~ Normal(cgh2rg(Y)[r], sigma), sigma = cgh2rg_amp(|s_e + s_k2e k^2 +
    s_kmu2e (k mu)^2|) sqrt(selec), k in h/Mpc from the mode index and the box size (no k table), mu = k . los / |k| (0 at k = 0),
@@ -474,6 +488,10 @@ int mcpm_lik_real_f32(mcpm_plan *plan, int family, int64_t n, const float *obs, 
    (device, 5 doubles): lp, d lp / d s_e, d s_k2e, d s_kmu2e, d lp / d sqrt(selec). */
 int mcpm_lik_fourier_f32(mcpm_plan *plan, const float *Y, const float *obs_rg, float box_x, float box_y, float box_z, float los_x,
                          float los_y, float los_z, float selec, float s_e, float s_k2e, float s_kmu2e, float *Y_bar, double *sums_out);
+/* The same with the scale multiplied by sqrt(temp) (model.py:883); temp = 1 is mcpm_lik_fourier_f32, bit for bit. */
+int mcpm_lik_fourier_temp_f32(mcpm_plan *plan, const float *Y, const float *obs_rg, float box_x, float box_y, float box_z, float los_x,
+                              float los_y, float los_z, float selec, float s_e, float s_k2e, float s_kmu2e, float temp, float *Y_bar,
+                              double *sums_out);
 
 /* ---- host-side float64 growth tables (nbody.py:679-745) ------------------------------------- */
 /* rg2cgh / cgh2rg with norm = "backward" (montecosmo/utils.py:785-921): a real Gaussian tensor (nx, ny, nz), all sizes

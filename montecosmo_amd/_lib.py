@@ -17,7 +17,7 @@ LIB_PATH = os.environ.get("MCPM_LIB") or os.path.join(_HERE, "libmcpm.so")      
 OK = 0
 POS_ABSOLUTE, POS_LATTICE = 0, 1
 AP_NONE, AP_AUTO, AP_PARAM = 0, 1, 2
-LIK_SHASH, LIK_POISSON = 0, 1
+LIK_SHASH, LIK_POISSON, LIK_TWO_QUAD = 0, 1, 2
 FD_INF, FD_2, FD_4 = 0, 2, 4
 
 
@@ -103,7 +103,10 @@ SIGNATURES = {
     "mcpm_kaiser_sky_tables_vjp_f32": (C.c_int, [_plan, _f32p, _f64p, C.c_int, _d64p, C.c_int, C.c_int, C.c_double, _f32p, _d64p]),
     "mcpm_lik_real_f32": (C.c_int, [_plan, C.c_int, C.c_int64, _f32p, _f32p, _f32p, C.c_float, _u8p, C.c_float, C.c_float, C.c_float,
                                     _f32p, _f32p, _d64p]),
+    "mcpm_lik_real_phi_f32": (C.c_int, [_plan, C.c_int, C.c_int64, _f32p, _f32p, _f32p, C.c_float, _u8p, _f32p] + [C.c_float] * 5
+                                       + [_d64p, _d64p, C.c_int, _f32p, _f32p, _f32p, _d64p]),
     "mcpm_lik_fourier_f32": (C.c_int, [_plan, _f32p, _f32p] + [C.c_float] * 10 + [_f32p, _d64p]),
+    "mcpm_lik_fourier_temp_f32": (C.c_int, [_plan, _f32p, _f32p] + [C.c_float] * 11 + [_f32p, _d64p]),
     "mcpm_lpt_combine_f32": (C.c_int, [_plan, _f32p, _f32p, _f32p, C.c_int64, _f32p, _f32p]),
     "mcpm_lpt_combine_vjp_f32": (C.c_int, [_plan, _f32p, _f32p, _f32p, C.c_int64, _f32p, _f32p, _f32p]),
     "mcpm_observe_pos_f32": (C.c_int, [_plan, _f32p, _f32p, _f32p, C.c_int64, C.c_int, C.POINTER(C.c_float), C.c_int,

@@ -1,5 +1,6 @@
-// The likelihoods of the field-level model besides 'quad_gauss' (montecosmo/model.py:872-886, :911-932) with their hand-derived
-// gradients: one pass over the final mesh ('shash', 'poisson') or over its half-spectrum ('fourier_gauss').  Elementwise, no LDS
+// The likelihoods of the field-level model besides 'quad_gauss' (montecosmo/model.py:872-886, :903-932) with their hand-derived
+// gradients: one pass over the final mesh ('shash', 'poisson', 'two_quad_gauss') or over its half-spectrum ('fourier_gauss'); the
+// primordial term s_ep phi of scale1 and the temperature of the tempered likelihood in lik_real_phi_kernel.  Elementwise, no LDS
 // tiling.  Every scalar is a float64 grid sum with the fixed-order fold of reduce_dev.h: bitwise the same call after call.
 #include "mcpm_internal.h"
 #include "reduce_dev.h"
@@ -142,6 +143,97 @@ __global__ __launch_bounds__(256) void lik_real_kernel(int64_t n, const float *_
     block_partial<5>(v, part, gridDim.x, blockIdx.x);
 }
 
+// TwoQuadGaussian(loc, scale1 = b, scale2 = a).log_prob(obs) (utils.py:541-616): obs = loc + b eps1 + a (eps2^2 - 1) with eps2 integrated
+// out by the Gauss-Hermite rule the caller hands over,
+//     lp = logsumexp_i [log wn_i - 0.5 r_i^2] - log b - log(2 pi) / 2,   r_i = (obs - loc - a (z_i^2 - 1)) / b.
+// The rule is symmetric and r_i reads z_i^2 alone, so the upper half of the nodes is visited (gz, glw point at it; nh nodes) and the
+// doubled weight is one log 2 at the end.  The exponents are float64 throughout: log wn_i spans 1e-1 .. 1e-46 and r_i^2 reaches
+// hundreds, so the difference of the two would keep four digits in float32.  Two sweeps -- the largest exponent, then the weights
+// p_i = exp(e_i - max) with their three moments -- recompute e_i (three float64 FMAs) instead of holding nh doubles per lane: the node
+// index is the same in every lane, the table comes through scalar loads, and nothing is indexed at run time (no scratch).
+// Gradients with the softmax weights: d/d loc = sum p_i r_i / b,  d/d b = sum p_i (r_i^2 - 1) / b,  d/d a = sum p_i r_i (z_i^2 - 1) / b.
+__device__ __forceinline__ Term two_quad_term(float obs, float loc, float b, float a, const double *__restrict__ gz,
+                                              const double *__restrict__ glw, int nh) {
+    const double bd = (double)b, u = ((double)obs - (double)loc) / bd, k = (double)a / bd;
+    double m = -(double)INFINITY;
+    for (int i = 0; i < nh; ++i) {
+        const double r = u - k * (gz[i] * gz[i] - 1.);
+        m = fmax(m, glw[i] - 0.5 * r * r);
+    }
+    double s0 = 0., s1 = 0., s2 = 0., s3 = 0.;
+    for (int i = 0; i < nh; ++i) {
+        const double q = gz[i] * gz[i] - 1., r = u - k * q, p = exp(glw[i] - 0.5 * r * r - m);
+        s0 += p;
+        s1 += p * r;
+        s2 += p * r * r;
+        s3 += p * r * q;
+    }
+    Term T;
+    T.lp = m + log(s0) + 0.69314718055994531 - log(bd) - LIK_HALF_LOG2PI_D;
+    T.g_loc = (float)(s1 / s0 / bd);
+    T.g_b = (float)((s2 / s0 - 1.) / bd);
+    T.g_a = (float)(s3 / s0 / bd);
+    return T;
+}
+
+// The real-space families with the primordial term and a temperature (model.py:873, :894-895, :905-906, :917-918):
+//     scale1 = (|s_e + s_ed delta + s_ep phi| + 1e-9) sqrt(selec) sqrt(temp),   scale2 = s_e2 sqrt(selec),   Poisson rate |count|^(1 / temp).
+// family 0 'shash', 1 'poisson', 2 'two_quad_gauss'.  Sums (6 rows): those of lik_real_kernel and d/d s_ep.  phi NULL: phi = 0 and no
+// phi_bar.  'shash' repeats lik_real_kernel's arithmetic expression by expression, with the factors of the temperature multiplied on
+// (st = 1 leaves every float as it is) and the phi term added under `if (phi)`: at phi NULL, temp 1 it returns lik_real_kernel's bits.
+template <int FAMILY>
+__global__ __launch_bounds__(256) void lik_real_phi_kernel(int64_t n, const float *__restrict__ obs, const float *__restrict__ count,
+                                                           const float *__restrict__ selec, float selec_scalar,
+                                                           const unsigned char *__restrict__ mask, const float *__restrict__ phi, float s_e,
+                                                           float s_ed, float s_e2, float s_ep, float temp, const double *__restrict__ gz,
+                                                           const double *__restrict__ glw, int nh, float *__restrict__ count_bar,
+                                                           float *__restrict__ phi_bar, float *__restrict__ sqsel_bar,
+                                                           double *__restrict__ part) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    double v[6] = {0., 0., 0., 0., 0., 0.};
+    if (i < n) {
+        const bool on = mask ? mask[i] != 0 : true;
+        const float o = on ? obs[i] : 0.f, c = on ? count[i] : 0.f;
+        float S = selec ? selec[i] : selec_scalar;
+        S = on ? S : 1.f;
+        double lp;
+        float cb, pb = 0.f, qb = 0.f, ge = 0.f, ged = 0.f, ge2 = 0.f, gep = 0.f;
+        if (FAMILY != 1) {
+            const float st = sqrtf(temp), ph = (phi && on) ? phi[i] : 0.f;
+            const float q = sqrtf(S), delta = c / S - 1.f;
+            float lin = s_e + s_ed * delta;
+            if (phi) lin += s_ep * ph;
+            const float al = fabsf(lin) + 1e-9f;
+            const Term T = FAMILY == 0 ? shash_term(o, c, al * q * st, s_e2 * q) : two_quad_term(o, c, al * q * st, s_e2 * q, gz, glw, nh);
+            const float sg = (lin > 0.f ? 1.f : (lin < 0.f ? -1.f : 0.f)) * q * st, gl = T.g_b * sg;      // d lp / d lin
+            lp = T.lp;
+            cb = T.g_loc + gl * s_ed / S;
+            ge = gl, ged = gl * delta, ge2 = T.g_a * q, gep = gl * ph;
+            pb = gl * s_ep;
+            const float alt = al * st;      // d scale1 / d q
+            qb = T.g_b * alt + T.g_a * s_e2 - 2.f * gl * s_ed * c / (S * q);      // d delta / d q = -2 count / q^3
+        } else {
+            // Poisson(|count|^(1 / temp)).  temp = 1 keeps lik_real_kernel's expressions (and bits); else log(rate) = log|count| / temp
+            // in float64 and d rate / d |count| = rate / (temp |count|).
+            const float ac = fabsf(c);
+            if (ac > 0.f) {
+                const bool unit = temp == 1.f;
+                const double ll = unit ? log((double)ac) : log((double)ac) / (double)temp, lamd = unit ? (double)ac : exp(ll);
+                lp = (o == 0.f ? 0. : (double)o * ll) - lamd - lgamma((double)o + 1.);
+                cb = (c > 0.f ? 1.f : -1.f) * (unit ? o / ac - 1.f : (o - (float)lamd) / (temp * ac));
+            } else {
+                lp = o > 0.f ? -(double)INFINITY : (o == 0.f ? 0. : (double)NAN);
+                cb = 0.f;
+            }
+        }
+        count_bar[i] = on ? cb : 0.f;
+        if (phi_bar) phi_bar[i] = on ? pb : 0.f;
+        if (sqsel_bar) sqsel_bar[i] = on ? qb : 0.f;
+        if (on) v[0] = lp, v[1] = (double)ge, v[2] = (double)ged, v[3] = (double)ge2, v[4] = (double)qb, v[5] = (double)gep;
+    }
+    block_partial<6>(v, part, gridDim.x, blockIdx.x);
+}
+
 __device__ __forceinline__ float lik_kfreq(int i, int n) {      // fftfreq: index n/2 of a full axis is -n/2
     const int s = (i < (n + 1) / 2) ? i : i - n;
     return LIK_TWO_PI * (float)s;
@@ -153,10 +245,11 @@ __device__ __forceinline__ float lik_kfreq(int i, int n) {      // fftfreq: inde
 // the two real elements the mode pairs with, cgh2rg's rule (cgh2rg_read) says whether that element really reads this mode and with which
 // weight.  A mode that no element reads -- the redundant mirror half of the kz = 0 and kz = nz/2 faces -- writes zero.  So every
 // element of Y_bar is written exactly once, by its own thread: no atomic, no zero fill.
-// Sums (5 rows): lp, d/d s_e, d/d s_k2e, d/d s_kmu2e, d/d sqrt(selec).
+// Sums (5 rows): lp, d/d s_e, d/d s_k2e, d/d s_kmu2e, d/d sqrt(selec).  A temperature (model.py:883) multiplies sigma by sqrt(temp): the
+// caller folds that factor into `sqsel` and passes it again as `q4`, the factor the last sum still lacks (1 at temp = 1: the same bits).
 __global__ __launch_bounds__(256) void lik_fourier_kernel(int nx, int ny, int nz, float bx, float by, float bz, float lx, float ly, float lz,
                                                           const float2 *__restrict__ Y, const float *__restrict__ obs_rg, float sqsel,
-                                                          float s_e, float s_k2e, float s_kmu2e, float2 *__restrict__ Y_bar,
+                                                          float s_e, float s_k2e, float s_kmu2e, float q4, float2 *__restrict__ Y_bar,
                                                           double *__restrict__ part) {
     const int nzc = nz / 2 + 1;
     const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x, Mh = (int64_t)nx * ny * nzc;
@@ -193,17 +286,17 @@ __global__ __launch_bounds__(256) void lik_fourier_kernel(int nx, int ny, int nz
             v[1] += (double)(gs * sg);
             v[2] += (double)(gs * sg * kk);
             v[3] += (double)(gs * sg * kl2);
-            v[4] += (double)(gs * al);
+            v[4] += (double)(gs * al * q4);
         }
         Y_bar[idx] = make_float2(yb[0], yb[1]);
     }
     block_partial<5>(v, part, gridDim.x, blockIdx.x);
 }
 
-int lik_fold(mcpm_plan *p, double *P, double *Q, unsigned *ticket, unsigned R, unsigned nb, double *sums_out) {
+int lik_fold(mcpm_plan *p, double *P, double *Q, unsigned *ticket, unsigned R, unsigned nb, double *sums_out, int K = 5) {
     DetOuts o{};
-    for (int k = 0; k < 5; ++k) o.p[k] = sums_out + k;
-    det_fold_kernel<<<R, 256, 0, p->stream>>>(P, nb, 5, Q, ticket, 1.0, o);
+    for (int k = 0; k < K; ++k) o.p[k] = sums_out + k;
+    det_fold_kernel<<<R, 256, 0, p->stream>>>(P, nb, K, Q, ticket, 1.0, o);
     return MCPM_OK;
 }
 
@@ -231,10 +324,46 @@ int mcpm_lik_real_f32(mcpm_plan *p, int family, int64_t n, const float *obs, con
     return MCPM_OK;
 }
 
-int mcpm_lik_fourier_f32(mcpm_plan *p, const float *Y, const float *obs_rg, float box_x, float box_y, float box_z, float los_x, float los_y,
-                         float los_z, float selec, float s_e, float s_k2e, float s_kmu2e, float *Y_bar, double *sums_out) {
+int mcpm_lik_real_phi_f32(mcpm_plan *p, int family, int64_t n, const float *obs, const float *count, const float *selec, float selec_scalar,
+                          const unsigned char *mask, const float *phi, float s_e, float s_ed, float s_e2, float s_ep, float temp,
+                          const double *quad_z, const double *quad_logw, int n_quad, float *count_bar, float *phi_bar, float *sqsel_bar,
+                          double *sums_out) {
     if (!p) return MCPM_E_ARG;
-    MCPM_REQUIRE(p, Y && obs_rg && Y_bar && sums_out && box_x > 0.f && box_y > 0.f && box_z > 0.f && selec > 0.f, MCPM_E_ARG,
+    MCPM_REQUIRE(p, n > 0 && n < ((int64_t)1 << 39) && obs && count && count_bar && sums_out && temp > 0.f, MCPM_E_ARG,
+                 "mcpm_lik_real_phi_f32: bad argument");
+    MCPM_REQUIRE(p, family == MCPM_LIK_SHASH || family == MCPM_LIK_POISSON || family == MCPM_LIK_TWO_QUAD, MCPM_E_ARG,
+                 "mcpm_lik_real_phi_f32: unknown family");
+    MCPM_REQUIRE(p, !phi == !phi_bar, MCPM_E_ARG, "mcpm_lik_real_phi_f32: phi and phi_bar go together");
+    MCPM_REQUIRE(p, family != MCPM_LIK_TWO_QUAD || (quad_z && quad_logw && n_quad >= 2 && n_quad <= 512 && !(n_quad & 1)), MCPM_E_ARG,
+                 "mcpm_lik_real_phi_f32: two_quad_gauss needs a symmetric rule with an even number of nodes");
+    double *P, *Q;
+    unsigned *ticket, R;
+    const unsigned nb = (unsigned)((n + 255) / 256);
+    const int nh = n_quad / 2;
+    StageTimer st_(p, ST_LPT, (family == MCPM_LIK_SHASH ? 400.0 : family == MCPM_LIK_POISSON ? 40.0 : 60.0 * nh) * n);
+    MCPM_TRY(mcpm_det_scratch(p, 6, nb, &P, &Q, &ticket, &R));
+#define LIK_PHI_LAUNCH(F)                                                                                                                  \
+    lik_real_phi_kernel<F><<<nb, 256, 0, p->stream>>>(n, obs, count, selec, selec_scalar, mask, phi, s_e, s_ed, s_e2, s_ep, temp,         \
+                                                      quad_z ? quad_z + nh : nullptr, quad_logw ? quad_logw + nh : nullptr, nh, count_bar, \
+                                                      phi_bar, sqsel_bar, P)
+    if (family == MCPM_LIK_SHASH)
+        LIK_PHI_LAUNCH(0);
+    else if (family == MCPM_LIK_POISSON)
+        LIK_PHI_LAUNCH(1);
+    else
+        LIK_PHI_LAUNCH(2);
+#undef LIK_PHI_LAUNCH
+    MCPM_LAUNCH_CHECK(p, "lik_real_phi_kernel");
+    lik_fold(p, P, Q, ticket, R, nb, sums_out, 6);
+    MCPM_LAUNCH_CHECK(p, "det_fold_kernel");
+    return MCPM_OK;
+}
+
+int mcpm_lik_fourier_temp_f32(mcpm_plan *p, const float *Y, const float *obs_rg, float box_x, float box_y, float box_z, float los_x,
+                              float los_y, float los_z, float selec, float s_e, float s_k2e, float s_kmu2e, float temp, float *Y_bar,
+                              double *sums_out) {
+    if (!p) return MCPM_E_ARG;
+    MCPM_REQUIRE(p, Y && obs_rg && Y_bar && sums_out && box_x > 0.f && box_y > 0.f && box_z > 0.f && selec > 0.f && temp > 0.f, MCPM_E_ARG,
                  "mcpm_lik_fourier_f32: bad argument");
     MCPM_REQUIRE(p, !p->g.xslab, MCPM_E_UNSUPPORTED, "mcpm_lik_fourier_f32: not slab-decomposed");
     const int nx = p->g.nx, ny = p->g.ny, nz = p->g.nz;
@@ -244,12 +373,19 @@ int mcpm_lik_fourier_f32(mcpm_plan *p, const float *Y, const float *obs_rg, floa
     const unsigned nb = (unsigned)((p->Mh + 255) / 256);
     StageTimer st_(p, ST_KSPACE, 24.0 * p->Mh);
     MCPM_TRY(mcpm_det_scratch(p, 5, nb, &P, &Q, &ticket, &R));
-    lik_fourier_kernel<<<nb, 256, 0, p->stream>>>(nx, ny, nz, box_x, box_y, box_z, los_x, los_y, los_z, (const float2 *)Y, obs_rg, sqrtf(selec),
-                                                  s_e, s_k2e, s_kmu2e, (float2 *)Y_bar, P);
+    // sqrt(selec temp) rounded once (it enters every mode alike, so its rounding is a coherent error of the sums); temp = 1: sqrtf(selec)
+    const float sq = (float)sqrt((double)selec * (double)temp);
+    lik_fourier_kernel<<<nb, 256, 0, p->stream>>>(nx, ny, nz, box_x, box_y, box_z, los_x, los_y, los_z, (const float2 *)Y, obs_rg, sq, s_e,
+                                                  s_k2e, s_kmu2e, sqrtf(temp), (float2 *)Y_bar, P);
     MCPM_LAUNCH_CHECK(p, "lik_fourier_kernel");
     lik_fold(p, P, Q, ticket, R, nb, sums_out);
     MCPM_LAUNCH_CHECK(p, "det_fold_kernel");
     return MCPM_OK;
+}
+
+int mcpm_lik_fourier_f32(mcpm_plan *p, const float *Y, const float *obs_rg, float box_x, float box_y, float box_z, float los_x, float los_y,
+                         float los_z, float selec, float s_e, float s_k2e, float s_kmu2e, float *Y_bar, double *sums_out) {
+    return mcpm_lik_fourier_temp_f32(p, Y, obs_rg, box_x, box_y, box_z, los_x, los_y, los_z, selec, s_e, s_k2e, s_kmu2e, 1.f, Y_bar, sums_out);
 }
 
 }  // extern "C"

@@ -6,11 +6,14 @@ Built branch (everything else stays in the reference): latents with a Normal pri
 reparametrisation `base = name_ * scale_fid + loc_fid` (bricks.py:270-276); initial conditions `white_mesh_ ~ N(0, scale)`
 per cell with the 'fourier' (rg2cgh) or 'real' (rfftn) preconditioning at unit scale, or the reference's default 'kaiser'
 preconditioning (rg2cgh with the per-mode posterior width of the fiducial linear Kaiser model; model.py:1127-1148);
-`evolve`; the 'quad_gauss' likelihood (model.py:852-866, :893-908) with phi = 0, an optional selection mesh (paint_shape),
+`evolve`; the 'quad_gauss' likelihood (model.py:852-870, :893-908), an optional selection mesh (paint_shape),
 an optional mask over the final cells and radial shells with their own (fixed) mean densities:
     count = rc * irfftn(chreshape(rfftn(gxy_mesh * selec_mesh), final_shape)),   rc = ngbars[shell(r)] cell^3 per cell
     selec = |rc * irfftn(chreshape(rfftn(selec_mesh), final_shape))|  (or mean(ngbars) cell^3 without a selection mesh)
-    delta = count / selec - 1;   obs[mask] ~ QuadGaussian(count, (|s_e + s_ed delta| + 1e-9) sqrt(selec), s_e2 sqrt(selec)).
+    delta = count / selec - 1;   phi = irfftn(chreshape(rfftn(phi of `evolve`), final_shape)) with png_type set, else 0
+    scale1 = (|s_e + s_ed delta + s_ep phi| + 1e-9) sqrt(selec) sqrt(temp),   scale2 = s_e2 sqrt(selec)
+    obs[mask] ~ QuadGaussian(count, scale1, scale2).
+temp = `temp_lik` of `logdensity_and_grad`, the temperature of the tempered likelihood (model.py:840; 1 = the posterior itself).
 Bounded latents (`low` / `high` in their config) use the reference's detruncated truncated-normal parametrisation
 (utils.py:189-226, :267-311) within |x| < 12 sigma; latents without `loc` / `scale` have a uniform prior on [low, high] in the
 same parametrisation (DetruncUnif, utils.py:314-353).
@@ -18,11 +21,12 @@ same parametrisation (DetruncUnif, utils.py:314-353).
 Other likelihoods (`lik_type`; value and gradient in one HIP kernel each, csrc/likelihood.hip, on the same count / selec):
     'shash'         obs[mask] ~ SinhArcsinh(count, sqrt(scale1^2 + 2 scale2^2), 3.540 scale2 / scale1, 1 + 5.884 (scale2 / scale1)^2) with the
                     scales of 'quad_gauss' (model.py:911-932; the default of the reference's drivers)
-    'poisson'       obs[mask] ~ Poisson(|count|) (model.py:872-873)
-    'fourier_gauss' cgh2rg(rfftn(obs)) ~ Normal(cgh2rg(rfftn(count)), cgh2rg_amp(|s_e + s_k2e k^2 + s_kmu2e (k mu)^2|) sqrt(selec)), full sky and
-                    scalar selection only (model.py:875-886).
-Not built: 'two_quad_gauss' (a 64-node quadrature), the s_ep * phi term of scale1 (phi would have to be carried out of `evolve`), temp != 1;
-'quad_gauss' itself stays on its torch path.
+    'two_quad_gauss' obs[mask] ~ TwoQuadGaussian(count, scale1, scale2): obs = count + scale1 eps1 + scale2 (eps2^2 - 1) with independent
+                    eps1, eps2, its density by the 64-node Gauss-Hermite rule of the reference (model.py:903-909, utils.py:541-616)
+    'poisson'       obs[mask] ~ Poisson(|count|^(1 / temp)) (model.py:872-873)
+    'fourier_gauss' cgh2rg(rfftn(obs)) ~ Normal(cgh2rg(rfftn(count)), cgh2rg_amp(|s_e + s_k2e k^2 + s_kmu2e (k mu)^2|) sqrt(selec) sqrt(temp)), full
+                    sky and scalar selection only (model.py:875-886).
+'quad_gauss' itself stays on its torch path.  Not built: the tempered prior `temp_prior` (`samp2base(temp=)`, model.py:640-679).
 
 The gradient is hand-derived end to end: elementwise likelihood / prior terms here (device tensors), the mesh and
 particle operators through their `*_vjp` twins -- no autodiff framework.
@@ -31,9 +35,10 @@ particle operators through their `*_vjp` twins -- no autodiff framework.
     1. `_prior`: every latent -- scalars and the per-shell ngbars alike, and `base_params` -- through `latent_log_prob_and_grad`, which picks
        uniform / truncated normal / normal from the latent's config; a saturated tail ends the call here with -inf and a zero gradient.
     2. `_forward`: white field -> transfer -> `evolve` -> mean counts `cm` and selection on the final mesh; `mean_counts` is this stage alone.
-    3. one likelihood method (`_lik_quad_gauss`, `_lik_hip`): (base, forward result, need_grad) -> (lp, cm_bar, stoch_bar, rcounts_bar or None).
+    3. one likelihood method (`_lik_quad_gauss`, `_lik_hip`): (base, forward result, need_grad) -> (lp, cm_bar, stoch_bar, rcounts_bar or
+       None); the forward result carries the temperature in (`temp`) and the cotangent of the final-mesh phi out (`phi_bar`).
        A new likelihood is one more such method.  Each keeps its own closed form of the shell gradient; `_per_shell` is the shared plumbing.
-    tail: gxy_bar = cm_bar rc -> `_down_vjp` -> selection -> `evolve_vjp` -> white-field adjoint -> `_base_bar` chained to the latents.
+    tail: gxy_bar = cm_bar rc -> `_down_vjp` -> selection -> `evolve_vjp` (with phi_bar) -> white-field adjoint -> `_base_bar` chained to the latents.
 """
 from __future__ import annotations
 
@@ -209,16 +214,21 @@ class FieldLevelLogDensity:
                (bricks.PNG_KEYS: fNL, fNL_bp, fNL_bpd, fNL_bpd2, fNL_bps2, fNL_bn2p) may appear in either; a missing one is
                fixed at 0.  They reach the model only when `fwd.png_type` is set.  The Alcock-Paczynski parameters alpha_iso, alpha_ap
                (bricks.AP_KEYS; the reference's prior: truncated normal, loc 1, scale 0.1, low 0, model.py:189-204) may appear in
-               either as well; a missing one is fixed at 1.  They are read only when `fwd.ap_auto is False`.  The stochastic term s_ep * phi of the
-               reference's likelihood (model.py:894) is not built.
+               either as well; a missing one is fixed at 1.  They are read only when `fwd.ap_auto is False`.  s_ep, the coefficient of the
+               primordial stochastic term s_ep * phi of scale1 (model.py:894), may appear in either; a missing one is fixed at 0, and a
+               sampled one takes the reference's prior for the entries its config leaves out (S_EP_LATENT; model.py:248-253).  It is read
+               by 'quad_gauss', 'shash' and 'two_quad_gauss' when `fwd.png_type` is set (else phi = 0); the Kaiser model defines no phi.
     make_cosmo(base) -> cosmology object (default: Planck18 with Omega_c = Omega_m - Omega_b and sigma8)
     """
 
     COSMO = ("Omega_m", "sigma8")
     STOCH = ("s_e", "s_ed", "s_e2")
     # stochastic parameters each likelihood reads; one it does not read need not be supplied, and gets a zero likelihood gradient if sampled
-    LIK_STOCH = {"quad_gauss": STOCH, "shash": STOCH, "fourier_gauss": ("s_e", "s_k2e", "s_kmu2e"), "poisson": ()}
-    ALL_STOCH = ("s_e", "s_ed", "s_e2", "s_k2e", "s_kmu2e")
+    LIK_STOCH = {"quad_gauss": STOCH, "shash": STOCH, "two_quad_gauss": STOCH, "fourier_gauss": ("s_e", "s_k2e", "s_kmu2e"), "poisson": ()}
+    ALL_STOCH = ("s_e", "s_ed", "s_e2", "s_ep", "s_k2e", "s_kmu2e")
+    PHI_LIKS = ("quad_gauss", "shash", "two_quad_gauss")      # the families whose scale1 has the term s_ep * phi
+    S_EP_LATENT = dict(loc=0., scale=1e5, loc_fid=0., scale_fid=1e2)      # model.py:248-253
+    N_QUAD = 64      # nodes of the Gauss-Hermite rule of 'two_quad_gauss' (utils.py:582)
 
     def __init__(self, fwd, count_obs, latents, fixed, precond="fourier", make_cosmo=None, selec_mesh=None, mask_mesh=None,
                  redges=None, n_rbins=None, lik_type="quad_gauss"):
@@ -237,6 +247,12 @@ class FieldLevelLogDensity:
             raise ValueError("Fourier likelihood takes a scalar selection: the per-mode scale does not broadcast with a selection mesh")
         self.fwd, self.precond, self.lik_type = fwd, precond, lik_type
         latents = dict(latents)
+        if "s_ep" in latents:
+            latents["s_ep"] = dict(self.S_EP_LATENT, **{k: v for k, v in latents["s_ep"].items() if v is not None})
+        # s_ep is read (and has a likelihood gradient) only where there is a phi: a real-space family on a model with png_type
+        self.reads_phi = lik_type in self.PHI_LIKS and fwd.png_type is not None
+        if lik_type in self.PHI_LIKS and ("s_ep" in latents or float(fixed.get("s_ep", 0.)) != 0.) and fwd.evolution == "kaiser":
+            raise ValueError("s_ep needs the phi of an 'lpt' or 'nbody' evolution: the Kaiser model defines none (model.py:690-696, :837)")
         self._ngb_conf = latents.pop("ngbars", None)
         self._n_rbins = n_rbins
         self.latents = {k: dict({"low": -math.inf, "high": math.inf}, **{kk: float(vv) for kk, vv in v.items() if vv is not None})
@@ -261,6 +277,9 @@ class FieldLevelLogDensity:
         if lik_type == "fourier_gauss":      # the observation in the real layout, once (model.py:885 applied to the data)
             self.los_fid = fwd.los_cell()
             self.obs_rg = cgh2rg(nbody.rfftn(self.count_obs))
+        if lik_type == "two_quad_gauss":      # nodes and log weights of E_{N(0,1)}[f] ~ sum wn_i f(z_i), host float64 (utils.py:589-591)
+            z, w = np.polynomial.hermite_e.hermegauss(self.N_QUAD)
+            self.quad = torch.from_numpy(np.stack([z, np.log(w) - 0.5 * LOG2PI])).to(self.count_obs.device)
 
     @staticmethod
     def _planck(base):
@@ -499,10 +518,11 @@ class FieldLevelLogDensity:
         return float(-0.5 * LOG2PI * w.numel() - self.scale.double().log().sum() - 0.5 * ((w / self.scale).double() ** 2).sum())
 
     # ---- stage 2: forward model up to the mean counts --------------------------------------------------------------------------------
-    def _forward(self, base, white_mesh_, need_ctx=False):
-        """What every likelihood is evaluated on (model.py:850-866): gxy (the galaxy mesh of `evolve`; ctx: its context when `need_ctx`),
+    def _forward(self, base, white_mesh_, need_ctx=False, need_phi=False):
+        """What every likelihood is evaluated on (model.py:850-870): gxy (the galaxy mesh of `evolve`; ctx: its context when `need_ctx`),
         rc (per-cell count multiplier from the shells' mean densities), dn (gxy times the selection mesh, brought to the final mesh),
-        cm = dn rc (the mean counts) and selec (a mesh with a selection mesh, else the float mean(rcounts))."""
+        cm = dn rc (the mean counts), selec (a mesh with a selection mesh, else the float mean(rcounts)) and, with `need_phi`, phi on the
+        final mesh where the likelihood reads it (a real-space family, png_type set, s_ep sampled or fixed away from 0), else None."""
         fwd = self.fwd
         w = nbody._f32(white_mesh_, fwd.init_shape)
         white = (nbody.rfftn(w) if self.precond == "real" else rg2cgh(w)) * self.transfer
@@ -512,13 +532,15 @@ class FieldLevelLogDensity:
         if need_ctx:
             # Omega_m sampled: the forward model makes the two evaluations of the growth-table Jacobian as soon as it has queued its kernels
             fwd.cosmo_fd_params = ("Omega_m",) if "Omega_m" in self.latents else None
-        out = fwd.evolve(self.make_cosmo(base), {k: base[k] for k in bricks.BIAS_KEYS}, white, return_ctx=need_ctx, **kw)
-        gxy, ctx = out if need_ctx else (out, None)
+        need_phi = need_phi and self.reads_phi and ("s_ep" in self.latents or float(base.get("s_ep", 0.)) != 0.)
+        out = fwd.evolve(self.make_cosmo(base), {k: base[k] for k in bricks.BIAS_KEYS}, white, return_ctx=need_ctx or need_phi, **kw)
+        gxy, ctx = out if (need_ctx or need_phi) else (out, None)
         rcounts = np.atleast_1d(np.asarray(base["ngbars"], dtype=np.float64)) * fwd.cell_length ** 3
         rc = torch.from_numpy(np.append(rcounts, 1.0).astype(np.float32)).to(gxy.device)[self.shell]
         selec = float(rcounts.mean()) if self.sel_down is None else (self.sel_down * rc).abs()
         dn = self._down(gxy if self.selec_mesh is None else gxy * self.selec_mesh)
-        return SimpleNamespace(gxy=gxy, ctx=ctx, rc=rc, dn=dn, cm=dn * rc, selec=selec)
+        phi = fwd.phi_final(ctx.phi).contiguous() if need_phi else None      # model.py:868-869
+        return SimpleNamespace(gxy=gxy, ctx=ctx, rc=rc, dn=dn, cm=dn * rc, selec=selec, phi=phi, phi_bar=None, temp=1.)
 
     def mean_counts(self, sample):
         """(count, selec) of the likelihood at `sample` (model.py:850-866): the mean counts on the final mesh, and the selection there (a mesh
@@ -526,44 +548,49 @@ class FieldLevelLogDensity:
         f = self._forward(self.base_params(sample), sample["white_mesh_"])
         return f.cm, f.selec
 
-    # ---- stage 3: likelihoods.  Each: (base, f = _forward's result, need_grad) -> (lp, cm_bar = d lp / d cm at fixed selec, the cotangents
-    # of the stochastic parameters, rcounts_bar = d lp / d rcounts per shell through count AND selec, or None with fixed ngbars); with
-    # need_grad = False only lp is formed and the rest is None ---------------------------------------------------------------------------
+    # ---- stage 3: likelihoods.  Each: (base, f = _forward's result with f.temp = temp_lik, need_grad) -> (lp, cm_bar = d lp / d cm at fixed selec, the
+    # cotangents of the stochastic parameters, rcounts_bar = d lp / d rcounts per shell through count AND selec, or None with fixed ngbars),
+    # and f.phi_bar = d lp / d f.phi where there is a phi; with need_grad = False only lp is formed and the rest is None -----------------
     def _per_shell(self, cell_bar):
         """A per-cell cotangent summed over each radial shell (float64 device tensor; the cells in no shell are dropped)."""
         return torch.bincount(self.shell.reshape(-1), weights=cell_bar.double().reshape(-1), minlength=self.n_rbins + 1)[:self.n_rbins]
 
     def _lik_hip(self, base, f, need_grad):
-        """'shash', 'poisson' or 'fourier_gauss': value, mesh cotangents and float64 sums from one kernel (csrc/likelihood.hip).  The kernel
-        gives count_bar at fixed selec and sqsel_bar = d lp / d sqrt(selec) at fixed count (per cell for the real-space families, its sum in
-        sums[4]); the shells get both."""
+        """'shash', 'two_quad_gauss', 'poisson' or 'fourier_gauss': value, mesh cotangents and float64 sums from one kernel
+        (csrc/likelihood.hip).  The kernel gives count_bar at fixed selec and sqsel_bar = d lp / d sqrt(selec) at fixed count (per cell for the
+        real-space families, its sum in sums[4]); the shells get both.  The temperature is applied inside the kernels."""
         plan = nbody.get_plan(self.final_shape)
         cm, selec, want_sqsel = f.cm.contiguous(), f.selec, self.ngb_lat is not None
-        sums = torch.empty(5, dtype=torch.float64, device=cm.device)
+        sums = torch.empty(6, dtype=torch.float64, device=cm.device)
         mesh_sel, qb = torch.is_tensor(selec), None
         if self.lik_type == "fourier_gauss":
             Y = nbody.rfftn(cm)
             Yb = torch.empty_like(Y)
             box, los = [float(v) for v in self.fwd.box_size], [float(v) for v in self.los_fid]
-            plan.call("mcpm_lik_fourier_f32", Y, self.obs_rg, *box, *los, float(selec), float(base["s_e"]), float(base["s_k2e"]),
-                      float(base["s_kmu2e"]), Yb, sums)
+            plan.call("mcpm_lik_fourier_temp_f32", Y, self.obs_rg, *box, *los, float(selec), float(base["s_e"]), float(base["s_k2e"]),
+                      float(base["s_kmu2e"]), float(f.temp), Yb, sums)
             keys = ("s_e", "s_k2e", "s_kmu2e")
         else:
             if mesh_sel:      # the selection made safe outside the mask
                 selec = (selec if self.mask is None else torch.where(self.mask, selec, torch.ones_like(selec))).contiguous()
-            shash = self.lik_type == "shash"
+            family = {"shash": _lib.LIK_SHASH, "poisson": _lib.LIK_POISSON, "two_quad_gauss": _lib.LIK_TWO_QUAD}[self.lik_type]
+            keys = self.LIK_STOCH[self.lik_type]
             cm_bar = torch.empty_like(cm)
             qb = torch.empty_like(cm) if (want_sqsel and mesh_sel) else None
-            st = [float(base[k]) if shash else 0.0 for k in self.STOCH]
-            plan.call("mcpm_lik_real_f32", _lib.LIK_SHASH if shash else _lib.LIK_POISSON, C.c_int64(cm.numel()), self.count_obs, cm,
-                      selec if mesh_sel else None, 1.0 if mesh_sel else float(selec), self.mask, *st, cm_bar, qb, sums)
-            keys = self.STOCH if shash else ()
+            st = [float(base[k]) if keys else 0.0 for k in self.STOCH]
+            quad = (self.quad[0], self.quad[1], self.N_QUAD) if family == _lib.LIK_TWO_QUAD else (None, None, 0)
+            if f.phi is not None:
+                f.phi_bar = torch.empty_like(f.phi)
+                keys = keys + ("s_ep",)
+            plan.call("mcpm_lik_real_phi_f32", family, C.c_int64(cm.numel()), self.count_obs, cm, selec if mesh_sel else None,
+                      1.0 if mesh_sel else float(selec), self.mask, f.phi, *st, float(base.get("s_ep", 0.)), float(f.temp), *quad, cm_bar,
+                      f.phi_bar, qb, sums)
         v = sums.cpu().numpy()
         if not need_grad:
             return float(v[0]), None, None, None
         if self.lik_type == "fourier_gauss":
             cm_bar = nbody.rfftn_vjp(Yb, overwrite=True)
-        stoch_bar = {k: float(v[1 + i]) for i, k in enumerate(keys)}
+        stoch_bar = {k: float(v[5 if k == "s_ep" else 1 + i]) for i, k in enumerate(keys)}
         if not want_sqsel:
             return float(v[0]), cm_bar, stoch_bar, None
         per = self._per_shell(cm_bar * f.dn)      # count = dn rc at fixed selec
@@ -585,7 +612,13 @@ class FieldLevelLogDensity:
             obs = torch.where(self.mask, obs, torch.zeros_like(obs))
         delta = cmu / selec - 1.0
         lin = base["s_e"] + base["s_ed"] * delta
+        s_ep, st = float(base.get("s_ep", 0.)), float(f.temp) ** .5
+        if f.phi is not None:
+            phi = f.phi if self.mask is None else torch.where(self.mask, f.phi, torch.zeros_like(f.phi))
+            lin = lin + s_ep * phi
         b = (lin.abs() + 1e-9) * selec ** .5
+        if st != 1.0:
+            b = b * st
         a = 0.0 if abs(float(base["s_e2"])) < 1e-10 else float(base["s_e2"]) * selec ** .5
         lpe, g_loc, g_b, g_a = quad_gaussian_log_prob_and_grad(obs, cmu, b, a)
         if self.mask is not None:
@@ -596,13 +629,18 @@ class FieldLevelLogDensity:
         if not need_grad:
             return lp, None, None, None
         sgn = torch.sign(lin) * selec ** .5
+        if st != 1.0:
+            sgn = sgn * st
         cm_bar = g_loc + g_b * sgn * (base["s_ed"] / selec)
         stoch_bar = {"s_e": float((g_b * sgn).double().sum()), "s_ed": float((g_b * sgn * delta).double().sum()),
                      "s_e2": float((g_a * selec ** .5).double().sum())}
+        if f.phi is not None:
+            f.phi_bar = g_b * sgn * s_ep
+            stoch_bar["s_ep"] = float((g_b * sgn * phi).double().sum())
         if self.ngb_lat is None:
             return lp, cm_bar, stoch_bar, None
         # d/d rcounts: through count = dn rc and through selec (|S rc| per cell, or mean(rcounts)), each in its closed form
-        wsel = g_b * (lin.abs() + 1e-9) + (g_a * float(base["s_e2"]) if torch.is_tensor(g_a) else 0.0)   # d lp / d sqrt(selec)
+        wsel = g_b * (lin.abs() + 1e-9) * st + (g_a * float(base["s_e2"]) if torch.is_tensor(g_a) else 0.0)   # d lp / d sqrt(selec)
         if self.sel_down is not None:
             # delta = count / selec does not move with rc; selec = |S| |rc|
             rc_bar = g_loc * f.dn + wsel * 0.5 * selec ** -.5 * self.sel_down.abs() * torch.sign(f.rc)
@@ -612,11 +650,12 @@ class FieldLevelLogDensity:
         return lp, cm_bar, stoch_bar, per.cpu().numpy() + common / self.n_rbins
 
     def draw_counts(self, sample, seed=0):
-        """One observed count mesh drawn from the likelihood at `sample` (model.py:873, :886, :901, :929): float32 device tensor, final_shape,
+        """One observed count mesh drawn from the likelihood at `sample` (model.py:873, :886, :901, :909, :929; temp = 1): float32 device tensor, final_shape,
         zero in the unobserved cells.  Host float64 draws on the mean counts of the HIP forward model; not on the hot path."""
         fwd, rng = self.fwd, np.random.default_rng(seed)
         base = self.base_params(sample)
-        cm, selec = self.mean_counts(sample)
+        f = self._forward(base, sample["white_mesh_"], need_phi=True)
+        cm, selec = f.cm, f.selec
         cm = cm.double().cpu().numpy()
         sel_mean = selec if not torch.is_tensor(selec) else None
         selec = selec.double().cpu().numpy() if torch.is_tensor(selec) else np.full(self.final_shape, selec)
@@ -635,10 +674,13 @@ class FieldLevelLogDensity:
             obs_rg = cgh2rg(nbody.rfftn(cm.astype(np.float32))) + sigma * torch.from_numpy(eps.astype(np.float32)).to(sigma.device)
             return nbody.irfftn(rg2cgh(obs_rg))
         else:
-            b = (np.abs(base["s_e"] + base["s_ed"] * (cm / selec - 1.0)) + 1e-9) * selec ** .5
+            phi = 0. if f.phi is None else np.where(mask, f.phi.double().cpu().numpy(), 0.)
+            b = (np.abs(base["s_e"] + base["s_ed"] * (cm / selec - 1.0) + float(base.get("s_ep", 0.)) * phi) + 1e-9) * selec ** .5
             a = float(base["s_e2"]) * selec ** .5
             if self.lik_type == "quad_gauss":      # utils.py:492-494
                 obs = cm + b * eps + a * (eps ** 2 - 1.0)
+            elif self.lik_type == "two_quad_gauss":      # two independent normals, utils.py:595-600
+                obs = cm + b * eps + a * (rng.standard_normal(self.final_shape) ** 2 - 1.0)
             else:      # 'shash', utils.py:431-435
                 from numpy.polynomial.hermite_e import hermegauss
                 x, wq = hermegauss(20)
@@ -681,9 +723,13 @@ class FieldLevelLogDensity:
             base_bar["Omega_m"] = self.fwd.cosmo_vjp(f.ctx, g, params=("Omega_m",))["Omega_m"]
         return base_bar
 
-    def logdensity_and_grad(self, sample, need_grad=True):
+    def logdensity_and_grad(self, sample, need_grad=True, temp_lik=1.):
         """sample: dict with the scalars `name_` (floats) and 'white_mesh_' (real tensor, fwd.init_shape).
-        Returns (log density, dict of gradients with the same keys)."""
+        Returns (log density, dict of gradients with the same keys).  `temp_lik`: the temperature of the likelihood (model.py:840, `temp` of
+        `_model(temp_prior, temp_lik)`): the noise scale of the Gaussian-like families times sqrt(temp_lik), the Poisson rate to the power
+        1 / temp_lik; the priors are not tempered (`temp_prior` is not built)."""
+        if not temp_lik > 0:
+            raise ValueError("temp_lik must be positive")
         fwd = self.fwd
         lp, base, grad, dbase = self._prior(sample)
         if lp == -math.inf:      # a latent sits in a saturated tail: zero density whatever the field (no forward model needed)
@@ -692,15 +738,17 @@ class FieldLevelLogDensity:
             return -math.inf, (self._zero_grad(sample) if need_grad else None)
         w = nbody._f32(sample["white_mesh_"], fwd.init_shape)
         lp += self._white_prior(w)
-        f = self._forward(base, w, need_ctx=True)
-        lpl, cm_bar, stoch_bar, rcounts_bar = (self._lik_quad_gauss if self.lik_type == "quad_gauss" else self._lik_hip)(base, f, need_grad)
+        f = self._forward(base, w, need_ctx=True, need_phi=True)
+        lik = self._lik_quad_gauss if self.lik_type == "quad_gauss" else self._lik_hip
+        f.temp = float(temp_lik)
+        lpl, cm_bar, stoch_bar, rcounts_bar = lik(base, f, need_grad)
         lp += lpl
         if not need_grad:
             return lp, None
         gxy_bar = self._down_vjp(cm_bar * f.rc, f.gxy.shape)
         if self.selec_mesh is not None:
             gxy_bar = gxy_bar * self.selec_mesh
-        g = fwd.evolve_vjp(f.ctx, gxy_bar)
+        g = fwd.evolve_vjp(f.ctx, gxy_bar) if f.phi_bar is None else fwd.evolve_vjp(f.ctx, gxy_bar, phi_bar=f.phi_bar)
         wb = g["white_mesh"] * self.transfer
         wbar = nbody.rfftn_vjp(wb, overwrite=True) if self.precond == "real" else rg2cgh_vjp(wb)
         grad["white_mesh_"] = wbar - (w if self.scale is None else w / self.scale ** 2)

@@ -5,8 +5,10 @@ reference asserts) or 'kaiser' (any sky, scalar a_obs or light cone: bricks.py:1
 non-Gaussianity: `evolve(..., png={'fNL': ..., ...})`, model.py:688, :751-758), ap_auto None, True or False (Alcock-Paczynski:
 model.py:64, :787-794; `evolve(..., ap={'alpha_iso': ..., 'alpha_ap': ...})` for False), kernel_type 'rectangular', linear power from a table (`lin_kpow`,
 bricks.py:75-77) or, with lin_kpow = None, from the Eisenstein-Hu fit of the current cosmology (bricks.py:72-74; power.py).
-Priors, likelihood and samplers: logdensity.py, samplers.py.  Not built: Eulerian bias, the stochastic term s_ep * phi of the
-likelihood (model.py:894), Alcock-Paczynski in the Kaiser model (model.py:703-729
+With png_type and 'lpt' / 'nbody' the Gaussian potential phi that the likelihood's stochastic term s_ep * phi reads (model.py:837, :869, :894)
+is `ctx.phi` of `evolve(..., return_ctx=True)`; `phi_final` brings it to the final mesh and `evolve_vjp(..., phi_bar=)` takes its cotangent back.
+Priors, likelihood and samplers: logdensity.py, samplers.py.  Not built: Eulerian bias, the tempered prior `temp_prior` (`samp2base(temp=)`,
+model.py:640-679), Alcock-Paczynski in the Kaiser model (model.py:703-729
 computes the moved positions and discards them), `ap_auto_absdetjac` and `rsd_ap_auto` (no live call site in the reference).
 
     fwd = FieldLevelForward(final_shape=(64, 64, 64), cell_length=20., box_center=(0, 0, 2000.), evolution='nbody',
@@ -247,7 +249,9 @@ class FieldLevelForward:
         With png_type (model.py:688, :751-758): fNL_bias -> bias weights from the GAUSSIAN evolution mesh -> add_png on it (phi is
         handed over from the bias step: three extra transforms in all) -> chreshape to init_shape and back, which cuts the modes
         phi^2 filled above the initial Nyquist -> lpt / nbody.  As in the reference, the transfer table of these two steps is the
-        Eisenstein-Hu one (model.py:751, :757 pass no kpow); the Kaiser model's follows `lin_kpow` (model.py:695)."""
+        Eisenstein-Hu one (model.py:751, :757 pass no kpow); the Kaiser model's follows `lin_kpow` (model.py:695).
+        The context of an 'lpt' / 'nbody' run carries `phi`: with png_type the Gaussian potential that `lagrangian_bias` returned (the
+        Gaussian evolution mesh divided by the transfer, real, evol_shape; model.py:837), else None (phi = 0)."""
         white = nbody._c64(white_mesh, r2chshape(self.init_shape))
         init_k = self._power_mult(white, cosmo)
         evol_k = chreshape(init_k, r2chshape(self.evol_shape))
@@ -291,11 +295,24 @@ class FieldLevelForward:
         gxy = nbody.irfftn(gxy_k)
         if return_ctx:
             return gxy, EvolveCtx(cosmo=cosmo, white=white, evol_k=evol_k, pos0=pos0, a=a, bctx=bctx, nctx=nctx, octx=octx,
-                                  pos_c=pos_c, w=w, jac=jac, scalar_fd=fd, lin_k=lin_k, actx=actx, png=png, png_in=png_in or {}, bias=bias)
+                                  pos_c=pos_c, w=w, jac=jac, scalar_fd=fd, lin_k=lin_k, actx=actx, png=png, png_in=png_in or {}, bias=bias,
+                                  phi=None if png is None else phi)
         return gxy
 
+    def phi_final(self, phi):
+        """phi of `evolve`'s context on the final mesh: irfftn(chreshape(rfftn(phi), final_shape)) (model.py:869)."""
+        if tuple(phi.shape) == self.final_shape:
+            return phi
+        return nbody.irfftn(chreshape(nbody.rfftn(phi), r2chshape(self.final_shape)))
+
+    def phi_final_vjp(self, phi_bar):
+        """Adjoint of `phi_final`: a final-shape cotangent -> the cotangent of phi on evol_shape."""
+        if tuple(self.evol_shape) == self.final_shape:
+            return phi_bar
+        return nbody.rfftn_vjp(chreshape_vjp(nbody.irfftn_vjp(phi_bar), r2chshape(self.evol_shape)), overwrite=True)
+
     # ---- reverse sweep -----------------------------------------------------------------------------------
-    def evolve_vjp(self, ctx, gxy_bar):
+    def evolve_vjp(self, ctx, gxy_bar, phi_bar=None):
         """Cotangent of gxy_mesh (real, paint_shape) -> {'white_mesh': complex64 cotangent (real-pair convention),
         'bias': dict, 'sigma8': float, 'growth': cotangents of the growth scalars (see nbody.lpt_vjp / nbody_bf_vjp),
         'bias_growth': cotangent(s) of a2g(a) through the bias weights, 'gf': cotangent of a2g(a_obs) a2f(a_obs) through rsd}.
@@ -304,9 +321,16 @@ class FieldLevelForward:
         With ap_auto also 'ap': {'alpha_iso', 'alpha_ap'} cotangents (0 for ap_auto=True), and for ap_auto=True at fixed a_obs 'ap_chi_bar':
         the cotangent of the chi nodes of chi2a(cosmo, r') (device float64; cosmo_vjp).
         With png_type also 'png': cotangents of the six entries of the `png` dict given to evolve (the fNL_bias reparametrisation
-        chained back, its b1 / b2 share added to 'bias'), and 'trans_bar': cotangent of the transfer table's entries (cosmo_vjp)."""
+        chained back, its b1 / b2 share added to 'bias'), and 'trans_bar': cotangent of the transfer table's entries (cosmo_vjp).
+        `phi_bar` (real, final_shape; 'lpt' / 'nbody' with png_type): the cotangent of `phi_final(ctx.phi)` from the likelihood.  It is pulled back
+        to evol_shape and joins the phi cotangent of the bias weights in front of `add_png_vjp`, so there is still one divide by the transfer
+        table, and 'trans_bar' carries its share."""
         if self.evolution == 'kaiser':
+            if phi_bar is not None:
+                raise ValueError("evolution 'kaiser' defines no phi (model.py:690-696): there is nothing a phi_bar could be the cotangent of")
             return self._kaiser_vjp(ctx, gxy_bar)
+        if phi_bar is not None and ctx.actx is None:
+            raise ValueError("phi_bar needs a context of a model with png_type set: without it phi = 0")
         cosmo = ctx.cosmo
         gb = nbody._f32(gxy_bar, self.paint_shape)
         kb = chreshape_vjp(nbody.irfftn_vjp(gb), r2chshape(self.init_shape)) * ctx.jac
@@ -330,6 +354,8 @@ class FieldLevelForward:
         if ctx.actx is not None:
             # three transforms: the cotangents of phi (bias weights and add_png) and of lap phi meet in k-space before the one divide by t
             ob = chreshape_vjp(chreshape_vjp(mb, r2chshape(self.init_shape)), r2chshape(self.evol_shape))
+            if phi_bar is not None:
+                phb = phb + self.phi_final_vjp(nbody._f32(phi_bar, self.final_shape))
             mb, png_bar["fNL"], trans_bar = bricks.add_png_vjp(ctx.actx, ob, phi_bar=phb, lap_phi_bar=lpb)
             png_bar, bb = bricks.fNL_bias_vjp(ctx.png_in, ctx.bias, png_bar, p=1., png_type=self.png_type)
             bias_bar["b1"] += bb["b1"]

@@ -1,8 +1,9 @@
 """End-to-end field-level NUTS on one MI355X (BASELINE config 5 in miniature or at size): synthetic truth -> observed
 counts -> `FieldLevelLogDensity` -> `samplers.nuts_sample`.
-usage: python tools/run_nuts_field.py [final_n=146] [n_warmup=200] [n_samples=200] [max_depth=6] [evolution=nbody] [out.json] [nuts|mclmc] [precond=fourier] [--start=prior|kaiser]
+usage: python tools/run_nuts_field.py [final_n=146] [n_warmup=200] [n_samples=200] [max_depth=6] [evolution=nbody] [out.json] [nuts|mclmc] [precond=fourier] [--start=prior|kaiser] [--lik=quad_gauss|shash|two_quad_gauss|poisson|fourier_gauss]
 --start=kaiser: the field starts from `kaiser_post` (the posterior of the fiducial linear Kaiser model given the counts, scale_field = 7/8 as
-montecosmo/script.py:33) instead of 0.1 randn prior_std; the default, `prior`, is the start this tool has always used."""
+montecosmo/script.py:33) instead of 0.1 randn prior_std; the default, `prior`, is the start this tool has always used.
+--lik: the likelihood the chain samples (default 'quad_gauss'); the synthetic counts keep their Gaussian noise whatever it is."""
 import json, sys, time
 import numpy as np, torch
 sys.path.insert(0, ".")
@@ -11,7 +12,10 @@ from montecosmo_amd import model, logdensity, samplers, bricks, utils, nbody
 start_kind = ([a.split("=", 1)[1] for a in sys.argv if a.startswith("--start=")] or ["prior"])[-1]
 if start_kind not in ("prior", "kaiser"):
     raise SystemExit("--start must be 'prior' or 'kaiser'")
-sys.argv = [a for a in sys.argv if not a.startswith("--start=")]
+lik_type = ([a.split("=", 1)[1] for a in sys.argv if a.startswith("--lik=")] or ["quad_gauss"])[-1]
+if lik_type not in logdensity.FieldLevelLogDensity.LIK_STOCH:
+    raise SystemExit(f"--lik must be one of {sorted(logdensity.FieldLevelLogDensity.LIK_STOCH)}")
+sys.argv = [a for a in sys.argv if not a.startswith(("--start=", "--lik="))]
 
 nf = int(sys.argv[1]) if len(sys.argv) > 1 else 146
 n_warm = int(sys.argv[2]) if len(sys.argv) > 2 else 200
@@ -30,12 +34,12 @@ lat = {"Omega_m": dict(loc=0.3111, scale=0.1, loc_fid=0.3111, scale_fid=1e-2),
        "sigma8": dict(loc=0.8102, scale=0.1, loc_fid=0.8102, scale_fid=1e-2),
        "b1": dict(loc=1., scale=1e2, loc_fid=1., scale_fid=1e-2), "b2": dict(loc=0., scale=1e2, loc_fid=0., scale_fid=3e-2),
        "bs2": dict(loc=0., scale=1e2, loc_fid=0., scale_fid=1e-1), "bn2": dict(loc=0., scale=1e3, loc_fid=0., scale_fid=1.)}
-fixed = dict(b3=0., bds2=0., bs3=0., bnpar=0., ngbars=1e-3, s_e=1.0, s_ed=0., s_e2=0.)
+fixed = dict(b3=0., bds2=0., bs3=0., bnpar=0., ngbars=1e-3, s_e=1.0, s_ed=0., s_e2=0., s_k2e=0., s_kmu2e=0.)
 torch.manual_seed(0)
 truth = {k + "_": 0.0 for k in lat}
 truth["white_mesh_"] = torch.randn(fwd.init_shape, device="cuda")
 # observed counts: the model's own mean at the truth + its Gaussian noise (model.py:893-908 with s_ed = s_e2 = 0)
-ld0 = logdensity.FieldLevelLogDensity(fwd, torch.zeros(fwd.final_shape), lat, fixed, precond=precond)
+ld0 = logdensity.FieldLevelLogDensity(fwd, torch.zeros(fwd.final_shape), lat, fixed, precond=precond, lik_type=lik_type)
 prior_std = 1.0 if ld0.scale is None else ld0.scale          # white_mesh_ ~ Normal(0, scale): the truth is a prior draw
 truth["white_mesh_"] = truth["white_mesh_"] * prior_std
 base = ld0.base_params(truth)
@@ -45,7 +49,7 @@ rc = fixed["ngbars"] * fwd.cell_length ** 3
 cm = rc * nbody.irfftn(utils.chreshape(nbody.rfftn(gxy), utils.r2chshape(fwd.final_shape)))
 obs = cm + rc ** .5 * torch.randn(fwd.final_shape, device="cuda")
 print(f"truth: mean count {float(cm.mean()):.3f}, count contrast std {float((cm / rc - 1).std()):.3f}", flush=True)
-ld = logdensity.FieldLevelLogDensity(fwd, obs, lat, fixed, precond=precond)
+ld = logdensity.FieldLevelLogDensity(fwd, obs, lat, fixed, precond=precond, lik_type=lik_type)
 flat = samplers.FlatLogDensity(ld)
 start = dict(truth)
 start["white_mesh_"] = 0.1 * torch.randn(fwd.init_shape, device="cuda") * prior_std     # away from the truth, near the prior mode
@@ -99,7 +103,7 @@ def field_correlation(q_end):
 
 corr = field_correlation(res["last_state"]["q"])
 print("correlation of the last state's initial field with the truth:", corr, flush=True)
-summary = {"sampler": sampler, "precond": precond, "final_shape": fwd.final_shape, "evol_shape": fwd.evol_shape, "evolution": evolution, "dimension": int(q0.numel()),
+summary = {"sampler": sampler, "precond": precond, "lik_type": lik_type, "final_shape": fwd.final_shape, "evol_shape": fwd.evol_shape, "evolution": evolution, "dimension": int(q0.numel()),
            "n_warmup": n_warm, "n_samples": n_samp, "max_tree_depth": depth, "wall_s": round(wall, 1),
            "gradient_evals": flat.n_eval, "ms_per_gradient": round(1e3 * wall / max(flat.n_eval - 1, 1), 2),
            "mean_leapfrogs": float(np.mean([i["n_leapfrog"] for i in infos])), "step_size": res["step_size"],
