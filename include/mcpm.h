@@ -535,6 +535,21 @@ int mcpm_bias_weights_vjp_f32(mcpm_plan *plan, int64_t n, const float *dr, const
                               const float *weights_bar, const float *dvel_bar, float *dr_bar, float *s2r_bar, float *s3r_bar,
                               float *lr_bar, float *gr_bar, float *growth_bar, double *scalars_out);
 
+/* Eulerian bias expansion on the painted matter field (montecosmo/bricks.py:513-586):
+     w = 1 + b1E d + b2E (d^2 - <d^2>) / 2 + bs2 (s2 - 2/3 <d^2>) + bn2 lap(d) [+ bp phi + bpdE (phi d - <phi d>)]
+   d = irfftn(matter_k with its zero mode dropped), s2 the squared traceless tidal shear of d, phi = irfftn(phi_k) (terms in brackets only
+   when phi_k != NULL); matter_k, phi_k: plain half-spectra of the plan's mesh, wavevectors in h/Mpc (kphys = mesh_shape / box_size).
+   coef6 (host) = {b1E, b2E, bs2, bn2, fNL_bp, fNL_bpdE}.  w: M floats.  saved (7 M floats, 8 M with phi_k) receives the real meshes
+   {d, h00, h11, h01, h02, h12, lap d [, phi]} (h_ij = d_i d_j laplace^-1 d) that the adjoint re-reads; moments (device, 2 doubles)
+   <d^2> and <phi d>, fixed-order float64 sums.  The VJP takes them back (has_phi != 0: the forward call had a phi_k) with the
+   cotangent of w and returns matter_k_bar (real-pair convention, irfftn multiplicity weights, zero mode 0), phi_k_bar (has_phi) and
+   coef_bar (device, 6 doubles).  No floating-point atomics: repeat calls are bitwise equal. */
+int mcpm_eulerian_bias_f32(mcpm_plan *plan, const float *matter_k, const float *phi_k, float kphys_x, float kphys_y, float kphys_z,
+                           const float *coef6, float *w, float *saved, double *moments);
+int mcpm_eulerian_bias_vjp_f32(mcpm_plan *plan, const float *saved, const double *moments, int has_phi, float kphys_x, float kphys_y,
+                               float kphys_z, const float *coef6, const float *w_bar, float *matter_k_bar, float *phi_k_bar,
+                               double *coef_bar);
+
 /* white2lin / lin2white multiplier (montecosmo/bricks.py:83-100, :149-161): out = in * sqrt(amp * P(|k|)), |k| in h/Mpc
    (kphys = mesh_shape / box_size), P linearly interpolated from the DEVICE float64 table (ks ascending, pows) and zero
    outside it (jnp.interp left = right = 0); amp = sigma8^2 for a table normalised to sigma8 = 1.  Real multiplier: the same

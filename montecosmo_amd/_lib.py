@@ -84,6 +84,9 @@ SIGNATURES = {
                                         C.POINTER(C.c_float), _f32p, _f32p, _d64p]),
     "mcpm_bias_weights_vjp_f32": (C.c_int, [_plan, C.c_int64, _f32p, _f32p, _f32p, _f32p, _f32p, C.c_int64, _f32p, C.c_float,
                                             C.POINTER(C.c_float), _f32p, _f32p, _f32p, _f32p, _f32p, _f32p, _f32p, _f32p, _d64p]),
+    "mcpm_eulerian_bias_f32": (C.c_int, [_plan, _f32p, _f32p, C.c_float, C.c_float, C.c_float, C.POINTER(C.c_float), _f32p, _f32p, _d64p]),
+    "mcpm_eulerian_bias_vjp_f32": (C.c_int, [_plan, _f32p, _d64p, C.c_int, C.c_float, C.c_float, C.c_float, C.POINTER(C.c_float), _f32p, _f32p,
+                                            _f32p, _d64p]),
     "mcpm_power_mult_f32": (C.c_int, [_plan, _f32p, C.c_float, C.c_float, C.c_float, C.c_double, _d64p, _d64p, C.c_int, _f32p]),
     "mcpm_interp_f32": (C.c_int, [_plan, _f32p, C.c_int64, _d64p, _d64p, C.c_int, C.c_float, _f32p]),
     "mcpm_png_add_f32": (C.c_int, [_plan, _f32p, C.c_float, C.c_float, C.c_float, _d64p, _d64p, C.c_int, C.c_float, C.c_int, _f32p,

@@ -9,113 +9,9 @@
 // between are mcpm_read_f32 / mcpm_paint_f32.
 #include "mcpm_internal.h"
 #include "reduce_dev.h"
-
-#define TWO_PI 6.283185307179586f
+#include "bias_dev.h"      // mode decoder, the 10-multiplier table, bias_spectra_kernel and its adjoint
 
 namespace {
-
-__device__ __forceinline__ float kfreq(int i, int n) {
-    int s = (i < (n + 1) / 2) ? i : i - n;
-    return TWO_PI * (float)s / (float)n;
-}
-
-struct BMode {
-    float k[3];     // physical wavevector
-    bool nyq[3], special;
-    float zw;
-};
-__device__ __forceinline__ BMode bdecode(const Geom &g, float kx, float ky, float kz, uint32_t idx) {
-    BMode m;
-    const int iz = idx % (uint32_t)g.nzh;
-    const uint32_t r = idx / (uint32_t)g.nzh;
-    const int iy = r % (uint32_t)g.ny, ix = r / (uint32_t)g.ny;
-    m.k[0] = kfreq(ix, g.nx) * kx;
-    m.k[1] = kfreq(iy, g.ny) * ky;
-    m.k[2] = TWO_PI * (float)iz / (float)g.nz * kz;
-    m.nyq[0] = !(g.nx & 1) && ix == g.nx / 2;
-    m.nyq[1] = !(g.ny & 1) && iy == g.ny / 2;
-    m.nyq[2] = iz == g.nz / 2;
-    m.special = iz == 0 || m.nyq[2];
-    m.zw = m.special ? 1.f : 2.f;
-    return m;
-}
-
-// the 10 multipliers y_s = irfftn(m_s X): real part re[s] (s = 0..6) or imaginary part im (s = 7..9)
-//  0: 1   1: kx kx/k2   2: ky ky/k2   3: kx ky/k2   4: kx kz/k2   5: ky kz/k2   6: -k2   7..9: i k_c
-// `herm`: apply numpy irfftn's projection on the kz = 0 / Nyquist planes (odd number of Nyquist factors -> 0)
-__device__ __forceinline__ void multipliers(const BMode &m, bool herm, float (&re)[7], float (&im)[3]) {
-    const float k2 = m.k[0] * m.k[0] + m.k[1] * m.k[1] + m.k[2] * m.k[2];
-    const float ik2 = k2 == 0.f ? 0.f : 1.f / k2;
-    const bool pr = herm && m.special;
-    re[0] = 1.f;
-    re[1] = m.k[0] * m.k[0] * ik2;
-    re[2] = m.k[1] * m.k[1] * ik2;
-    re[3] = (pr && m.nyq[0] != m.nyq[1]) ? 0.f : m.k[0] * m.k[1] * ik2;
-    re[4] = (pr && m.nyq[0] != m.nyq[2]) ? 0.f : m.k[0] * m.k[2] * ik2;
-    re[5] = (pr && m.nyq[1] != m.nyq[2]) ? 0.f : m.k[1] * m.k[2] * ik2;
-    re[6] = -k2;
-#pragma unroll
-    for (int c = 0; c < 3; ++c) im[c] = (pr && m.nyq[c]) ? 0.f : m.k[c];
-}
-
-// GROUP 0: spectra 0..5 (6 outputs), GROUP 1: spectra 6..9 (4 outputs); out[s] = scale * m_s * in
-template <int GROUP>
-__global__ __launch_bounds__(256) void bias_spectra_kernel(Geom g, float kx, float ky, float kz, float scale,
-                                                           const float2 *__restrict__ in, float2 *__restrict__ out, int64_t Mh) {
-    const uint32_t idx = blockIdx.x * 256u + threadIdx.x;
-    if (idx >= Mh) return;
-    const BMode m = bdecode(g, kx, ky, kz, idx);
-    float re[7], im[3];
-    multipliers(m, true, re, im);
-    const float2 v = in[idx];
-    if (GROUP == 0) {
-#pragma unroll
-        for (int s = 0; s < 6; ++s) out[s * Mh + idx] = make_float2(scale * re[s] * v.x, scale * re[s] * v.y);
-    } else {
-        out[idx] = make_float2(scale * re[6] * v.x, scale * re[6] * v.y);
-#pragma unroll
-        for (int c = 0; c < 3; ++c) out[(1 + c) * Mh + idx] = make_float2(-scale * im[c] * v.y, scale * im[c] * v.x);  // (a+ib)(i s)
-    }
-}
-
-// out (+)= scale * zw * sum_s conj(m_s) in[s]   (adjoint of irfftn o multiply; un-projected multipliers)
-template <int GROUP>
-__global__ __launch_bounds__(256) void bias_spectra_vjp_kernel(Geom g, float kx, float ky, float kz, float scale,
-                                                               const float2 *__restrict__ in, float2 *__restrict__ out,
-                                                               int64_t Mh, int accumulate) {
-    const uint32_t idx = blockIdx.x * 256u + threadIdx.x;
-    if (idx >= Mh) return;
-    const BMode m = bdecode(g, kx, ky, kz, idx);
-    float re[7], im[3];
-    multipliers(m, false, re, im);
-    float ar = 0.f, ai = 0.f;
-    if (GROUP == 0) {
-#pragma unroll
-        for (int s = 0; s < 6; ++s) {
-            const float2 v = in[s * Mh + idx];
-            ar += re[s] * v.x;
-            ai += re[s] * v.y;
-        }
-    } else {
-        const float2 v = in[idx];
-        ar += re[6] * v.x;
-        ai += re[6] * v.y;
-#pragma unroll
-        for (int c = 0; c < 3; ++c) {
-            const float2 w = in[(1 + c) * Mh + idx];
-            ar += im[c] * w.y;   // (a+ib)(-i s)
-            ai += -im[c] * w.x;
-        }
-    }
-    ar *= scale * m.zw;
-    ai *= scale * m.zw;
-    if (accumulate) {
-        const float2 o = out[idx];
-        ar += o.x;
-        ai += o.y;
-    }
-    out[idx] = make_float2(ar, ai);
-}
 
 // r6 = {delta, h00, h11, h01, h02, h12} (h_ij = d_i d_j laplace^-1 delta) -> shear^2, 3 det(shear)
 __global__ __launch_bounds__(256) void shear_combine_kernel(const float *__restrict__ r6, int64_t M, float *__restrict__ s2,

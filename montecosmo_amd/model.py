@@ -1,13 +1,13 @@
 """`FieldLevelModel.evolve` (montecosmo/model.py:686-838) on the HIP path, with its hand-written reverse sweep.
 
-Built branch: bias_type 'lagrangian', evolution 'lpt' (scalar a_obs or light cone), 'nbody' (scalar a_obs, as the
-reference asserts) or 'kaiser' (any sky, scalar a_obs or light cone: bricks.py:170-231), png_type None, 'fNL' or 'bias' (local primordial
+Built branches: bias_type 'lagrangian' or 'eulerian' (model.py:68, :753-754, :797-831; `FieldLevelForward(bias_type=)`), evolution 'lpt'
+(scalar a_obs or light cone), 'nbody' (scalar a_obs, as the reference asserts) or 'kaiser' (any sky, scalar a_obs or light cone: bricks.py:170-231), png_type None, 'fNL' or 'bias' (local primordial
 non-Gaussianity: `evolve(..., png={'fNL': ..., ...})`, model.py:688, :751-758), ap_auto None, True or False (Alcock-Paczynski:
 model.py:64, :787-794; `evolve(..., ap={'alpha_iso': ..., 'alpha_ap': ...})` for False), kernel_type 'rectangular', linear power from a table (`lin_kpow`,
 bricks.py:75-77) or, with lin_kpow = None, from the Eisenstein-Hu fit of the current cosmology (bricks.py:72-74; power.py).
 With png_type and 'lpt' / 'nbody' the Gaussian potential phi that the likelihood's stochastic term s_ep * phi reads (model.py:837, :869, :894)
 is `ctx.phi` of `evolve(..., return_ctx=True)`; `phi_final` brings it to the final mesh and `evolve_vjp(..., phi_bar=)` takes its cotangent back.
-Priors, likelihood and samplers: logdensity.py, samplers.py.  Not built: Eulerian bias, the tempered prior `temp_prior` (`samp2base(temp=)`,
+Priors, likelihood and samplers: logdensity.py, samplers.py.  Not built: the tempered prior `temp_prior` (`samp2base(temp=)`,
 model.py:640-679), Alcock-Paczynski in the Kaiser model (model.py:703-729
 computes the moved positions and discards them), `ap_auto_absdetjac` and `rsd_ap_auto` (no live call site in the reference).
 
@@ -20,6 +20,8 @@ Chain (every arrow is a HIP kernel sequence of libmcpm.so, each with its VJP):
 white_mesh -white2lin-> init_mesh -chreshape-> evol mesh -lagrangian_bias-> (weights, dvel, phi); [-add_png(phi)-> -chreshape to
 init_shape and back->] -lpt | nbody_bf-> (pos, vel)
 -observe_pos (los, rsd, Alcock-Paczynski)-> pos on init_shape -nufft(weights, paint_shape)-> spectrum -chreshape-> -irfftn-> gxy_mesh.
+bias_type 'eulerian': the particles are painted unweighted (and, with png_type, once more weighted by phi read at their Lagrangian
+positions), -nufft(1 | phi_pos)-> matter / phi spectra -chreshape-> -eulerian_bias-> gxy_mesh; `lagrangian_bias` still supplies dvel and phi.
 """
 from __future__ import annotations
 
@@ -35,7 +37,10 @@ class FieldLevelForward:
     def __init__(self, final_shape=(64, 64, 64), cell_length=20., box_center=(0., 0., 0.), box_rotvec=(0., 0., 0.),
                  evolution='lpt', nbody_a_start=0., nbody_n_steps=10, lpt_order=2, paint_order=2, paint_deconv=True,
                  init_oversamp=3 / 2, evol_oversamp=7 / 4, ptcl_oversamp=7 / 4, paint_oversamp=7 / 4, interlace_order=2,
-                 a_obs=None, curved_sky=True, lin_kpow=None, png_type=None, ap_auto=None, cosmo_fid=None):
+                 a_obs=None, curved_sky=True, lin_kpow=None, png_type=None, ap_auto=None, cosmo_fid=None, bias_type='lagrangian'):
+        if bias_type not in ('lagrangian', 'eulerian'):
+            raise ValueError("bias_type must be 'lagrangian' or 'eulerian'")
+        self.bias_type = bias_type      # evolution 'kaiser' ignores it, as in the reference (model.py:690-696)
         if evolution not in ('kaiser', 'lpt', 'nbody'):
             raise ValueError("evolution must be 'kaiser', 'lpt' or 'nbody'")
         if png_type not in (None, 'fNL', 'bias'):
@@ -73,7 +78,7 @@ class FieldLevelForward:
         """The model attributes as a dict (what the parity tests hand to their float64 checker)."""
         keys = ("init_shape", "evol_shape", "ptcl_shape", "paint_shape", "box_size", "box_center", "box_rotvec", "a_obs",
                 "curved_sky", "evolution", "nbody_a_start", "nbody_n_steps", "lpt_order", "paint_order", "paint_deconv",
-                "interlace_order", "lin_kpow")
+                "interlace_order", "lin_kpow", "bias_type")
         return {k: getattr(self, k) for k in keys}
 
     @classmethod
@@ -288,16 +293,59 @@ class FieldLevelForward:
         apkw = {} if self.ap_auto is None else dict(ap_auto=self.ap_auto, ap=ap, cosmo_fid=self.cosmo_fid)
         pos_c, octx = bricks.observe_pos(cosmo, pos, vel, self.box_center, self.box_rotvec, self.box_size, self.evol_shape,
                                          self.init_shape, a_obs=self.a_obs, curved_sky=self.curved_sky, dvel=dvel, return_ctx=True, **apkw)
-        gxy_k = nbody.nufft(pos_c, self.init_shape, self.paint_shape, weights=w, paint_order=self.paint_order,
-                            interlace_order=self.interlace_order, paint_deconv=self.paint_deconv)
         jac = float(np.divide(self.init_shape, self.ptcl_shape).prod())
-        gxy_k = chreshape(gxy_k * jac, r2chshape(self.paint_shape))
-        gxy = nbody.irfftn(gxy_k)
+        ectx = phi_pos = None
+        if self.bias_type == 'eulerian':
+            gxy, ectx, phi_pos = self._eulerian_paint(pos_c, pos0, bias, png, None if png is None else phi, jac)
+        else:
+            gxy_k = nbody.nufft(pos_c, self.init_shape, self.paint_shape, weights=w, paint_order=self.paint_order,
+                                interlace_order=self.interlace_order, paint_deconv=self.paint_deconv)
+            gxy_k = chreshape(gxy_k * jac, r2chshape(self.paint_shape))
+            gxy = nbody.irfftn(gxy_k)
         if return_ctx:
             return gxy, EvolveCtx(cosmo=cosmo, white=white, evol_k=evol_k, pos0=pos0, a=a, bctx=bctx, nctx=nctx, octx=octx,
                                   pos_c=pos_c, w=w, jac=jac, scalar_fd=fd, lin_k=lin_k, actx=actx, png=png, png_in=png_in or {}, bias=bias,
-                                  phi=None if png is None else phi)
+                                  phi=None if png is None else phi, ectx=ectx, phi_pos=phi_pos)
         return gxy
+
+    # ---- Eulerian bias (model.py:815-831): unweighted paint(s), then the expansion on the painted mesh ----------------------
+    def _nufft_kw(self):
+        return dict(paint_order=self.paint_order, interlace_order=self.interlace_order, paint_deconv=self.paint_deconv)
+
+    def _phi_lattice(self):
+        """True where the NGP read of phi at the Lagrangian lattice is the identity (the particles are the evolution mesh's own points)."""
+        return tuple(self.ptcl_shape) == tuple(self.evol_shape)
+
+    def _eulerian_paint(self, pos_c, pos0, bias, png, phi, jac):
+        """-> (gxy_mesh, context of bricks.eulerian_bias, phi_pos or None).  Both paints carry the Jacobian prod(init_shape / ptcl_shape) of the
+        Lagrangian branch (model.py:806): nufft returns counts per init cell and chreshape keeps the mean, so this is what makes the painted
+        field mean-one; model.py:820, :827 have paint_shape there, which scales delta by (paint / init)^3."""
+        kshape = r2chshape(self.paint_shape)
+        mk = chreshape(nbody.nufft(pos_c, self.init_shape, self.paint_shape, weights=1., **self._nufft_kw()) * jac, kshape)
+        pk = phi_pos = None
+        if png is not None:      # phi advected with the particles (model.py:754, :824-828)
+            phi_pos = phi.reshape(-1) if self._phi_lattice() else nbody.read(pos0, phi, order=1)
+            pk = chreshape(nbody.nufft(pos_c, self.init_shape, self.paint_shape, weights=phi_pos, **self._nufft_kw()) * jac, kshape)
+        gxy, ectx = bricks.eulerian_bias(mk, pk, self.box_size, bias, png, png_type=self.png_type, return_ctx=True)
+        return gxy, ectx, phi_pos
+
+    def _eulerian_paint_vjp(self, ctx, gb):
+        """Cotangent of gxy_mesh -> (cotangent of pos_c from both paints, bias_bar, png_bar or None, cotangent of phi on evol_shape or None)."""
+        mkb, pkb, bias_bar, png_bar = bricks.eulerian_bias_vjp(ctx.ectx, gb)
+        ishape = r2chshape(self.init_shape)
+        kw = dict(self._nufft_kw(), paint_shape=self.paint_shape)
+        pb, _ = nbody.nufft_vjp(ctx.pos_c, self.init_shape, 1., chreshape_vjp(mkb, ishape) * ctx.jac, **kw)
+        phi_b = None
+        if pkb is not None:
+            pb2, ppb = nbody.nufft_vjp(ctx.pos_c, self.init_shape, ctx.phi_pos, chreshape_vjp(pkb, ishape) * ctx.jac, **kw)
+            pb = pb + pb2
+            if self._phi_lattice():
+                phi_b = ppb.reshape(self.evol_shape)
+            else:      # adjoint of the NGP read w.r.t. its mesh: a weighted paint on the Lagrangian lattice
+                plan, p, n, mode = nbody._pos_args(ctx.pos0, self.evol_shape)
+                phi_b = torch.empty(self.evol_shape, dtype=torch.float32, device=ppb.device)
+                plan.call("mcpm_paint_f32", p, n, mode, ppb.contiguous(), 1, 0.0, 1, phi_b, 0)
+        return pb, bias_bar, png_bar, phi_b
 
     def phi_final(self, phi):
         """phi of `evolve`'s context on the final mesh: irfftn(chreshape(rfftn(phi), final_shape)) (model.py:869)."""
@@ -333,9 +381,14 @@ class FieldLevelForward:
             raise ValueError("phi_bar needs a context of a model with png_type set: without it phi = 0")
         cosmo = ctx.cosmo
         gb = nbody._f32(gxy_bar, self.paint_shape)
-        kb = chreshape_vjp(nbody.irfftn_vjp(gb), r2chshape(self.init_shape)) * ctx.jac
-        pb, wb = nbody.nufft_vjp(ctx.pos_c, self.init_shape, ctx.w, kb, self.paint_order, self.interlace_order, self.paint_deconv,
-                                 paint_shape=self.paint_shape)
+        eul = getattr(ctx, "ectx", None) is not None
+        if eul:      # the Lagrangian weights are not painted: their cotangent is zero, lagrangian_bias_vjp still pulls dvel's back
+            pb, ebias_bar, epng_bar, ephi_b = self._eulerian_paint_vjp(ctx, gb)
+            wb = torch.zeros_like(ctx.w)
+        else:
+            kb = chreshape_vjp(nbody.irfftn_vjp(gb), r2chshape(self.init_shape)) * ctx.jac
+            pb, wb = nbody.nufft_vjp(ctx.pos_c, self.init_shape, ctx.w, kb, self.paint_order, self.interlace_order, self.paint_deconv,
+                                     paint_shape=self.paint_shape)
         extra = {}
         if self.ap_auto is None:
             xb, vb, dvb, gfb = bricks.observe_pos_vjp(ctx.octx, pb)
@@ -347,6 +400,13 @@ class FieldLevelForward:
             mesh_b, bias_bar, bg_bar = bricks.lagrangian_bias_vjp(ctx.bctx, wb, dvb)
         else:
             mesh_b, bias_bar, bg_bar, png_bar, _, (phb, lpb) = bricks.lagrangian_bias_vjp(ctx.bctx, wb, dvb, defer_phi=True)
+        if eul:
+            for k in ("b1", "b2", "bs2", "bn2"):
+                bias_bar[k] += ebias_bar[k]
+            if epng_bar is not None:      # the advected phi joins the other readers of phi in front of add_png_vjp's one divide by t
+                png_bar["fNL_bp"] += epng_bar["fNL_bp"]
+                png_bar["fNL_bpd"] += epng_bar["fNL_bpd"]
+                phb = phb + ephi_b
         if self.evolution == 'lpt':
             mb, growth = nbody.lpt_vjp(cosmo, ctx.lin_k, ctx.pos0, ctx.a, xb, vb, lpt_order=self.lpt_order, ctx=ctx.nctx)
         else:

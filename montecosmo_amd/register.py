@@ -16,6 +16,7 @@ Schema (key: meaning; * = mandatory)
     lin_kpow                                 (2, N): k and P(k) / sigma8^2
     white_mesh | white_fake                  whitened initial conditions, half-spectrum at r2chshape(init_shape)
     png_type                                 'fNL' | 'bias' (absent / None: no primordial non-Gaussianity)
+    bias_type                                'lagrangian' | 'eulerian' (model.py:68; absent / None: 'lagrangian')
     ap_auto                                  Alcock-Paczynski (model.py:64): True automatic (the catalogue was gridded with cosmo_fid),
                                              False alpha_iso / alpha_ap parameters, absent / None: none
 
@@ -29,7 +30,7 @@ import numpy as np
 
 MANDATORY = ("cell_length", "box_center", "box_rotvec", "init_oversamp", "paint_oversamp", "cosmo_fid", "count_mesh")
 OPTIONAL = ("selec_mesh", "mask_mesh", "n_tracers", "n_randoms", "a_obs", "curved_sky", "paint_order", "interlace_order",
-            "paint_deconv", "kernel_type", "cell_budget", "padding", "lin_kpow", "white_mesh", "white_fake", "png_type", "ap_auto")
+            "paint_deconv", "kernel_type", "cell_budget", "padding", "lin_kpow", "white_mesh", "white_fake", "png_type", "ap_auto", "bias_type")
 
 
 def _flatten(d, prefix=""):
@@ -129,6 +130,8 @@ def model_arguments(reg, **overrides):
             fwd[k] = reg[k]
     if reg.get("png_type") not in (None, "None"):      # 'fNL' or 'bias' (model.py:84); absent or None: no primordial non-Gaussianity
         fwd["png_type"] = str(reg["png_type"])
+    if reg.get("bias_type") not in (None, "None"):     # 'lagrangian' or 'eulerian' (model.py:68); absent or None: the model's default, 'lagrangian'
+        fwd["bias_type"] = str(reg["bias_type"])
     if reg.get("ap_auto") not in (None, "None"):       # True / False (model.py:64); absent or None: no Alcock-Paczynski
         from . import bricks
         v = reg["ap_auto"]
