@@ -320,13 +320,14 @@ int mcpm_bias_weights_f32(mcpm_plan *p, int64_t n, const float *dr, const float 
     if (!p) return MCPM_E_ARG;
     MCPM_REQUIRE(p, n > 0 && dr && s2r && s3r && lr && gr && bias8 && weights && dvel, MCPM_E_ARG, "mcpm_bias_weights_f32: bad argument");
     const Bias8 B{bias8[0], bias8[1], bias8[2], bias8[3], bias8[4], bias8[5], bias8[6], bias8[7]};
-    double *sig = p->reduce, *P, *Q;
-    unsigned *ticket, R;
+    double *sig = p->reduce + MCPM_RED_SCALARS;
+    DetSum s;
     const unsigned nb = (unsigned)((n + 255) / 256);
     StageTimer st_(p, ST_LPT, 60.0 * n);
-    MCPM_TRY(mcpm_det_scratch(p, 1, nb, &P, &Q, &ticket, &R));
-    bias_moment_kernel<<<nb, 256, 0, p->stream>>>(dr, growth, growth_scalar, n, P);
-    det_fold_kernel<<<R, 256, 0, p->stream>>>(P, nb, 1, Q, ticket, 1.0 / (double)n, det_outs(sig));
+    MCPM_TRY(mcpm_det_begin(p, 1, nb, &s));
+    bias_moment_kernel<<<nb, 256, 0, p->stream>>>(dr, growth, growth_scalar, n, s.P);
+    MCPM_LAUNCH_CHECK(p, "bias_moment_kernel");
+    MCPM_TRY(mcpm_det_fold(p, s, 1, 1.0 / (double)n, det_outs_ptrs(DET_STORE, sig)));
     bias_weights_kernel<<<nb, 256, 0, p->stream>>>(dr, s2r, s3r, lr, gr, ges, gcs, growth, growth_scalar, B, sig, n, weights, dvel);
     MCPM_LAUNCH_CHECK(p, "bias_weights_kernel");
     if (sigma2_out) MCPM_HIP(p, hipMemcpyAsync(sigma2_out, sig, sizeof(double), hipMemcpyDeviceToDevice, p->stream));
@@ -345,23 +346,21 @@ int mcpm_bias_weights_vjp_f32(mcpm_plan *p, int64_t n, const float *dr, const fl
     MCPM_REQUIRE(p, n > 0 && dr && s2r && s3r && lr && gr && bias8 && weights_bar && dvel_bar && drb && s2rb && s3rb && lrb && grb && scalars_out,
                  MCPM_E_ARG, "mcpm_bias_weights_vjp_f32: bad argument");
     const Bias8 B{bias8[0], bias8[1], bias8[2], bias8[3], bias8[4], bias8[5], bias8[6], bias8[7]};
-    double *P, *Q;
-    unsigned *ticket, R;
+    DetSum s;
     const unsigned nb = (unsigned)((n + 255) / 256);
     StageTimer st_(p, ST_LPT, 120.0 * n);
-    MCPM_TRY(mcpm_det_scratch(p, 9, nb, &P, &Q, &ticket, &R));      // 9 rows of per-workgroup partials, summed in a fixed order
-    bias_moment_kernel<<<nb, 256, 0, p->stream>>>(dr, growth, growth_scalar, n, P);
-    det_fold_kernel<<<R, 256, 0, p->stream>>>(P, nb, 1, Q, ticket, 1.0 / (double)n, det_outs(scalars_out + 9));
+    MCPM_TRY(mcpm_det_begin(p, 9, nb, &s));      // 9 rows of per-workgroup partials, summed in a fixed order
+    bias_moment_kernel<<<nb, 256, 0, p->stream>>>(dr, growth, growth_scalar, n, s.P);
+    MCPM_LAUNCH_CHECK(p, "bias_moment_kernel");
+    MCPM_TRY(mcpm_det_fold(p, s, 1, 1.0 / (double)n, det_outs_ptrs(DET_STORE, scalars_out + 9)));
     bias_vjp_reduce_kernel<<<nb, 256, 0, p->stream>>>(dr, s2r, s3r, lr, gr, ges, gcs, growth, growth_scalar, B, scalars_out + 9, weights_bar,
-                                                      dvel_bar, n, P);
-    DetOuts o9{};
-    for (int k = 0; k < 9; ++k) o9.p[k] = scalars_out + k;      // [8] = sigma2_bar for now
-    det_fold_kernel<<<R, 256, 0, p->stream>>>(P, nb, 9, Q, ticket, 1.0, o9);
+                                                      dvel_bar, n, s.P);
+    MCPM_LAUNCH_CHECK(p, "bias_vjp_reduce_kernel");
+    MCPM_TRY(mcpm_det_fold(p, s, 9, 1.0, det_outs_row(DET_STORE, scalars_out, 9)));      // [8] = sigma2_bar for now
     bias_vjp_particles_kernel<<<nb, 256, 0, p->stream>>>(dr, s2r, s3r, lr, gr, ges, gcs, growth, growth_scalar, B, scalars_out + 9, scalars_out + 8,
-                                                         weights_bar, dvel_bar, n, drb, s2rb, s3rb, lrb, grb, growth_bar, P);
-    det_fold_kernel<<<R, 256, 0, p->stream>>>(P, nb, 1, Q, ticket, 1.0, det_outs(scalars_out + 8));   // summed growth cotangent
+                                                         weights_bar, dvel_bar, n, drb, s2rb, s3rb, lrb, grb, growth_bar, s.P);
     MCPM_LAUNCH_CHECK(p, "bias_vjp_particles_kernel");
-    return MCPM_OK;
+    return mcpm_det_fold(p, s, 1, 1.0, det_outs_ptrs(DET_STORE, scalars_out + 8));      // summed growth cotangent
 }
 
 // white2lin / lin2white multiplier (bricks.py:149-161): out = in * sqrt(amp * P(|k|)) on the plan's half-spectrum, |k| in h/Mpc

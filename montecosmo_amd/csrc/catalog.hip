@@ -102,6 +102,7 @@ __global__ __launch_bounds__(256) void sky2cart_minmax_kernel(const double *__re
 // one workgroup: out[k] = min (k < 3) / max (k >= 3) over the nblk partials of row k; nblk = 0 leaves +inf / -inf
 __global__ __launch_bounds__(256) void minmax_fold_kernel(const double *__restrict__ P, unsigned nblk, double *__restrict__ out) {
     __shared__ double mm[6][4];
+    P += nblk;      // rows 1..6 of sky2cart_minmax_kernel's partials
 #pragma unroll
     for (int k = 0; k < 6; ++k) {
         double t = k < 3 ? INFINITY : -INFINITY;
@@ -244,20 +245,17 @@ int mcpm_sky2cart_minmax_f64(mcpm_plan *p, const double *ra, const double *dec, 
     MCPM_REQUIRE(p, (ra && dec && z) || n == 0, MCPM_E_ARG, "mcpm_sky2cart_minmax_f64: null coordinate array");
     MCPM_REQUIRE(p, !weights || wsum, MCPM_E_ARG, "mcpm_sky2cart_minmax_f64: weights without an output for their sum");
     const unsigned nb = cat_blocks(n);
-    double *P, *Q;
-    unsigned *ticket, R;
+    DetSum s;
     StageTimer st_(p, ST_AXPY, (weights ? 32.0 : 24.0) * n);
-    MCPM_TRY(mcpm_det_scratch(p, 7, std::max(nb, 1u), &P, &Q, &ticket, &R));
+    // 7 rows of nb partials: row 0 (the weights) is folded, rows 1..6 (minima, maxima) are read by minmax_fold_kernel
+    MCPM_TRY(mcpm_det_begin(p, 7, nb, &s));
     if (wsum && (!weights || n == 0)) MCPM_HIP(p, hipMemsetAsync(wsum, 0, sizeof(double), p->stream));
     if (n > 0) {
-        sky2cart_minmax_kernel<<<nb, 256, 0, p->stream>>>(ra, dec, z, n, atab, chitab, ntab, weights, P);
+        sky2cart_minmax_kernel<<<nb, 256, 0, p->stream>>>(ra, dec, z, n, atab, chitab, ntab, weights, s.P);
         MCPM_LAUNCH_CHECK(p, "sky2cart_minmax_kernel");
-        if (weights) {
-            det_fold_kernel<<<R, 256, 0, p->stream>>>(P, nb, 1, Q, ticket, 1.0, det_outs(wsum));
-            MCPM_LAUNCH_CHECK(p, "det_fold_kernel");
-        }
+        if (weights) MCPM_TRY(mcpm_det_fold(p, s, 1, 1.0, det_outs_ptrs(DET_STORE, wsum)));
     }
-    minmax_fold_kernel<<<1, 256, 0, p->stream>>>(P + nb, nb, minmax6);
+    minmax_fold_kernel<<<1, 256, 0, p->stream>>>(s.P, s.nblk, minmax6);
     MCPM_LAUNCH_CHECK(p, "minmax_fold_kernel");
     return MCPM_OK;
 }
@@ -320,17 +318,12 @@ int mcpm_masked_sum_f64(mcpm_plan *p, const float *mesh, const unsigned char *ma
         return MCPM_OK;
     }
     const unsigned nb = cat_blocks(n);
-    double *P, *Q;
-    unsigned *ticket, R;
+    DetSum s;
     StageTimer st_(p, ST_AXPY, 5.0 * n);
-    MCPM_TRY(mcpm_det_scratch(p, 2, nb, &P, &Q, &ticket, &R));
-    masked_sum_kernel<<<nb, 256, 0, p->stream>>>(mesh, mask, n, P);
+    MCPM_TRY(mcpm_det_begin(p, 2, nb, &s));
+    masked_sum_kernel<<<nb, 256, 0, p->stream>>>(mesh, mask, n, s.P);
     MCPM_LAUNCH_CHECK(p, "masked_sum_kernel");
-    DetOuts o{};
-    o.p[0] = out2, o.p[1] = out2 + 1;
-    det_fold_kernel<<<R, 256, 0, p->stream>>>(P, nb, 2, Q, ticket, 1.0, o);
-    MCPM_LAUNCH_CHECK(p, "det_fold_kernel");
-    return MCPM_OK;
+    return mcpm_det_fold(p, s, 2, 1.0, det_outs_row(DET_STORE, out2, 2));
 }
 
 }  // extern "C"

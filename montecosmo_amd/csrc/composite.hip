@@ -225,28 +225,15 @@ static int lattice_scatter(mcpm_plan *p, const float *xb, const float *vb, float
     return MCPM_OK;
 }
 
-// adds up the K per-workgroup partials a kernel with `nblk` workgroups left in P (reduce_dev.h): *outs[k] += scale sum (NULL: dropped)
-static int det_fold(mcpm_plan *p, const double *P, double *Q, unsigned *ticket, unsigned R, unsigned nblk, int K, double scale,
-                    double *o0, double *o1 = nullptr, double *o2 = nullptr) {
-    DetOuts o{};
-    o.p[0] = o0, o.p[1] = o1, o.p[2] = o2;
-    o.accumulate = 1;
-    det_fold_kernel<<<R, 256, 0, p->stream>>>(P, nblk, K, Q, ticket, scale, o);
-    MCPM_LAUNCH_CHECK(p, "det_fold_kernel");
-    return MCPM_OK;
-}
-
 // out0 += sum_i a[i].F(q_i), out1 += sum_i b[i].F(q_i), added up in a fixed order (deterministic grid sums, reduce_dev.h)
 static int lattice_dot(mcpm_plan *p, const float *meshes3, const float *a, const float *b, double *out0, double *out1) {
     dim3 grid, block;
     lattice_launch(p->g, grid, block);
-    double *P, *Q;
-    unsigned *ticket, R;
-    MCPM_TRY(mcpm_det_scratch(p, 2, grid.x, &P, &Q, &ticket, &R));
-    lattice_dot_kernel<<<grid, block, 0, p->stream>>>(p->g, meshes3, p->M, a, b, P);
+    DetSum s;
+    MCPM_TRY(mcpm_det_begin(p, 2, grid.x, &s));
+    lattice_dot_kernel<<<grid, block, 0, p->stream>>>(p->g, meshes3, p->M, a, b, s.P);
     MCPM_LAUNCH_CHECK(p, "lattice_dot_kernel");
-    MCPM_TRY(det_fold(p, P, Q, ticket, R, grid.x, 2, 1.0, a ? out0 : nullptr, b ? out1 : nullptr));
-    return MCPM_OK;
+    return mcpm_det_fold(p, s, 2, 1.0, det_outs_ptrs(DET_ACCUMULATE, a ? out0 : nullptr, b ? out1 : nullptr));
 }
 
 // out = a x + b y; with_max: also leaves max|out| for the fixed-point paint of `out` (plan->fx_wmax / fx_src)
@@ -699,22 +686,34 @@ static int step_adjoint_particles(mcpm_plan *p, const float *pos_in, const float
     unsigned *fb_max = (hinted && p->paint3_variant == 4) ? p->fx_wmax : nullptr;
     static const int ntp_env = [] { const char *e = getenv("MCPM_NT_PART"); return e ? atoi(e) : 3; }();     // streaming loads / stores: 2.80 -> 2.62 ms at 512^3
     const int ntp = (N < ((int64_t)1 << 23) ? 0 : (ntp_env & 3)) | (mode & MCPM_ADJ_CARRIED_IN) | (carry_out ? MCPM_ADJ_CARRY_OUT : 0);      // (streaming: not for problems that live in the caches)
-    double *P, *Q;      // this launch's per-workgroup partials of (alpha_bar, beta_bar, dg_bar)
-    unsigned *ticket, R;
-    MCPM_TRY(mcpm_det_scratch(p, 3, grid.x, &P, &Q, &ticket, &R));
+    DetSum s;      // this launch's per-workgroup partials of (alpha_bar, beta_bar, dg_bar)
+    MCPM_TRY(mcpm_det_begin(p, 3, grid.x, &s));
 #define ADJ(OR)                                                                                                                   \
     if (layout) step_adjoint_kernel<OR, true><<<grid, block, 0, p->stream>>>(p->g, pos_in, vel_in, pos_bar_src, vel_bar_src, pos_bar, vel_bar, force_meshes, rho_bar, M, a, b, t, \
-                                                           P, fb_next, p->hint_beta, p->hint_tau, (float)dtau_ddg, fb_max, ntp);  \
+                                                           s.P, fb_next, p->hint_beta, p->hint_tau, (float)dtau_ddg, fb_max, ntp);  \
     else step_adjoint_kernel<OR, false><<<grid, block, 0, p->stream>>>(p->g, pos_in, vel_in, pos_bar_src, vel_bar_src, pos_bar, vel_bar, force_meshes, rho_bar, M, a, b, t, \
-                                                           P, fb_next, p->hint_beta, p->hint_tau, (float)dtau_ddg, fb_max, ntp)
+                                                           s.P, fb_next, p->hint_beta, p->hint_tau, (float)dtau_ddg, fb_max, ntp)
     if (paint_order == 2) ADJ(2);
     else if (paint_order == 1) ADJ(1);
     else if (paint_order == 3) ADJ(3);
     else ADJ(4);
 #undef ADJ
     MCPM_LAUNCH_CHECK(p, "step_adjoint_kernel");
-    if (alpha_bar || beta_bar || dg_bar) {
-        MCPM_TRY(det_fold(p, P, Q, ticket, R, grid.x, 3, 1.0, alpha_bar, beta_bar, dg_bar));
+    if (alpha_bar || beta_bar || dg_bar) MCPM_TRY(mcpm_det_fold(p, s, 3, 1.0, det_outs_ptrs(DET_ACCUMULATE, alpha_bar, beta_bar, dg_bar)));
+    return MCPM_OK;
+}
+
+// a stand-alone LPT adjoint: its three scalar cotangents go through plan->reduce to the host (scalar_bars may be NULL), in the host's signs
+static int lpt_vjp_host(mcpm_plan *p, const float *init_mesh, int lpt_order, const double *lpt_scalars, const float *dpos_bar, const float *vel_bar,
+                        float *init_mesh_bar, int lap_fd, int grad_fd, const float *saved, double *scalar_bars) {
+    double *sb = p->reduce + MCPM_RED_SCALARS;
+    MCPM_HIP(p, hipMemsetAsync(sb, 0, sizeof(double) * 3, p->stream));
+    MCPM_TRY(lpt_vjp_device(p, init_mesh, lpt_order, lpt_scalars, dpos_bar, vel_bar, init_mesh_bar, sb, lap_fd, grad_fd, saved));
+    if (scalar_bars) {
+        MCPM_HIP(p, hipMemcpyAsync(scalar_bars, sb, sizeof(double) * 3, hipMemcpyDeviceToHost, p->stream));
+        MCPM_HIP(p, hipStreamSynchronize(p->stream));
+        scalar_bars[1] = -scalar_bars[1];
+        scalar_bars[2] = -scalar_bars[2];
     }
     return MCPM_OK;
 }
@@ -726,15 +725,7 @@ int mcpm_lpt_vjp_f32(mcpm_plan *p, const float *init_mesh, int lpt_order, const 
     if (!p) return MCPM_E_ARG;
     MCPM_REQUIRE(p, init_mesh && lpt_scalars && dpos_bar && vel_bar && init_mesh_bar, MCPM_E_ARG, "mcpm_lpt_vjp_f32: null argument");
     MCPM_REQUIRE(p, lpt_order == 1 || lpt_order == 2, MCPM_E_ORDER, "mcpm_lpt_vjp_f32: lpt_order must be 1 or 2");
-    MCPM_HIP(p, hipMemsetAsync(p->reduce, 0, sizeof(double) * 3, p->stream));
-    MCPM_TRY(lpt_vjp_device(p, init_mesh, lpt_order, lpt_scalars, dpos_bar, vel_bar, init_mesh_bar, p->reduce));
-    if (scalar_bars) {
-        MCPM_HIP(p, hipMemcpyAsync(scalar_bars, p->reduce, sizeof(double) * 3, hipMemcpyDeviceToHost, p->stream));
-        MCPM_HIP(p, hipStreamSynchronize(p->stream));
-        scalar_bars[1] = -scalar_bars[1];
-        scalar_bars[2] = -scalar_bars[2];
-    }
-    return MCPM_OK;
+    return lpt_vjp_host(p, init_mesh, lpt_order, lpt_scalars, dpos_bar, vel_bar, init_mesh_bar, MCPM_FD_INF, MCPM_FD_INF, nullptr, scalar_bars);
 }
 
 // mcpm_lpt_f32 that also leaves its force and Hessian meshes in `save` (3 M floats for lpt_order 1, 12 M for 2), and the adjoint that
@@ -752,15 +743,7 @@ int mcpm_lpt_vjp_saved_f32(mcpm_plan *p, const float *init_mesh, int lpt_order, 
     if (!p) return MCPM_E_ARG;
     MCPM_REQUIRE(p, init_mesh && lpt_scalars && saved && dpos_bar && vel_bar && init_mesh_bar, MCPM_E_ARG, "mcpm_lpt_vjp_saved_f32: null argument");
     MCPM_REQUIRE(p, lpt_order == 1 || lpt_order == 2, MCPM_E_ORDER, "mcpm_lpt_vjp_saved_f32: lpt_order must be 1 or 2");
-    MCPM_HIP(p, hipMemsetAsync(p->reduce, 0, sizeof(double) * 3, p->stream));
-    MCPM_TRY(lpt_vjp_device(p, init_mesh, lpt_order, lpt_scalars, dpos_bar, vel_bar, init_mesh_bar, p->reduce, MCPM_FD_INF, MCPM_FD_INF, saved));
-    if (scalar_bars) {
-        MCPM_HIP(p, hipMemcpyAsync(scalar_bars, p->reduce, sizeof(double) * 3, hipMemcpyDeviceToHost, p->stream));
-        MCPM_HIP(p, hipStreamSynchronize(p->stream));
-        scalar_bars[1] = -scalar_bars[1];
-        scalar_bars[2] = -scalar_bars[2];
-    }
-    return MCPM_OK;
+    return lpt_vjp_host(p, init_mesh, lpt_order, lpt_scalars, dpos_bar, vel_bar, init_mesh_bar, MCPM_FD_INF, MCPM_FD_INF, saved, scalar_bars);
 }
 
 int mcpm_lpt_vjp_opts_f32(mcpm_plan *p, const float *init_mesh, int lpt_order, const double *lpt_scalars, int lap_fd, int grad_fd,
@@ -768,15 +751,7 @@ int mcpm_lpt_vjp_opts_f32(mcpm_plan *p, const float *init_mesh, int lpt_order, c
     if (!p) return MCPM_E_ARG;
     MCPM_REQUIRE(p, init_mesh && lpt_scalars && dpos_bar && vel_bar && init_mesh_bar, MCPM_E_ARG, "mcpm_lpt_vjp_opts_f32: null argument");
     MCPM_REQUIRE(p, lpt_order == 1 || lpt_order == 2, MCPM_E_ORDER, "mcpm_lpt_vjp_opts_f32: lpt_order must be 1 or 2");
-    MCPM_HIP(p, hipMemsetAsync(p->reduce, 0, sizeof(double) * 3, p->stream));
-    MCPM_TRY(lpt_vjp_device(p, init_mesh, lpt_order, lpt_scalars, dpos_bar, vel_bar, init_mesh_bar, p->reduce, lap_fd, grad_fd));
-    if (scalar_bars) {
-        MCPM_HIP(p, hipMemcpyAsync(scalar_bars, p->reduce, sizeof(double) * 3, hipMemcpyDeviceToHost, p->stream));
-        MCPM_HIP(p, hipStreamSynchronize(p->stream));
-        scalar_bars[1] = -scalar_bars[1];
-        scalar_bars[2] = -scalar_bars[2];
-    }
-    return MCPM_OK;
+    return lpt_vjp_host(p, init_mesh, lpt_order, lpt_scalars, dpos_bar, vel_bar, init_mesh_bar, lap_fd, grad_fd, nullptr, scalar_bars);
 }
 
 // VJP of pm_forces(pos, mesh_shape, order, paint_deconv, grad_fd, lap_fd) w.r.t. pos (painted case, nbody.py:583-604)
@@ -910,7 +885,7 @@ int mcpm_nbody_bf_vjp_f32(mcpm_plan *p, const float *init_mesh, int n_steps, con
     if (!p) return MCPM_E_ARG;
     MCPM_REQUIRE(p, init_mesh && alpha && beta && lpt_scalars && ckpt && pos_bar && vel_bar && init_mesh_bar, MCPM_E_ARG,
                  "mcpm_nbody_bf_vjp_f32: null argument");
-    MCPM_REQUIRE(p, n_steps >= 1 && 2 * n_steps + 4 <= MCPM_NREDUCE, MCPM_E_ARG, "mcpm_nbody_bf_vjp_f32: bad n_steps");
+    MCPM_REQUIRE(p, n_steps >= 1 && 2 * n_steps + MCPM_RED_SWEEP_TAIL <= MCPM_NREDUCE - MCPM_RED_SWEEP, MCPM_E_ARG, "mcpm_nbody_bf_vjp_f32: bad n_steps");
     MCPM_REQUIRE(p, paint_order >= 1 && paint_order <= 4, MCPM_E_ORDER, "mcpm_nbody_bf_vjp_f32: paint_order must be 1..4");
     MCPM_REQUIRE(p, lpt_order == 1 || lpt_order == 2, MCPM_E_ORDER, "mcpm_nbody_bf_vjp_f32: lpt_order must be 1 or 2");
     const int64_t N = p->Np, M = p->M;
@@ -920,33 +895,35 @@ int mcpm_nbody_bf_vjp_f32(mcpm_plan *p, const float *init_mesh, int n_steps, con
     auto state_x = [&](int i) { return ckpt + (int64_t)(2 * i) * pitch; };
     auto state_v = [&](int i) { return ckpt + (int64_t)(2 * i + 1) * pitch; };
     auto force_m = [&](int i) { return ckpt + (int64_t)n_steps * 2 * mcpm_pitch_max(p) + (int64_t)i * 3 * M; };
-    MCPM_HIP(p, hipMemsetAsync(p->reduce, 0, sizeof(double) * (2 * n_steps + 4), p->stream));
+    // the sweep's rows of plan->reduce (the map in mcpm_internal.h), in the order of scalar_bars
+    double *alpha_bar = p->reduce + MCPM_RED_SWEEP, *beta_bar = alpha_bar + n_steps, *lpt_bar = beta_bar + n_steps, *dg_bar = lpt_bar + 3;
+    const size_t nbars = 2 * (size_t)n_steps + MCPM_RED_SWEEP_TAIL;
+    MCPM_HIP(p, hipMemsetAsync(alpha_bar, 0, sizeof(double) * nbars, p->stream));
     p->fb_valid = 0;
     for (int i = n_steps - 1; i >= 0; --i) {
         if (i > 0) MCPM_TRY(mcpm_plan_hint_next_adjoint(p, beta[i - 1], dg));
         // the first reverse step READS the loss cotangents where the caller has them and writes the running ones (no copy of 24 N bytes)
         const bool first = i == n_steps - 1;
         MCPM_TRY(mcpm_bullfrog_step_vjp_from_f32(p, state_x(i), state_v(i), force_m(i), alpha[i], beta[i], first ? dg / 2 : dg, paint_order,
-                                                 first ? pos_bar : xb, first ? vel_bar : vb, xb, vb, p->reduce + i, p->reduce + n_steps + i,
-                                                 first ? 0.5 : 1.0, p->reduce + 2 * n_steps + 3));
+                                                 first ? pos_bar : xb, first ? vel_bar : vb, xb, vb, alpha_bar + i, beta_bar + i,
+                                                 first ? 0.5 : 1.0, dg_bar));
     }
     // initial half drift x'_0 = x_0 + v_0 dg/2 (its explicit dg dependence: <x_bar, v_0> / 2)
     {
         unsigned nbk = (unsigned)((3 * N + 255) / 256);
-        double *P, *Q;
-        unsigned *ticket, R;
-        MCPM_TRY(mcpm_det_scratch(p, 1, nbk, &P, &Q, &ticket, &R));
-        dot_partial_kernel<<<nbk, 256, 0, p->stream>>>(xb, state_v(0), 3 * N, P);
+        DetSum s;
+        MCPM_TRY(mcpm_det_begin(p, 1, nbk, &s));
+        dot_partial_kernel<<<nbk, 256, 0, p->stream>>>(xb, state_v(0), 3 * N, s.P);
         MCPM_LAUNCH_CHECK(p, "dot_partial_kernel");
-        MCPM_TRY(det_fold(p, P, Q, ticket, R, nbk, 1, 0.5, p->reduce + 2 * n_steps + 3));
+        MCPM_TRY(mcpm_det_fold(p, s, 1, 0.5, det_outs_ptrs(DET_ACCUMULATE, dg_bar)));
     }
     MCPM_TRY(axpby(p, vb, xb, 3 * N, 1.f, (float)(dg / 2), vb));
 
     // ---- adjoint of lpt (nbody.py:634-667) at the lattice, read_order = 1
-    MCPM_TRY(lpt_vjp_device(p, init_mesh, lpt_order, lpt_scalars, xb, vb, init_mesh_bar, p->reduce + 2 * n_steps, MCPM_FD_INF, MCPM_FD_INF,
+    MCPM_TRY(lpt_vjp_device(p, init_mesh, lpt_order, lpt_scalars, xb, vb, init_mesh_bar, lpt_bar, MCPM_FD_INF, MCPM_FD_INF,
                             ckpt + ckpt_lpt_offset(p, n_steps)));
     if (scalar_bars) {
-        MCPM_HIP(p, hipMemcpyAsync(scalar_bars, p->reduce, sizeof(double) * (2 * n_steps + 4), hipMemcpyDeviceToHost, p->stream));
+        MCPM_HIP(p, hipMemcpyAsync(scalar_bars, alpha_bar, sizeof(double) * nbars, hipMemcpyDeviceToHost, p->stream));
         MCPM_HIP(p, hipStreamSynchronize(p->stream));
         scalar_bars[2 * n_steps + 1] = -scalar_bars[2 * n_steps + 1];
         scalar_bars[2 * n_steps + 2] = -scalar_bars[2 * n_steps + 2];

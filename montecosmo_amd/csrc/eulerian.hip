@@ -171,22 +171,15 @@ int mcpm_eulerian_bias_f32(mcpm_plan *p, const float *matter_k, const float *phi
     eul_lap_phi_kernel<<<nbh, 256, 0, p->stream>>>(p->g, kpx, kpy, kpz, scale, (const float2 *)matter_k, (const float2 *)phi_k, (float2 *)spec, Mh);
     MCPM_LAUNCH_CHECK(p, "eul_lap_phi_kernel");
     MCPM_TRY(mcpm_fft_c2r(p, spec, saved + 6 * M, phi_k ? 2 : 1));
-    double *P, *Q;
-    unsigned *ticket, R;
-    MCPM_TRY(mcpm_det_scratch(p, 2, nb, &P, &Q, &ticket, &R));
-    DetOuts o2{};
-    o2.p[0] = moments;
-    o2.p[1] = moments + 1;
+    DetSum s;
+    MCPM_TRY(mcpm_det_begin(p, 2, nb, &s));
     StageTimer st_(p, ST_LPT, (phi_k ? 44.0 : 36.0) * M);      // moments: 1 (2) floats in; weights: 7 (8) in, 1 out
-    if (phi_k) {
-        eul_moment_kernel<true><<<nb, 256, 0, p->stream>>>(saved, M, P);
-        det_fold_kernel<<<R, 256, 0, p->stream>>>(P, nb, 2, Q, ticket, 1.0 / (double)M, o2);
-        eul_weights_kernel<true><<<nb, 256, 0, p->stream>>>(saved, M, B, moments, w);
-    } else {
-        eul_moment_kernel<false><<<nb, 256, 0, p->stream>>>(saved, M, P);
-        det_fold_kernel<<<R, 256, 0, p->stream>>>(P, nb, 2, Q, ticket, 1.0 / (double)M, o2);
-        eul_weights_kernel<false><<<nb, 256, 0, p->stream>>>(saved, M, B, moments, w);
-    }
+    if (phi_k) eul_moment_kernel<true><<<nb, 256, 0, p->stream>>>(saved, M, s.P);
+    else eul_moment_kernel<false><<<nb, 256, 0, p->stream>>>(saved, M, s.P);
+    MCPM_LAUNCH_CHECK(p, "eul_moment_kernel");
+    MCPM_TRY(mcpm_det_fold(p, s, 2, 1.0 / (double)M, det_outs_row(DET_STORE, moments, 2)));
+    if (phi_k) eul_weights_kernel<true><<<nb, 256, 0, p->stream>>>(saved, M, B, moments, w);
+    else eul_weights_kernel<false><<<nb, 256, 0, p->stream>>>(saved, M, B, moments, w);
     MCPM_LAUNCH_CHECK(p, "eul_weights_kernel");
     return MCPM_OK;
 }
@@ -204,24 +197,20 @@ int mcpm_eulerian_bias_vjp_f32(mcpm_plan *p, const float *saved, const double *m
     const float scale = 1.f / (float)M;
     const Coef6 B{coef6[0], coef6[1], coef6[2], coef6[3], coef6[4], coef6[5]};
     float *spec = p->spec, *r = p->fmesh;      // scratch: up to 6 plain spectra, 8 of the 9 real meshes
-    double *P, *Q, *mbar = p->reduce;
-    unsigned *ticket, R;
-    MCPM_TRY(mcpm_det_scratch(p, 8, nb, &P, &Q, &ticket, &R));
-    DetOuts o8{};
-    for (int k = 0; k < 6; ++k) o8.p[k] = coef_bar + k;
+    double *mbar = p->reduce + MCPM_RED_SCALARS;
+    DetSum s;
+    MCPM_TRY(mcpm_det_begin(p, 8, nb, &s));
+    DetOuts o8 = det_outs_row(DET_STORE, coef_bar, 6);
     o8.p[6] = mbar;
     o8.p[7] = mbar + 1;
     {
         StageTimer st_(p, ST_LPT, (has_phi ? 100.0 : 88.0) * M);      // pass 1: 8 (9) floats in; pass 2: 7 (8) in, 7 (8) out
-        if (has_phi) {
-            eul_vjp_reduce_kernel<true><<<nb, 256, 0, p->stream>>>(saved, M, B, moments, w_bar, P);
-            det_fold_kernel<<<R, 256, 0, p->stream>>>(P, nb, 8, Q, ticket, 1.0, o8);
-            eul_vjp_cells_kernel<true><<<nb, 256, 0, p->stream>>>(saved, M, B, mbar, w_bar, r);
-        } else {
-            eul_vjp_reduce_kernel<false><<<nb, 256, 0, p->stream>>>(saved, M, B, moments, w_bar, P);
-            det_fold_kernel<<<R, 256, 0, p->stream>>>(P, nb, 8, Q, ticket, 1.0, o8);
-            eul_vjp_cells_kernel<false><<<nb, 256, 0, p->stream>>>(saved, M, B, mbar, w_bar, r);
-        }
+        if (has_phi) eul_vjp_reduce_kernel<true><<<nb, 256, 0, p->stream>>>(saved, M, B, moments, w_bar, s.P);
+        else eul_vjp_reduce_kernel<false><<<nb, 256, 0, p->stream>>>(saved, M, B, moments, w_bar, s.P);
+        MCPM_LAUNCH_CHECK(p, "eul_vjp_reduce_kernel");
+        MCPM_TRY(mcpm_det_fold(p, s, 8, 1.0, o8));
+        if (has_phi) eul_vjp_cells_kernel<true><<<nb, 256, 0, p->stream>>>(saved, M, B, mbar, w_bar, r);
+        else eul_vjp_cells_kernel<false><<<nb, 256, 0, p->stream>>>(saved, M, B, mbar, w_bar, r);
         MCPM_LAUNCH_CHECK(p, "eul_vjp_cells_kernel");
     }
     MCPM_TRY(mcpm_fft_r2c(p, r, spec, 6));

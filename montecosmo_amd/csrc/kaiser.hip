@@ -303,19 +303,15 @@ int mcpm_kaiser_sky_vjp_f32(mcpm_plan *p, const float *meshes, const float *phi,
     MCPM_TRY(kaiser_args(p, "mcpm_kaiser_sky_vjp_f32", geom, flags, tables, nchi, ngrow, g_obs, f_obs, b1E, fNL_bp, &a));
     a.vec = a.vec && aligned16(meshes) && aligned16(phi) && aligned16(out_bar) && aligned16(meshes_bar) && aligned16(phi_bar);
     const unsigned nb = (unsigned)((a.nslot + 255) / 256);
-    double *P, *Q;
-    unsigned *ticket, R;
-    MCPM_TRY(mcpm_det_scratch(p, 4, nb, &P, &Q, &ticket, &R));
+    DetSum s;
+    MCPM_TRY(mcpm_det_begin(p, 4, nb, &s));
     StageTimer st_(p, ST_LPT, (8.0 * (a.curved ? 6 : 2) + 4.0 + (phi ? 8.0 : 0.0)) * p->M);
 #define K(C, L, V) \
-    kaiser_sky_vjp_kernel<C, L, V><<<nb, 256, 0, p->stream>>>(a.G, a.tb, a.P, meshes, phi, out_bar, p->M, a.nslot, meshes_bar, phi_bar, P)
+    kaiser_sky_vjp_kernel<C, L, V><<<nb, 256, 0, p->stream>>>(a.G, a.tb, a.P, meshes, phi, out_bar, p->M, a.nslot, meshes_bar, phi_bar, s.P)
     KAISER_DISPATCH(K, a);
 #undef K
-    DetOuts o{};
-    for (int k = 0; k < 4; ++k) o.p[k] = scalars_out + k;
-    det_fold_kernel<<<R, 256, 0, p->stream>>>(P, nb, 4, Q, ticket, 1.0, o);
     MCPM_LAUNCH_CHECK(p, "kaiser_sky_vjp_kernel");
-    return MCPM_OK;
+    return mcpm_det_fold(p, s, 4, 1.0, det_outs_row(DET_STORE, scalars_out, 4));
 }
 
 int mcpm_kaiser_sky_tables_vjp_f32(mcpm_plan *p, const float *meshes, const double *geom, int flags, const double *tables, int nchi, int ngrow,
@@ -326,9 +322,9 @@ int mcpm_kaiser_sky_tables_vjp_f32(mcpm_plan *p, const float *meshes, const doub
     KArgs a;
     MCPM_TRY(kaiser_args(p, "mcpm_kaiser_sky_tables_vjp_f32", geom, flags, tables, nchi, ngrow, 0., 0., b1E, 0., &a));
     const size_t ntot = (size_t)nchi + 2 * (size_t)ngrow;
-    MCPM_REQUIRE(p, ntot + 8 <= 3072 && ntot * sizeof(double) <= 60 * 1024, MCPM_E_ARG, "mcpm_kaiser_sky_tables_vjp_f32: tables exceed the accumulators");
+    MCPM_REQUIRE(p, ntot + MCPM_RED_TABLES_TAIL <= MCPM_RED_TABLES_END - MCPM_RED_TABLES && ntot * sizeof(double) <= 60 * 1024, MCPM_E_ARG, "mcpm_kaiser_sky_tables_vjp_f32: tables exceed the accumulators");
     // integer accumulators and the maxima: the plan's reduction scratch (free between the model-side calls)
-    unsigned long long *acc = reinterpret_cast<unsigned long long *>(p->reduce);
+    unsigned long long *acc = reinterpret_cast<unsigned long long *>(p->reduce + MCPM_RED_TABLES);
     unsigned *mx = reinterpret_cast<unsigned *>(acc + ntot);
     MCPM_HIP(p, hipMemsetAsync(acc, 0, (ntot + 4) * sizeof(double), p->stream));
     const unsigned nb = (unsigned)std::min<int64_t>((p->M + 255) / 256, 2048);

@@ -293,13 +293,6 @@ __global__ __launch_bounds__(256) void lik_fourier_kernel(int nx, int ny, int nz
     block_partial<5>(v, part, gridDim.x, blockIdx.x);
 }
 
-int lik_fold(mcpm_plan *p, double *P, double *Q, unsigned *ticket, unsigned R, unsigned nb, double *sums_out, int K = 5) {
-    DetOuts o{};
-    for (int k = 0; k < K; ++k) o.p[k] = sums_out + k;
-    det_fold_kernel<<<R, 256, 0, p->stream>>>(P, nb, K, Q, ticket, 1.0, o);
-    return MCPM_OK;
-}
-
 }  // namespace
 
 extern "C" {
@@ -309,19 +302,16 @@ int mcpm_lik_real_f32(mcpm_plan *p, int family, int64_t n, const float *obs, con
     if (!p) return MCPM_E_ARG;
     MCPM_REQUIRE(p, n > 0 && n < ((int64_t)1 << 39) && obs && count && count_bar && sums_out, MCPM_E_ARG, "mcpm_lik_real_f32: bad argument");
     MCPM_REQUIRE(p, family == MCPM_LIK_SHASH || family == MCPM_LIK_POISSON, MCPM_E_ARG, "mcpm_lik_real_f32: unknown family");
-    double *P, *Q;
-    unsigned *ticket, R;
+    DetSum s;
     const unsigned nb = (unsigned)((n + 255) / 256);
     StageTimer st_(p, ST_LPT, (family == MCPM_LIK_SHASH ? 400.0 : 40.0) * n);
-    MCPM_TRY(mcpm_det_scratch(p, 5, nb, &P, &Q, &ticket, &R));
+    MCPM_TRY(mcpm_det_begin(p, 5, nb, &s));
     if (family == MCPM_LIK_SHASH)
-        lik_real_kernel<0><<<nb, 256, 0, p->stream>>>(n, obs, count, selec, selec_scalar, mask, s_e, s_ed, s_e2, count_bar, sqsel_bar, P);
+        lik_real_kernel<0><<<nb, 256, 0, p->stream>>>(n, obs, count, selec, selec_scalar, mask, s_e, s_ed, s_e2, count_bar, sqsel_bar, s.P);
     else
-        lik_real_kernel<1><<<nb, 256, 0, p->stream>>>(n, obs, count, selec, selec_scalar, mask, s_e, s_ed, s_e2, count_bar, sqsel_bar, P);
+        lik_real_kernel<1><<<nb, 256, 0, p->stream>>>(n, obs, count, selec, selec_scalar, mask, s_e, s_ed, s_e2, count_bar, sqsel_bar, s.P);
     MCPM_LAUNCH_CHECK(p, "lik_real_kernel");
-    lik_fold(p, P, Q, ticket, R, nb, sums_out);
-    MCPM_LAUNCH_CHECK(p, "det_fold_kernel");
-    return MCPM_OK;
+    return mcpm_det_fold(p, s, 5, 1.0, det_outs_row(DET_STORE, sums_out, 5));
 }
 
 int mcpm_lik_real_phi_f32(mcpm_plan *p, int family, int64_t n, const float *obs, const float *count, const float *selec, float selec_scalar,
@@ -336,16 +326,15 @@ int mcpm_lik_real_phi_f32(mcpm_plan *p, int family, int64_t n, const float *obs,
     MCPM_REQUIRE(p, !phi == !phi_bar, MCPM_E_ARG, "mcpm_lik_real_phi_f32: phi and phi_bar go together");
     MCPM_REQUIRE(p, family != MCPM_LIK_TWO_QUAD || (quad_z && quad_logw && n_quad >= 2 && n_quad <= 512 && !(n_quad & 1)), MCPM_E_ARG,
                  "mcpm_lik_real_phi_f32: two_quad_gauss needs a symmetric rule with an even number of nodes");
-    double *P, *Q;
-    unsigned *ticket, R;
+    DetSum s;
     const unsigned nb = (unsigned)((n + 255) / 256);
     const int nh = n_quad / 2;
     StageTimer st_(p, ST_LPT, (family == MCPM_LIK_SHASH ? 400.0 : family == MCPM_LIK_POISSON ? 40.0 : 60.0 * nh) * n);
-    MCPM_TRY(mcpm_det_scratch(p, 6, nb, &P, &Q, &ticket, &R));
+    MCPM_TRY(mcpm_det_begin(p, 6, nb, &s));
 #define LIK_PHI_LAUNCH(F)                                                                                                                  \
     lik_real_phi_kernel<F><<<nb, 256, 0, p->stream>>>(n, obs, count, selec, selec_scalar, mask, phi, s_e, s_ed, s_e2, s_ep, temp,         \
                                                       quad_z ? quad_z + nh : nullptr, quad_logw ? quad_logw + nh : nullptr, nh, count_bar, \
-                                                      phi_bar, sqsel_bar, P)
+                                                      phi_bar, sqsel_bar, s.P)
     if (family == MCPM_LIK_SHASH)
         LIK_PHI_LAUNCH(0);
     else if (family == MCPM_LIK_POISSON)
@@ -354,9 +343,7 @@ int mcpm_lik_real_phi_f32(mcpm_plan *p, int family, int64_t n, const float *obs,
         LIK_PHI_LAUNCH(2);
 #undef LIK_PHI_LAUNCH
     MCPM_LAUNCH_CHECK(p, "lik_real_phi_kernel");
-    lik_fold(p, P, Q, ticket, R, nb, sums_out, 6);
-    MCPM_LAUNCH_CHECK(p, "det_fold_kernel");
-    return MCPM_OK;
+    return mcpm_det_fold(p, s, 6, 1.0, det_outs_row(DET_STORE, sums_out, 6));
 }
 
 int mcpm_lik_fourier_temp_f32(mcpm_plan *p, const float *Y, const float *obs_rg, float box_x, float box_y, float box_z, float los_x,
@@ -368,19 +355,16 @@ int mcpm_lik_fourier_temp_f32(mcpm_plan *p, const float *Y, const float *obs_rg,
     MCPM_REQUIRE(p, !p->g.xslab, MCPM_E_UNSUPPORTED, "mcpm_lik_fourier_f32: not slab-decomposed");
     const int nx = p->g.nx, ny = p->g.ny, nz = p->g.nz;
     MCPM_REQUIRE(p, !(nx & 1) && !(ny & 1) && !(nz & 1), MCPM_E_SHAPE, "mcpm_lik_fourier_f32: rg2cgh / cgh2rg need even sides");
-    double *P, *Q;
-    unsigned *ticket, R;
+    DetSum s;
     const unsigned nb = (unsigned)((p->Mh + 255) / 256);
     StageTimer st_(p, ST_KSPACE, 24.0 * p->Mh);
-    MCPM_TRY(mcpm_det_scratch(p, 5, nb, &P, &Q, &ticket, &R));
+    MCPM_TRY(mcpm_det_begin(p, 5, nb, &s));
     // sqrt(selec temp) rounded once (it enters every mode alike, so its rounding is a coherent error of the sums); temp = 1: sqrtf(selec)
     const float sq = (float)sqrt((double)selec * (double)temp);
     lik_fourier_kernel<<<nb, 256, 0, p->stream>>>(nx, ny, nz, box_x, box_y, box_z, los_x, los_y, los_z, (const float2 *)Y, obs_rg, sq, s_e,
-                                                  s_k2e, s_kmu2e, sqrtf(temp), (float2 *)Y_bar, P);
+                                                  s_k2e, s_kmu2e, sqrtf(temp), (float2 *)Y_bar, s.P);
     MCPM_LAUNCH_CHECK(p, "lik_fourier_kernel");
-    lik_fold(p, P, Q, ticket, R, nb, sums_out);
-    MCPM_LAUNCH_CHECK(p, "det_fold_kernel");
-    return MCPM_OK;
+    return mcpm_det_fold(p, s, 5, 1.0, det_outs_row(DET_STORE, sums_out, 5));
 }
 
 int mcpm_lik_fourier_f32(mcpm_plan *p, const float *Y, const float *obs_rg, float box_x, float box_y, float box_z, float los_x, float los_y,

@@ -24,7 +24,30 @@
 #define MCPM_STORE_DATA_HAZARD_NOP "s_nop 2"
 
 
-#define MCPM_NREDUCE 6144   // [0, 3072): scalar outputs and the bias / observe slot rows; [3072, 6144): the 3 x MCPM_NSLOT step-adjoint slots (kept zero between uses)
+// MAP OF plan->reduce: MCPM_NREDUCE device doubles for the scalar results of the model-side and adjoint entry points (offsets and extents
+// in doubles).  The table cotangents and the reverse sweep start at 0 and overlay the scalars, the PNG accumulators and each other.  That
+// is safe: every user is one entry point on the plan's one stream, it clears what it accumulates into, and its values are read only by
+// work the same call enqueues behind them (its next kernel, the copy to the caller's buffer), so nothing here is live between two calls.
+enum McpmReduceMap {
+    MCPM_NREDUCE = 6144,
+    // doubles [0, 8).  bias.hip: <d^2> [0]; png.hip: <d^2>, <phi d> [0, 1], S0, S1 [0, 1], the mean of mcpm_png_add_f32 [0]; eulerian.hip: the
+    // two moment cotangents [0, 1]; composite.hip: the three LPT scalar cotangents of mcpm_lpt_vjp*_f32 [0, 3)
+    MCPM_RED_SCALARS = 0,
+    MCPM_RED_NSCALARS = 8,
+    // mcpm_png_add_vjp_f32: ntab <= MCPM_RED_PNG_NTAB 64-bit integer accumulators, then the bits of their maximum; BEHIND the scalars, because
+    // the same call holds S0, S1 there
+    MCPM_RED_PNG_ACC = MCPM_RED_SCALARS + MCPM_RED_NSCALARS,
+    MCPM_RED_PNG_NTAB = 2048,
+    // mcpm_*_tables_vjp_f32 (observe.hip, kaiser.hip): ntot 64-bit integer accumulators, then the maxima (the first 4 slots of the tail),
+    // ntot + MCPM_RED_TABLES_TAIL <= MCPM_RED_TABLES_END - MCPM_RED_TABLES
+    MCPM_RED_TABLES = 0,
+    MCPM_RED_TABLES_TAIL = 8,
+    MCPM_RED_TABLES_END = 3072,
+    // mcpm_nbody_bf_vjp_f32, doubles: alpha_bar[n_steps], beta_bar[n_steps], then the tail (3 LPT scalar cotangents, dg_bar), up to MCPM_NREDUCE
+    MCPM_RED_SWEEP = 0,
+    MCPM_RED_SWEEP_TAIL = 4,
+};
+static_assert(MCPM_RED_PNG_ACC + MCPM_RED_PNG_NTAB + 1 <= MCPM_NREDUCE && MCPM_RED_TABLES_END <= MCPM_NREDUCE, "plan->reduce map");
 #ifndef MCPM_NZPAD
 #define MCPM_NZPAD 16  // complex elements added to the nz/2 pitch of the internal spectra
 #endif
@@ -130,8 +153,9 @@ struct mcpm_plan {
     // measures the candidates on the caller's buffer; mcpm_plan_set_particle_pitch fixes one.
     int64_t ppitch;
     float *vscratch;  // variable-size particle scratch (pm_forces_vjp)
-    double *part;     // per-workgroup partial sums of the deterministic grid reductions (reduce_dev.h), allocated on first use
+    double *part;     // scratch of the deterministic grid sums (reduce.hip lays it out), allocated on first use
     int64_t part_n;
+    int det_stale;    // a HIP error may have kept a fold from resetting its counter: mcpm_det_begin clears it before the next sum
     int64_t vscratch_n;
     float *tw[3];    // twiddle tables exp(-2 pi i j / n) of the hand-written FFT, per axis (x, y, z)
 
@@ -176,9 +200,16 @@ struct StageTimer {
 extern thread_local std::string g_mcpm_create_error;
 
 int mcpm_fail(mcpm_plan *plan, int code, const std::string &msg);
-// Scratch of one deterministic grid reduction (reduce_dev.h): K values from nblk workgroups.  *P: K * nblk partials, *Q: K * R second-level
-// sums, *ticket: zero between launches; *R: workgroups of det_fold_kernel.  (plan.hip)
-int mcpm_det_scratch(mcpm_plan *p, int K, unsigned nblk, double **P, double **Q, unsigned **ticket, unsigned *R);
+// One deterministic f64 grid sum (reduce.hip).  mcpm_det_begin: room for K rows of partials from nblk workgroups; the producer kernel leaves
+// row k at P[k * nblk + block] (reduce_dev.h::block_partial).  mcpm_det_fold: adds up rows 0 .. K-1 (K at most the begin's) in a fixed order
+// and leaves scale * sum where `outs` says (det_outs_row / det_outs_ptrs).  A begin invalidates the plan's earlier sum.
+struct DetOuts;
+struct DetSum {
+    double *P;
+    unsigned nblk;
+};
+int mcpm_det_begin(mcpm_plan *p, int K, unsigned nblk, DetSum *s);
+int mcpm_det_fold(mcpm_plan *p, const DetSum &s, int K, double scale, const DetOuts &outs);
 void mcpm_slab_state_free(mcpm_plan *p);   // slab.hip
 #define MCPM_PITCH_MAX_SHIFT 17472      // floats: 64 KB + 4 KB + 256 B, the largest candidate shift between particle arrays
 static inline int64_t mcpm_pitch_max(const mcpm_plan *p) { return 3 * p->Np + MCPM_PITCH_MAX_SHIFT; }

@@ -497,20 +497,16 @@ int mcpm_observe_pos_ap_vjp_f32(mcpm_plan *p, const float *pos, const float *vel
     MCPM_TRY(make_ap(p, "mcpm_observe_pos_ap_vjp_f32", og.curved, og.lightcone, nchi, ap_mode, alpha_iso, alpha_ap, ap_tables, nap, nfid, &ap));
     Tables tb{tables, tables ? tables + nchi : nullptr, tables ? tables + 2 * nchi : nullptr,
               tables ? tables + 2 * nchi + ngrow : nullptr, tables ? tables + 2 * nchi + 2 * ngrow : nullptr};
-    double *P, *Q;
-    unsigned *ticket, R;
+    DetSum s;
     const unsigned nb = (unsigned)((n + 255) / 256);
     const int nred = ap_mode == MCPM_AP_NONE ? 1 : 3;
     StageTimer st_(p, ST_LPT, (dvel ? 84.0 : 60.0) * n);
-    MCPM_TRY(mcpm_det_scratch(p, nred, nb, &P, &Q, &ticket, &R));
-#define K(MO, AP) observe_vjp_kernel<MO, AP><<<nb, 256, 0, p->stream>>>(p->g, og, tb, ap, pos, vel, dvel, n, out_bar, pos_bar, vel_bar, dvel_bar, P)
+    MCPM_TRY(mcpm_det_begin(p, nred, nb, &s));
+#define K(MO, AP) observe_vjp_kernel<MO, AP><<<nb, 256, 0, p->stream>>>(p->g, og, tb, ap, pos, vel, dvel, n, out_bar, pos_bar, vel_bar, dvel_bar, s.P)
     OBS_DISPATCH(K, mode, ap_mode);
 #undef K
-    DetOuts outs = det_outs(gf_bar);
-    if (nred == 3) outs.p[1] = alpha_bar, outs.p[2] = alpha_bar + 1;
-    det_fold_kernel<<<R, 256, 0, p->stream>>>(P, nb, nred, Q, ticket, 1.0, outs);
     MCPM_LAUNCH_CHECK(p, "observe_vjp_kernel");
-    return MCPM_OK;
+    return mcpm_det_fold(p, s, nred, 1.0, nred == 3 ? det_outs_ptrs(DET_STORE, gf_bar, alpha_bar, alpha_bar + 1) : det_outs_ptrs(DET_STORE, gf_bar));
 }
 
 int mcpm_observe_pos_vjp_f32(mcpm_plan *p, const float *pos, const float *vel, const float *dvel, int64_t n, int mode,
@@ -529,9 +525,9 @@ int mcpm_lightcone_tables_vjp_f32(mcpm_plan *p, const float *r0, int64_t n, cons
     if (!p) return MCPM_E_ARG;
     MCPM_REQUIRE(p, r0 && tables && g_bar && table_bar && n > 0 && nchi >= 2 && ngrow >= 2, MCPM_E_ARG, "mcpm_lightcone_tables_vjp_f32: bad argument");
     const size_t ntot = (size_t)nchi + 4 * (size_t)ngrow;
-    MCPM_REQUIRE(p, ntot + 8 <= 3072 && ntot * sizeof(double) <= 60 * 1024, MCPM_E_ARG, "mcpm_lightcone_tables_vjp_f32: tables exceed the accumulators");
+    MCPM_REQUIRE(p, ntot + MCPM_RED_TABLES_TAIL <= MCPM_RED_TABLES_END - MCPM_RED_TABLES && ntot * sizeof(double) <= 60 * 1024, MCPM_E_ARG, "mcpm_lightcone_tables_vjp_f32: tables exceed the accumulators");
     // integer accumulators and the maxima: the plan's reduction scratch (free between the model-side calls)
-    unsigned long long *acc = reinterpret_cast<unsigned long long *>(p->reduce);
+    unsigned long long *acc = reinterpret_cast<unsigned long long *>(p->reduce + MCPM_RED_TABLES);
     unsigned *mx = reinterpret_cast<unsigned *>(acc + ntot);
     MCPM_HIP(p, hipMemsetAsync(acc, 0, (ntot + 4) * sizeof(double), p->stream));
     const unsigned nb = (unsigned)std::min<int64_t>((n + 255) / 256, 2048);
@@ -557,13 +553,13 @@ int mcpm_observe_pos_ap_tables_vjp_f32(mcpm_plan *p, const float *pos, const flo
     MCPM_REQUIRE(p, !lc || (tables && nchi >= 2 && ngrow >= 2), MCPM_E_ARG, "mcpm_observe_pos_ap_tables_vjp_f32: light cone needs the tables");
     if (!lc) nchi = nap, ngrow = 0;      // the accumulator's layout: the Alcock-Paczynski look-up's chi nodes alone
     const size_t ntot = (size_t)nchi + 2 * (size_t)ngrow;
-    MCPM_REQUIRE(p, ntot + 8 <= 3072 && ntot * sizeof(double) <= 60 * 1024, MCPM_E_ARG, "mcpm_observe_pos_ap_tables_vjp_f32: tables exceed the accumulators");
+    MCPM_REQUIRE(p, ntot + MCPM_RED_TABLES_TAIL <= MCPM_RED_TABLES_END - MCPM_RED_TABLES && ntot * sizeof(double) <= 60 * 1024, MCPM_E_ARG, "mcpm_observe_pos_ap_tables_vjp_f32: tables exceed the accumulators");
     Obs og = make_obs(p, geom, flags, nchi, ngrow);
     Ap ap;
     MCPM_TRY(make_ap(p, "mcpm_observe_pos_ap_tables_vjp_f32", og.curved, og.lightcone, nchi, ap_mode, alpha_iso, alpha_ap, ap_tables, nap, nfid, &ap));
     Tables tb{tables, tables ? tables + nchi : nullptr, tables ? tables + 2 * nchi : nullptr,
               tables ? tables + 2 * nchi + ngrow : nullptr, tables ? tables + 2 * nchi + 2 * ngrow : nullptr};
-    unsigned long long *acc = reinterpret_cast<unsigned long long *>(p->reduce);
+    unsigned long long *acc = reinterpret_cast<unsigned long long *>(p->reduce + MCPM_RED_TABLES);
     unsigned *mx = reinterpret_cast<unsigned *>(acc + ntot);
     MCPM_HIP(p, hipMemsetAsync(acc, 0, (ntot + 4) * sizeof(double), p->stream));
     const unsigned nb = (unsigned)std::min<int64_t>((n + 255) / 256, 2048);

@@ -7,10 +7,12 @@
 thread_local std::string g_mcpm_create_error;
 
 int mcpm_fail(mcpm_plan *plan, int code, const std::string &msg) {
-    if (plan)
+    if (plan) {
         plan->err = msg;
-    else
+        if (code == MCPM_E_HIP) plan->det_stale = 1;      // a deterministic sum may not have run to its end (reduce.hip)
+    } else {
         g_mcpm_create_error = msg;
+    }
     return code;
 }
 
@@ -141,6 +143,7 @@ static int plan_create_impl(int nx, int ny, int nz, int px, int py, int pz, int 
     p->ppitch = 0;
     p->part = nullptr;
     p->part_n = 0;
+    p->det_stale = 0;
     p->vscratch = nullptr;
     p->vscratch_n = 0;
     p->tw[0] = p->tw[1] = p->tw[2] = nullptr;
@@ -181,7 +184,7 @@ static int plan_create_impl(int nx, int ny, int nz, int px, int py, int pz, int 
     }
     (void)hipMemsetAsync(p->outlier_count, 0, sizeof(int) * 8, p->stream);
     (void)hipMemsetAsync(p->fx_redo, 0, sizeof(int), p->stream);
-    (void)hipMemsetAsync(p->reduce, 0, sizeof(double) * MCPM_NREDUCE, p->stream);   // the slot area stays zero between uses
+    (void)hipMemsetAsync(p->reduce, 0, sizeof(double) * MCPM_NREDUCE, p->stream);
     *out = p;
     return MCPM_OK;
 }
@@ -246,34 +249,6 @@ int mcpm_plan_set_centre(mcpm_plan *p, int centre) {
     p->centre = centre ? 1 : 0;
     return MCPM_OK;
 }
-
-}  // extern "C"
-
-int mcpm_det_scratch(mcpm_plan *p, int K, unsigned nblk, double **P, double **Q, unsigned **ticket, unsigned *R) {
-    // Few first-stage workgroups: each ends with one atomic on the shared ticket, and those serialise at ~27 ns apiece (1024 of them:
-    // 34 us per fold at 512^3, against 23 us with 256); 128 workgroups still pull 12.6 MB of partials in a few microseconds.
-    const unsigned r = std::max(1u, std::min(128u, (nblk + 511u) / 512u));
-    // [ticket (one double slot, kept zero)] [Q: K * 1024] [P: K * nblk]
-    const int64_t need = 1 + (int64_t)K * 1024 + (int64_t)K * nblk;
-    if (p->part_n < need) {
-        if (p->part) {
-            MCPM_HIP(p, hipStreamSynchronize(p->stream));
-            (void)hipFree(p->part);
-            p->part = nullptr;
-        }
-        const int64_t n = need + need / 4;
-        if (hipMalloc((void **)&p->part, sizeof(double) * n) != hipSuccess) return mcpm_fail(p, MCPM_E_NOMEM, "reduction scratch");
-        p->part_n = n;
-        MCPM_HIP(p, hipMemsetAsync(p->part, 0, sizeof(double), p->stream));
-    }
-    *ticket = reinterpret_cast<unsigned *>(p->part);
-    *Q = p->part + 1;
-    *P = p->part + 1 + (int64_t)K * 1024;
-    *R = r;
-    return MCPM_OK;
-}
-
-extern "C" {
 
 int mcpm_plan_last_bucketed(mcpm_plan *p, int64_t *count) {
     if (!p || !count) return MCPM_E_ARG;

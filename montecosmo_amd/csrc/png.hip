@@ -356,15 +356,14 @@ int mcpm_png_weights_f32(mcpm_plan *p, int64_t n, const float *dr, const float *
     if (!p) return MCPM_E_ARG;
     MCPM_REQUIRE(p, n > 0 && dr && s2r && ph && lp && png5 && weights, MCPM_E_ARG, "mcpm_png_weights_f32: bad argument");
     const Png5 B{png5[0], png5[1], png5[2], png5[3], png5[4]};
-    double *mom = p->reduce, *P, *Q;
-    unsigned *ticket, R;
+    double *mom = p->reduce + MCPM_RED_SCALARS;
+    DetSum s;
     const unsigned nb = (unsigned)((n + 255) / 256);
     StageTimer st_(p, ST_LPT, 40.0 * n);
-    MCPM_TRY(mcpm_det_scratch(p, 2, nb, &P, &Q, &ticket, &R));
-    png_w_moment_kernel<<<nb, 256, 0, p->stream>>>(dr, ph, growth, growth_scalar, n, P);
-    DetOuts o2{};
-    o2.p[0] = mom, o2.p[1] = mom + 1;
-    det_fold_kernel<<<R, 256, 0, p->stream>>>(P, nb, 2, Q, ticket, 1.0 / (double)n, o2);
+    MCPM_TRY(mcpm_det_begin(p, 2, nb, &s));
+    png_w_moment_kernel<<<nb, 256, 0, p->stream>>>(dr, ph, growth, growth_scalar, n, s.P);
+    MCPM_LAUNCH_CHECK(p, "png_w_moment_kernel");
+    MCPM_TRY(mcpm_det_fold(p, s, 2, 1.0 / (double)n, det_outs_row(DET_STORE, mom, 2)));
     png_weights_kernel<<<nb, 256, 0, p->stream>>>(dr, s2r, ph, lp, growth, growth_scalar, B, mom, n, weights);
     MCPM_LAUNCH_CHECK(p, "png_weights_kernel");
     if (moments_out) MCPM_HIP(p, hipMemcpyAsync(moments_out, mom, 2 * sizeof(double), hipMemcpyDeviceToDevice, p->stream));
@@ -380,24 +379,21 @@ int mcpm_png_weights_vjp_f32(mcpm_plan *p, int64_t n, const float *dr, const flo
     MCPM_REQUIRE(p, n > 0 && dr && s2r && ph && lp && png5 && weights_bar && drb && s2rb && phb && lpb && scalars_out, MCPM_E_ARG,
                  "mcpm_png_weights_vjp_f32: bad argument");
     const Png5 B{png5[0], png5[1], png5[2], png5[3], png5[4]};
-    double *P, *Q, *mom = scalars_out + 8;
-    unsigned *ticket, R;
+    double *mom = scalars_out + 8;
+    DetSum s;
     const unsigned nb = (unsigned)((n + 255) / 256);
     StageTimer st_(p, ST_LPT, 80.0 * n);
-    MCPM_TRY(mcpm_det_scratch(p, 7, nb, &P, &Q, &ticket, &R));
-    png_w_moment_kernel<<<nb, 256, 0, p->stream>>>(dr, ph, growth, growth_scalar, n, P);
-    DetOuts o2{};
-    o2.p[0] = mom, o2.p[1] = mom + 1;
-    det_fold_kernel<<<R, 256, 0, p->stream>>>(P, nb, 2, Q, ticket, 1.0 / (double)n, o2);
-    png_w_vjp_reduce_kernel<<<nb, 256, 0, p->stream>>>(dr, s2r, ph, lp, growth, growth_scalar, B, mom, weights_bar, n, P);
-    DetOuts o7{};
-    for (int k = 0; k < 7; ++k) o7.p[k] = scalars_out + k;
-    det_fold_kernel<<<R, 256, 0, p->stream>>>(P, nb, 7, Q, ticket, 1.0, o7);
+    MCPM_TRY(mcpm_det_begin(p, 7, nb, &s));
+    png_w_moment_kernel<<<nb, 256, 0, p->stream>>>(dr, ph, growth, growth_scalar, n, s.P);
+    MCPM_LAUNCH_CHECK(p, "png_w_moment_kernel");
+    MCPM_TRY(mcpm_det_fold(p, s, 2, 1.0 / (double)n, det_outs_row(DET_STORE, mom, 2)));
+    png_w_vjp_reduce_kernel<<<nb, 256, 0, p->stream>>>(dr, s2r, ph, lp, growth, growth_scalar, B, mom, weights_bar, n, s.P);
+    MCPM_LAUNCH_CHECK(p, "png_w_vjp_reduce_kernel");
+    MCPM_TRY(mcpm_det_fold(p, s, 7, 1.0, det_outs_row(DET_STORE, scalars_out, 7)));
     png_w_vjp_particles_kernel<<<nb, 256, 0, p->stream>>>(dr, s2r, ph, lp, growth, growth_scalar, B, mom, scalars_out + 5, weights_bar, n, drb, s2rb,
-                                                          phb, lpb, growth_bar, P);
-    det_fold_kernel<<<R, 256, 0, p->stream>>>(P, nb, 1, Q, ticket, 1.0, det_outs(scalars_out + 7));
+                                                          phb, lpb, growth_bar, s.P);
     MCPM_LAUNCH_CHECK(p, "png_w_vjp_particles_kernel");
-    return MCPM_OK;
+    return mcpm_det_fold(p, s, 1, 1.0, det_outs_ptrs(DET_STORE, scalars_out + 7));
 }
 
 int mcpm_png_add_f32(mcpm_plan *p, const float *lin_mesh, float kpx, float kpy, float kpz, const double *ks, const double *trans, int ntab,
@@ -416,13 +412,14 @@ int mcpm_png_add_f32(mcpm_plan *p, const float *lin_mesh, float kpx, float kpy, 
         }
         MCPM_TRY(mcpm_fft_c2r(p, p->spec1, phi, 1));
     }
-    double *mean = p->reduce, *P, *Q;
-    unsigned *ticket, R;
-    MCPM_TRY(mcpm_det_scratch(p, 1, nbr, &P, &Q, &ticket, &R));
+    double *mean = p->reduce + MCPM_RED_SCALARS;
+    DetSum s;
+    MCPM_TRY(mcpm_det_begin(p, 1, nbr, &s));
     {
         StageTimer st_(p, ST_LPT, 12.0 * M);
-        png_moment_kernel<<<nbr, 256, 0, p->stream>>>(phi, M, P);
-        det_fold_kernel<<<R, 256, 0, p->stream>>>(P, nbr, 1, Q, ticket, 1.0 / (double)M, det_outs(mean));
+        png_moment_kernel<<<nbr, 256, 0, p->stream>>>(phi, M, s.P);
+        MCPM_LAUNCH_CHECK(p, "png_moment_kernel");
+        MCPM_TRY(mcpm_det_fold(p, s, 1, 1.0 / (double)M, det_outs_ptrs(DET_STORE, mean)));
         png_quad_kernel<<<nbr, 256, 0, p->stream>>>(phi, fnl, mean, M, p->rho);
         MCPM_LAUNCH_CHECK(p, "png_quad_kernel");
     }
@@ -441,12 +438,12 @@ int mcpm_png_add_vjp_f32(mcpm_plan *p, const float *lin_mesh, const float *out, 
     MCPM_REQUIRE(p, lin_mesh && ks && trans && ntab >= 2 && lin_mesh_bar && fnl_bar && trans_bar, MCPM_E_ARG, "mcpm_png_add_vjp_f32: bad argument");
     MCPM_REQUIRE(p, out_bar ? (out && phi && mean) : (phi_bar != nullptr), MCPM_E_ARG,
                  "mcpm_png_add_vjp_f32: out_bar needs out, phi and mean; without out_bar, phi_bar is the cotangent to pull back");
-    MCPM_REQUIRE(p, ntab <= 2048, MCPM_E_ARG, "mcpm_png_add_vjp_f32: table exceeds the accumulators");
+    MCPM_REQUIRE(p, ntab <= MCPM_RED_PNG_NTAB, MCPM_E_ARG, "mcpm_png_add_vjp_f32: table exceeds the accumulators");
     MCPM_REQUIRE(p, !p->g.xslab, MCPM_E_UNSUPPORTED, "mcpm_png_add_vjp_f32: not slab-decomposed");
     const int64_t M = p->M, Mh = p->Mh;
     const unsigned nbk = (unsigned)((Mh + 255) / 256), nbr = (unsigned)((M + 255) / 256);
-    // plan scalars: [0, 1] = S0, S1;  [8, 8 + ntab) integer accumulators of the table cotangent, then the bits of the maximum
-    unsigned long long *acc = reinterpret_cast<unsigned long long *>(p->reduce + 8);
+    // plan scalars (the map in mcpm_internal.h): S0, S1; behind them ntab integer accumulators of the table cotangent, then the bits of the maximum
+    unsigned long long *acc = reinterpret_cast<unsigned long long *>(p->reduce + MCPM_RED_PNG_ACC);
     unsigned *mx = reinterpret_cast<unsigned *>(acc + ntab);
     const float *psib = phi_bar;      // without out_bar, phi_bar alone is pulled back: no C2R, no sums, fNL_bar = 0
     if (out_bar) {
@@ -457,14 +454,13 @@ int mcpm_png_add_vjp_f32(mcpm_plan *p, const float *lin_mesh, const float *out, 
             MCPM_LAUNCH_CHECK(p, "png_vjp_in_kernel");
         }
         MCPM_TRY(mcpm_fft_c2r(p, p->spec1, pb, 1));
-        double *sums = p->reduce, *P, *Q;
-        unsigned *ticket, R;
-        MCPM_TRY(mcpm_det_scratch(p, 2, nbr, &P, &Q, &ticket, &R));
+        double *sums = p->reduce + MCPM_RED_SCALARS;
+        DetSum s;
+        MCPM_TRY(mcpm_det_begin(p, 2, nbr, &s));
         StageTimer st_(p, ST_LPT, 20.0 * M);
-        png_vjp_sums_kernel<<<nbr, 256, 0, p->stream>>>(phi, pb, M, P);
-        DetOuts o2{};
-        o2.p[0] = sums, o2.p[1] = sums + 1;
-        det_fold_kernel<<<R, 256, 0, p->stream>>>(P, nbr, 2, Q, ticket, 1.0, o2);
+        png_vjp_sums_kernel<<<nbr, 256, 0, p->stream>>>(phi, pb, M, s.P);
+        MCPM_LAUNCH_CHECK(p, "png_vjp_sums_kernel");
+        MCPM_TRY(mcpm_det_fold(p, s, 2, 1.0, det_outs_row(DET_STORE, sums, 2)));
         png_quad_vjp_kernel<<<nbr, 256, 0, p->stream>>>(phi, fnl, mean, sums, M, phi_bar, pb, fnl_bar);
         MCPM_LAUNCH_CHECK(p, "png_quad_vjp_kernel");
         psib = pb;

@@ -1,0 +1,93 @@
+// Second stage of the deterministic f64 grid sums (first stage: reduce_dev.h): the scratch, the fold kernel and its launcher.
+#include <algorithm>
+
+#include "mcpm_internal.h"
+#include "reduce_dev.h"
+
+constexpr unsigned DET_MAXR = 128;      // most workgroups a fold is launched with
+
+// plan->part: [ticket (one unsigned in a double's slot, zero between launches)] [Q: K * DET_MAXR second-level sums] [P: K * nblk partials]
+static unsigned *det_ticket(const mcpm_plan *p) { return reinterpret_cast<unsigned *>(p->part); }
+static double *det_Q(const mcpm_plan *p) { return p->part + 1; }
+// Workgroups of the fold.  Few: each ends with one atomic on the shared ticket, and those serialise at ~27 ns apiece (1024 of them:
+// 34 us per fold at 512^3, against 23 us with 256); 128 workgroups still pull 12.6 MB of partials in a few microseconds.
+static unsigned det_R(unsigned nblk) { return std::max(1u, std::min(DET_MAXR, (nblk + 511u) / 512u)); }
+
+// R workgroups each sum a contiguous range of every row of P into Q[k * R + r]; the last one to finish (the ticket) sums Q and writes the
+// outputs, then zeroes the ticket for the next launch (which is what lets a captured graph replay a fold).  K <= DET_MAXK,
+// R <= DET_MAXR.
+// (The last workgroup's sum over Q is a fixed TREE over 256 lanes, not a serial loop: 256 dependent-latency loads by one lane cost
+// 43 us at 256^3 and 55 us at 512^3 -- `profiles/r04_kernel_stats_*.csv` of the first version -- against 5 us for everything else.)
+__global__ __launch_bounds__(256) void det_fold_kernel(const double *__restrict__ P, unsigned nblk, int K, double *Q, unsigned *ticket, double scale,
+                                                       DetOuts o) {
+    const unsigned R = gridDim.x, r = blockIdx.x, C = (nblk + R - 1) / R, lo = r * C, hi = min(lo + C, nblk);
+    __shared__ double sh[DET_MAXK][4];
+    __shared__ int last;
+    for (int k = 0; k < K; ++k) {
+        // eight independent loads in flight per lane, added in a fixed pattern (one load per iteration is a chain of memory latencies:
+        // 29 us per fold at 512^3, 16 iterations x 3 rows)
+        const double *Pk = P + (size_t)k * nblk;
+        double t = 0.;
+        for (unsigned i = lo + threadIdx.x; i < hi; i += 256 * 8) {
+            double v[8];
+#pragma unroll
+            for (int j = 0; j < 8; ++j) v[j] = i + 256u * j < hi ? Pk[i + 256u * j] : 0.;
+            t += ((v[0] + v[1]) + (v[2] + v[3])) + ((v[4] + v[5]) + (v[6] + v[7]));
+        }
+        t = wave_sum(t);
+        if ((threadIdx.x & 63) == 63) sh[k][threadIdx.x >> 6] = t;
+    }
+    __syncthreads();
+    if ((int)threadIdx.x < K) Q[(size_t)threadIdx.x * R + r] = (sh[threadIdx.x][0] + sh[threadIdx.x][1]) + (sh[threadIdx.x][2] + sh[threadIdx.x][3]);
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        __threadfence();
+        last = atomicAdd(ticket, 1u) == R - 1u;
+    }
+    __syncthreads();
+    if (!last) return;
+    __threadfence();
+    for (int k = 0; k < K; ++k) {      // lane i holds Q[k][i] (+ Q[k][i + 256] ..., in that order); the same DPP tree and wave order as above
+        double t = 0.;
+        for (unsigned i = threadIdx.x; i < R; i += 256) t += __hip_atomic_load(Q + (size_t)k * R + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        t = wave_sum(t);
+        if ((threadIdx.x & 63) == 63) sh[k][threadIdx.x >> 6] = t;
+    }
+    __syncthreads();
+    if ((int)threadIdx.x < K) {
+        const double t = (sh[threadIdx.x][0] + sh[threadIdx.x][1]) + (sh[threadIdx.x][2] + sh[threadIdx.x][3]);
+        double *dst = o.p[threadIdx.x];
+        if (dst) *dst = (o.accumulate ? *dst : 0.) + scale * t;
+    }
+    if (threadIdx.x == 0) *ticket = 0u;
+}
+
+int mcpm_det_begin(mcpm_plan *p, int K, unsigned nblk, DetSum *s) {
+    MCPM_REQUIRE(p, K >= 1 && K <= DET_MAXK, MCPM_E_ARG, "deterministic sum: bad row count");
+    const int64_t need = 1 + (int64_t)K * DET_MAXR + (int64_t)K * nblk;
+    if (p->part_n < need) {
+        if (p->part) {
+            MCPM_HIP(p, hipStreamSynchronize(p->stream));
+            (void)hipFree(p->part);
+            p->part = nullptr;
+            p->part_n = 0;
+        }
+        const int64_t n = need + need / 4;
+        if (hipMalloc((void **)&p->part, sizeof(double) * n) != hipSuccess) return mcpm_fail(p, MCPM_E_NOMEM, "reduction scratch");
+        p->part_n = n;
+        p->det_stale = 1;      // fresh memory: the ticket starts at zero
+    }
+    if (p->det_stale) {      // a HIP error since the last sum (mcpm_fail): a fold may have stopped short of resetting its ticket
+        MCPM_HIP(p, hipMemsetAsync(det_ticket(p), 0, sizeof(unsigned), p->stream));
+        p->det_stale = 0;
+    }
+    s->P = det_Q(p) + (int64_t)K * DET_MAXR;
+    s->nblk = nblk;
+    return MCPM_OK;
+}
+
+int mcpm_det_fold(mcpm_plan *p, const DetSum &s, int K, double scale, const DetOuts &outs) {
+    det_fold_kernel<<<det_R(s.nblk), 256, 0, p->stream>>>(s.P, s.nblk, K, det_Q(p), det_ticket(p), scale, outs);
+    MCPM_LAUNCH_CHECK(p, "det_fold_kernel");      // on failure mcpm_fail marks the ticket stale
+    return MCPM_OK;
+}
