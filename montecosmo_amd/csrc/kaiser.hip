@@ -12,18 +12,12 @@
 #include "reduce_dev.h"
 #include "tables_dev.h"
 
-#include <algorithm>
-
 namespace {
 
 struct KGeom {
     double cell[3], org[3];     // x_a = i_a cell[a] + org[a], org = -box / 2 + R^T centre
     float lf[3];                // flat-sky line of sight (cell axes)
     int nx, ny, nz, nq;         // nq = ceil(nz / 4) slots of four cells per z row
-};
-struct KTab {                   // device, float64; chi ascending
-    const double *chi, *a_of_chi, *a, *g, *f;
-    int nchi, ngrow;
 };
 struct KPar {
     float g, f, b1E, fnl;       // g(a_obs), f(a_obs) (unused on the light cone), 1 + b1, fNL_bp
@@ -34,7 +28,7 @@ struct KCell {
 };
 
 template <int CURVED, int LC>
-__device__ __forceinline__ void kaiser_cell(const KGeom &G, const KTab &tb, const KPar &P, float x0, float x1, int iz, KCell &c) {
+__device__ __forceinline__ void kaiser_cell(const KGeom &G, const LcTables &tb, const KPar &P, float x0, float x1, int iz, KCell &c) {
     const float x2 = (float)((double)iz * G.cell[2] + G.org[2]);
     float r;
     if (CURVED) {
@@ -110,7 +104,7 @@ __device__ __forceinline__ void store4(float *__restrict__ p, int cnt, const flo
 
 // ---- forward ---------------------------------------------------------------------------------------------------------------
 template <int CURVED, int LC, int VEC>
-__global__ __launch_bounds__(256) void kaiser_sky_kernel(KGeom G, KTab tb, KPar P, const float *__restrict__ meshes, const float *__restrict__ phi,
+__global__ __launch_bounds__(256) void kaiser_sky_kernel(KGeom G, LcTables tb, KPar P, const float *__restrict__ meshes, const float *__restrict__ phi,
                                                          int64_t M, int64_t nslot, float *__restrict__ out) {
     constexpr int NM = CURVED ? 6 : 2;
     const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
@@ -139,7 +133,7 @@ __global__ __launch_bounds__(256) void kaiser_sky_kernel(KGeom G, KTab tb, KPar 
 // mesh cotangents written, and per-workgroup partials of (b1E_bar, fNL_bp_bar, g_bar, f_bar); the last two are 0 on the light cone,
 // where g and f are per-cell look-ups whose cotangents go to the tables (kaiser_tables_vjp_kernel)
 template <int CURVED, int LC, int VEC>
-__global__ __launch_bounds__(256) void kaiser_sky_vjp_kernel(KGeom G, KTab tb, KPar P, const float *__restrict__ meshes,
+__global__ __launch_bounds__(256) void kaiser_sky_vjp_kernel(KGeom G, LcTables tb, KPar P, const float *__restrict__ meshes,
                                                              const float *__restrict__ phi, const float *__restrict__ ob, int64_t M,
                                                              int64_t nslot, float *__restrict__ mb, float *__restrict__ phb,
                                                              double *__restrict__ part) {
@@ -195,13 +189,13 @@ __global__ __launch_bounds__(256) void kaiser_sky_vjp_kernel(KGeom G, KTab tb, K
 // light cone: per cell g_bar = out_bar (b1E d + f q), f_bar = out_bar g q, and through a = chi2a(r) the cotangent of the chi nodes;
 // accumulators chi_bar[nchi], g_bar[ngrow], f_bar[ngrow] (kinds 0, 1, 2), the layout of observe_tables_vjp_kernel
 template <int CURVED, int PASS>
-__global__ __launch_bounds__(256) void kaiser_tables_vjp_kernel(KGeom G, KTab tb, KPar P, const float *__restrict__ meshes,
+__global__ __launch_bounds__(256) void kaiser_tables_vjp_kernel(KGeom G, LcTables tb, KPar P, const float *__restrict__ meshes,
                                                                 const float *__restrict__ ob, int64_t M, unsigned *__restrict__ mxbits,
                                                                 unsigned long long *__restrict__ out) {
     extern __shared__ unsigned long long shl[];
     constexpr int NM = CURVED ? 6 : 2;
     const int ntot = tb.nchi + 2 * tb.ngrow;
-    Acc A;
+    Acc<3> A;
     acc_begin(A, shl, ntot, mxbits, PASS);
     const int o_chi = 0, o_g = tb.nchi, o_f = tb.nchi + tb.ngrow;
     bool bad = false;
@@ -234,7 +228,7 @@ __host__ inline bool aligned16(const void *q) { return (reinterpret_cast<uintptr
 
 struct KArgs {
     KGeom G;
-    KTab tb;
+    LcTables tb;
     KPar P;
     int curved, lc, vec;
     int64_t nslot;
@@ -255,7 +249,7 @@ int kaiser_args(mcpm_plan *p, const char *who, const double *geom, int flags, co
     }
     a.G.nx = n[0], a.G.ny = n[1], a.G.nz = n[2], a.G.nq = (n[2] + 3) / 4;
     a.curved = flags & 1, a.lc = (flags >> 1) & 1, a.vec = n[2] % 4 == 0;
-    if (a.lc) a.tb = KTab{tables, tables + nchi, tables + 2 * nchi, tables + 2 * nchi + ngrow, tables + 2 * nchi + 2 * ngrow, nchi, ngrow};
+    if (a.lc) a.tb = lc_tables(tables, nchi, ngrow);
     a.P = KPar{(float)g_obs, (float)f_obs, (float)b1E, (float)fNL_bp};
     a.nslot = (int64_t)n[0] * n[1] * a.G.nq;
     *out = a;
@@ -321,25 +315,18 @@ int mcpm_kaiser_sky_tables_vjp_f32(mcpm_plan *p, const float *meshes, const doub
     MCPM_REQUIRE(p, (flags & 2) != 0, MCPM_E_ARG, "mcpm_kaiser_sky_tables_vjp_f32: light cone only (flags bit 1, tables)");
     KArgs a;
     MCPM_TRY(kaiser_args(p, "mcpm_kaiser_sky_tables_vjp_f32", geom, flags, tables, nchi, ngrow, 0., 0., b1E, 0., &a));
-    const size_t ntot = (size_t)nchi + 2 * (size_t)ngrow;
-    MCPM_REQUIRE(p, ntot + MCPM_RED_TABLES_TAIL <= MCPM_RED_TABLES_END - MCPM_RED_TABLES && ntot * sizeof(double) <= 60 * 1024, MCPM_E_ARG, "mcpm_kaiser_sky_tables_vjp_f32: tables exceed the accumulators");
-    // integer accumulators and the maxima: the plan's reduction scratch (free between the model-side calls)
-    unsigned long long *acc = reinterpret_cast<unsigned long long *>(p->reduce + MCPM_RED_TABLES);
-    unsigned *mx = reinterpret_cast<unsigned *>(acc + ntot);
-    MCPM_HIP(p, hipMemsetAsync(acc, 0, (ntot + 4) * sizeof(double), p->stream));
-    const unsigned nb = (unsigned)std::min<int64_t>((p->M + 255) / 256, 2048);
+    TabSum t;
+    MCPM_TRY(mcpm_tab_begin(p, "mcpm_kaiser_sky_tables_vjp_f32", MCPM_RED_TABLES, (size_t)nchi + 2 * (size_t)ngrow, p->M, &t));
     StageTimer st_(p, ST_LPT, 2.0 * (4.0 * (a.curved ? 6 : 2) + 4.0) * p->M);
-    if (a.curved) {
-        kaiser_tables_vjp_kernel<1, 0><<<nb, 256, 0, p->stream>>>(a.G, a.tb, a.P, meshes, out_bar, p->M, mx, acc);
-        kaiser_tables_vjp_kernel<1, 1><<<nb, 256, ntot * sizeof(double), p->stream>>>(a.G, a.tb, a.P, meshes, out_bar, p->M, mx, acc);
-    } else {
-        kaiser_tables_vjp_kernel<0, 0><<<nb, 256, 0, p->stream>>>(a.G, a.tb, a.P, meshes, out_bar, p->M, mx, acc);
-        kaiser_tables_vjp_kernel<0, 1><<<nb, 256, ntot * sizeof(double), p->stream>>>(a.G, a.tb, a.P, meshes, out_bar, p->M, mx, acc);
-    }
-    // kinds 0, 1, 2 = chi, g, f (the scale kernel's last two boundaries coincide with the end)
-    lc_scale_kernel<<<(unsigned)((ntot + 255) / 256), 256, 0, p->stream>>>(acc, mx, (int)ntot, nchi, nchi + ngrow, (int)ntot, (int)ntot, table_bar);
-    MCPM_LAUNCH_CHECK(p, "kaiser_tables_vjp_kernel");
-    return MCPM_OK;
+#define K(C)                                                                                                                   \
+    kaiser_tables_vjp_kernel<C, 0><<<t.nb, 256, 0, p->stream>>>(a.G, a.tb, a.P, meshes, out_bar, p->M, t.mx, t.acc);          \
+    MCPM_LAUNCH_CHECK(p, "kaiser_tables_vjp_kernel");                                                                          \
+    kaiser_tables_vjp_kernel<C, 1><<<t.nb, 256, t.lds, p->stream>>>(a.G, a.tb, a.P, meshes, out_bar, p->M, t.mx, t.acc);      \
+    MCPM_LAUNCH_CHECK(p, "kaiser_tables_vjp_kernel")
+    if (a.curved) { K(1); } else { K(0); }
+#undef K
+    const int kind_end[3] = {nchi, nchi + ngrow, t.ntot};      // chi, g, f
+    return mcpm_tab_finish(p, t, kind_end, 3, table_bar);
 }
 
 }  // extern "C"

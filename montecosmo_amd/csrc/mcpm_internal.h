@@ -34,20 +34,24 @@ enum McpmReduceMap {
     // two moment cotangents [0, 1]; composite.hip: the three LPT scalar cotangents of mcpm_lpt_vjp*_f32 [0, 3)
     MCPM_RED_SCALARS = 0,
     MCPM_RED_NSCALARS = 8,
-    // mcpm_png_add_vjp_f32: ntab <= MCPM_RED_PNG_NTAB 64-bit integer accumulators, then the bits of their maximum; BEHIND the scalars, because
-    // the same call holds S0, S1 there
+    // The two regions of the integer table sums (mcpm_tab_begin): ntot 64-bit integer accumulators, then MCPM_RED_TAB_TAIL doubles whose
+    // head holds the bits of the maxima, one unsigned per kind (MCPM_TAB_KINDS at most).
+    MCPM_TAB_KINDS = 5,
+    MCPM_RED_TAB_TAIL = 8,
+    // mcpm_png_add_vjp_f32: ntab <= MCPM_RED_PNG_NTAB accumulators of one kind; BEHIND the scalars, because the same call holds S0, S1 there
     MCPM_RED_PNG_ACC = MCPM_RED_SCALARS + MCPM_RED_NSCALARS,
     MCPM_RED_PNG_NTAB = 2048,
-    // mcpm_*_tables_vjp_f32 (observe.hip, kaiser.hip): ntot 64-bit integer accumulators, then the maxima (the first 4 slots of the tail),
-    // ntot + MCPM_RED_TABLES_TAIL <= MCPM_RED_TABLES_END - MCPM_RED_TABLES
+    // mcpm_*_tables_vjp_f32 (observe.hip, kaiser.hip): ntot + MCPM_RED_TAB_TAIL <= MCPM_RED_TABLES_END - MCPM_RED_TABLES
     MCPM_RED_TABLES = 0,
-    MCPM_RED_TABLES_TAIL = 8,
     MCPM_RED_TABLES_END = 3072,
     // mcpm_nbody_bf_vjp_f32, doubles: alpha_bar[n_steps], beta_bar[n_steps], then the tail (3 LPT scalar cotangents, dg_bar), up to MCPM_NREDUCE
     MCPM_RED_SWEEP = 0,
     MCPM_RED_SWEEP_TAIL = 4,
 };
-static_assert(MCPM_RED_PNG_ACC + MCPM_RED_PNG_NTAB + 1 <= MCPM_NREDUCE && MCPM_RED_TABLES_END <= MCPM_NREDUCE, "plan->reduce map");
+static_assert(MCPM_RED_PNG_ACC + MCPM_RED_PNG_NTAB + MCPM_RED_TAB_TAIL <= MCPM_NREDUCE && MCPM_RED_TABLES_END <= MCPM_NREDUCE &&
+                  MCPM_TAB_KINDS * sizeof(unsigned) <= MCPM_RED_TAB_TAIL * sizeof(double), "plan->reduce map");
+// pass 1 of a table sum keeps one 64-bit LDS accumulator per entry: the larger region fits the default dynamic-LDS limit of a launch
+static_assert(MCPM_RED_PNG_NTAB <= MCPM_RED_TABLES_END - MCPM_RED_TABLES && (MCPM_RED_TABLES_END - MCPM_RED_TABLES) * sizeof(double) <= 64 * 1024, "table sums: LDS");
 #ifndef MCPM_NZPAD
 #define MCPM_NZPAD 16  // complex elements added to the nz/2 pitch of the internal spectra
 #endif
@@ -210,6 +214,19 @@ struct DetSum {
 };
 int mcpm_det_begin(mcpm_plan *p, int K, unsigned nblk, DetSum *s);
 int mcpm_det_fold(mcpm_plan *p, const DetSum &s, int K, double scale, const DetOuts &outs);
+// One order-independent integer table sum (reduce.hip; the rule and the device side: tables_dev.h).  mcpm_tab_begin: checks that ntot entries
+// fit `region` of plan->reduce (MCPM_RED_TABLES or MCPM_RED_PNG_ACC), clears its accumulators and maxima and sizes the grid for nelem elements.
+// The caller launches its producer kernel twice on (t.mx, t.acc): pass 0 <<<t.nb, 256, 0>>>, pass 1 <<<t.nb, 256, t.lds>>>.  mcpm_tab_finish
+// scales the integers back into out[ntot] (device); kind_end[k] = one past the last entry of kind k, kind_end[nkinds - 1] = ntot.
+struct TabSum {
+    unsigned long long *acc;
+    unsigned *mx;
+    int ntot;
+    unsigned nb;
+    size_t lds;
+};
+int mcpm_tab_begin(mcpm_plan *p, const char *who, int region, size_t ntot, int64_t nelem, TabSum *t);
+int mcpm_tab_finish(mcpm_plan *p, const TabSum &t, const int *kind_end, int nkinds, double *out);
 void mcpm_slab_state_free(mcpm_plan *p);   // slab.hip
 #define MCPM_PITCH_MAX_SHIFT 17472      // floats: 64 KB + 4 KB + 256 B, the largest candidate shift between particle arrays
 static inline int64_t mcpm_pitch_max(const mcpm_plan *p) { return 3 * p->Np + MCPM_PITCH_MAX_SHIFT; }

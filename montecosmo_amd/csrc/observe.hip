@@ -27,11 +27,6 @@ struct Obs {
     float lf[3];                // flat-sky line of sight
     int curved, lightcone;
     float gf;                   // g(a_obs) f(a_obs) when not on the light cone
-    int nchi, ngrow;
-};
-
-struct Tables {                 // device, float64; chi ascending
-    const double *chi, *a_of_chi, *a, *g, *f;
 };
 
 // Alcock-Paczynski stage.  mode: MCPM_AP_NONE / MCPM_AP_AUTO / MCPM_AP_PARAM (a template argument of the kernels).
@@ -56,7 +51,7 @@ struct Fwd {
 };
 
 // common forward evaluation of one particle; x = absolute cell coordinates on the evolution mesh
-__device__ __forceinline__ void forward(const Obs &og, const Tables &tb, const float (&x)[3], const float (&vel)[3],
+__device__ __forceinline__ void forward(const Obs &og, const LcTables &tb, const float (&x)[3], const float (&vel)[3],
                                         const float (&dv)[3], Fwd &w) {
     float t[3];
 #pragma unroll
@@ -81,8 +76,8 @@ __device__ __forceinline__ void forward(const Obs &og, const Tables &tb, const f
     w.dgf_dr = 0.f;
     if (og.lightcone) {
         double da_dr, dg_da, df_da;
-        const double a = interp1((double)w.r, tb.chi, tb.a_of_chi, og.nchi, da_dr);
-        const double g = interp1(a, tb.a, tb.g, og.ngrow, dg_da), f = interp1(a, tb.a, tb.f, og.ngrow, df_da);
+        const double a = interp1((double)w.r, tb.chi, tb.a_of_chi, tb.nchi, da_dr);
+        const double g = interp1(a, tb.a, tb.g, tb.ngrow, dg_da), f = interp1(a, tb.a, tb.f, tb.ngrow, df_da);
         w.gf = (float)(g * f);
         w.dgf_dr = (float)((dg_da * f + g * df_da) * da_dr);
     }
@@ -161,7 +156,7 @@ __device__ __forceinline__ void lattice_point(const Geom &g, int64_t i, float (&
 }
 
 template <int MODE, int AP>
-__global__ __launch_bounds__(256) void observe_kernel(Geom g, Obs og, Tables tb, Ap ap, const float *__restrict__ pos,
+__global__ __launch_bounds__(256) void observe_kernel(Geom g, Obs og, LcTables tb, Ap ap, const float *__restrict__ pos,
                                                       const float *__restrict__ vel, const float *__restrict__ dvel, int64_t n,
                                                       float *__restrict__ out) {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
@@ -193,7 +188,7 @@ __global__ __launch_bounds__(256) void observe_kernel(Geom g, Obs og, Tables tb,
 }
 
 template <int MODE, int AP>
-__global__ __launch_bounds__(256) void observe_vjp_kernel(Geom g, Obs og, Tables tb, Ap ap, const float *__restrict__ pos,
+__global__ __launch_bounds__(256) void observe_vjp_kernel(Geom g, Obs og, LcTables tb, Ap ap, const float *__restrict__ pos,
                                                           const float *__restrict__ vel, const float *__restrict__ dvel, int64_t n,
                                                           const float *__restrict__ ob, float *__restrict__ pos_bar,
                                                           float *__restrict__ vel_bar, float *__restrict__ dvel_bar, double *part) {
@@ -279,7 +274,7 @@ __global__ __launch_bounds__(256) void lightcone_tables_vjp_kernel(const float *
                                                                    unsigned *__restrict__ mxbits, unsigned long long *__restrict__ out) {
     extern __shared__ unsigned long long shl[];
     const int ntot = nchi + 4 * ng;
-    Acc A;
+    Acc<5> A;
     acc_begin(A, shl, ntot, mxbits, PASS);
     const double *chi = tb, *aoc = tb + nchi, *ag = tb + 2 * nchi, *tg = ag + ng, *tg2 = tg + ng, *tf = tg2 + ng, *tf2 = tf + ng;
     const int o_chi = 0, o_g = nchi, o_g2 = nchi + ng, o_f = nchi + 2 * ng, o_f2 = nchi + 3 * ng;
@@ -321,15 +316,15 @@ __global__ __launch_bounds__(256) void lightcone_tables_vjp_kernel(const float *
 // look-up at r' (the fiducial table is constant): a_bar = rho_bar d chi_fid / d a goes into the same chi_bar accumulator.  Off the
 // light cone (og.lightcone = 0, ngrow = 0) that is the only contribution.
 template <int MODE, int AP, int PASS>
-__global__ __launch_bounds__(256) void observe_tables_vjp_kernel(Geom g, Obs og, Tables tb, Ap ap, const float *__restrict__ pos,
+__global__ __launch_bounds__(256) void observe_tables_vjp_kernel(Geom g, Obs og, LcTables tb, Ap ap, const float *__restrict__ pos,
                                                                  const float *__restrict__ vel, const float *__restrict__ dvel, int64_t n,
                                                                  const float *__restrict__ ob, unsigned *__restrict__ mxbits,
                                                                  unsigned long long *__restrict__ out) {
     extern __shared__ unsigned long long shl[];
-    const int ntot = og.nchi + 2 * og.ngrow;
-    Acc A;
+    const int ntot = tb.nchi + 2 * tb.ngrow;
+    Acc<3> A;
     acc_begin(A, shl, ntot, mxbits, PASS);
-    const int o_chi = 0, o_g = og.nchi, o_f = og.nchi + og.ngrow;
+    const int o_chi = 0, o_g = tb.nchi, o_f = tb.nchi + tb.ngrow;
     bool bad = false;
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
         float q[3] = {0.f, 0.f, 0.f}, x[3], v[3], dv[3] = {0.f, 0.f, 0.f}, o[3];
@@ -366,8 +361,8 @@ __global__ __launch_bounds__(256) void observe_tables_vjp_kernel(Geom g, Obs og,
         if (og.lightcone) {
             const float sb = Db[0] * w.l[0] + Db[1] * w.l[1] + Db[2] * w.l[2];
             const double gfb = (double)sb * ((double)w.l[0] * w.Vr[0] + (double)w.l[1] * w.Vr[1] + (double)w.l[2] * w.Vr[2]);
-            const Interp ba = interp_idx((double)w.r, tb.chi, tb.a_of_chi, og.nchi);
-            const Interp bg = interp_idx(ba.y, tb.a, tb.g, og.ngrow);
+            const Interp ba = interp_idx((double)w.r, tb.chi, tb.a_of_chi, tb.nchi);
+            const Interp bg = interp_idx(ba.y, tb.a, tb.g, tb.ngrow);
             double f, sf;
             interp_at(bg, tb.a, tb.f, f, sf);
             const double gb = gfb * f, fb = gfb * bg.y, ab = gb * bg.slope + fb * sf;
@@ -380,7 +375,7 @@ __global__ __launch_bounds__(256) void observe_tables_vjp_kernel(Geom g, Obs og,
     acc_end<PASS>(A, ntot, mxbits, out, bad);
 }
 
-Obs make_obs(const mcpm_plan *p, const float *geom, int flags, int nchi, int ngrow) {
+Obs make_obs(const mcpm_plan *p, const float *geom, int flags) {
     Obs og;
     for (int i = 0; i < 9; ++i) og.R[i] = geom[i];
     const int ms[3] = {p->g.nx, p->g.ny, p->g.nz};
@@ -397,8 +392,6 @@ Obs make_obs(const mcpm_plan *p, const float *geom, int flags, int nchi, int ngr
     og.curved = flags & 1;
     og.lightcone = (flags >> 1) & 1;
     og.gf = geom[18];
-    og.nchi = nchi;
-    og.ngrow = ngrow;
     return og;
 }
 
@@ -430,6 +423,24 @@ int make_ap(mcpm_plan *p, const char *who, int curved, int lightcone, int nchi, 
     return MCPM_OK;
 }
 
+// What the three *_ap_* entry points share: the argument checks (ptrs_ok: the entry point's own required pointers) and the kernels' structs
+struct ObsArgs {
+    Obs og;
+    LcTables tb;
+    Ap ap;
+};
+int obs_args(mcpm_plan *p, const char *who, bool ptrs_ok, const float *pos, const float *vel, int64_t n, int mode, const float *geom, int flags,
+             const double *tables, int nchi, int ngrow, int ap_mode, double alpha_iso, double alpha_ap, const double *ap_tables, int nap, int nfid,
+             ObsArgs *a) {
+    const std::string w(who);
+    MCPM_REQUIRE(p, pos && vel && geom && ptrs_ok && n > 0, MCPM_E_ARG, w + ": bad argument");
+    MCPM_REQUIRE(p, mode == MCPM_POS_ABSOLUTE || (mode == MCPM_POS_LATTICE && n == p->Np), MCPM_E_ARG, w + ": bad pos_mode / count");
+    MCPM_REQUIRE(p, !(flags & 2) || (tables && nchi >= 2 && ngrow >= 2), MCPM_E_ARG, w + ": light cone needs the tables");
+    a->og = make_obs(p, geom, flags);
+    a->tb = lc_tables(tables, nchi, ngrow);
+    return make_ap(p, who, a->og.curved, a->og.lightcone, nchi, ap_mode, alpha_iso, alpha_ap, ap_tables, nap, nfid, &a->ap);
+}
+
 #define OBS_DISPATCH(K, MO, AP, ...)                                                                    \
     do {                                                                                                \
         if ((MO) == MCPM_POS_LATTICE) {                                                                 \
@@ -456,17 +467,12 @@ int mcpm_observe_pos_ap_f32(mcpm_plan *p, const float *pos, const float *vel, co
                             const float *geom, int flags, const double *tables, int nchi, int ngrow, int ap_mode, double alpha_iso,
                             double alpha_ap, const double *ap_tables, int nap, int nfid, float *out) {
     if (!p) return MCPM_E_ARG;
-    MCPM_REQUIRE(p, pos && vel && geom && out && n > 0, MCPM_E_ARG, "mcpm_observe_pos_ap_f32: bad argument");
-    MCPM_REQUIRE(p, mode == MCPM_POS_ABSOLUTE || (mode == MCPM_POS_LATTICE && n == p->Np), MCPM_E_ARG, "mcpm_observe_pos_ap_f32: bad pos_mode / count");
-    MCPM_REQUIRE(p, !(flags & 2) || (tables && nchi >= 2 && ngrow >= 2), MCPM_E_ARG, "mcpm_observe_pos_ap_f32: light cone needs the tables");
-    Obs og = make_obs(p, geom, flags, nchi, ngrow);
-    Ap ap;
-    MCPM_TRY(make_ap(p, "mcpm_observe_pos_ap_f32", og.curved, og.lightcone, nchi, ap_mode, alpha_iso, alpha_ap, ap_tables, nap, nfid, &ap));
-    Tables tb{tables, tables ? tables + nchi : nullptr, tables ? tables + 2 * nchi : nullptr,
-              tables ? tables + 2 * nchi + ngrow : nullptr, tables ? tables + 2 * nchi + 2 * ngrow : nullptr};
+    ObsArgs a;
+    MCPM_TRY(obs_args(p, "mcpm_observe_pos_ap_f32", out != nullptr, pos, vel, n, mode, geom, flags, tables, nchi, ngrow, ap_mode, alpha_iso, alpha_ap,
+                      ap_tables, nap, nfid, &a));
     const unsigned nb = (unsigned)((n + 255) / 256);
     StageTimer st_(p, ST_LPT, (dvel ? 48.0 : 36.0) * n);
-#define K(MO, AP) observe_kernel<MO, AP><<<nb, 256, 0, p->stream>>>(p->g, og, tb, ap, pos, vel, dvel, n, out)
+#define K(MO, AP) observe_kernel<MO, AP><<<nb, 256, 0, p->stream>>>(p->g, a.og, a.tb, a.ap, pos, vel, dvel, n, out)
     OBS_DISPATCH(K, mode, ap_mode);
 #undef K
     MCPM_LAUNCH_CHECK(p, "observe_kernel");
@@ -487,22 +493,17 @@ int mcpm_observe_pos_ap_vjp_f32(mcpm_plan *p, const float *pos, const float *vel
                                 double alpha_ap, const double *ap_tables, int nap, int nfid, const float *out_bar, float *pos_bar,
                                 float *vel_bar, float *dvel_bar, double *gf_bar, double *alpha_bar) {
     if (!p) return MCPM_E_ARG;
-    MCPM_REQUIRE(p, pos && vel && geom && out_bar && pos_bar && vel_bar && gf_bar && n > 0, MCPM_E_ARG, "mcpm_observe_pos_ap_vjp_f32: bad argument");
-    MCPM_REQUIRE(p, mode == MCPM_POS_ABSOLUTE || (mode == MCPM_POS_LATTICE && n == p->Np), MCPM_E_ARG, "mcpm_observe_pos_ap_vjp_f32: bad pos_mode / count");
-    MCPM_REQUIRE(p, !(flags & 2) || (tables && nchi >= 2 && ngrow >= 2), MCPM_E_ARG, "mcpm_observe_pos_ap_vjp_f32: light cone needs the tables");
+    ObsArgs a;
+    MCPM_TRY(obs_args(p, "mcpm_observe_pos_ap_vjp_f32", out_bar && pos_bar && vel_bar && gf_bar, pos, vel, n, mode, geom, flags, tables, nchi, ngrow,
+                      ap_mode, alpha_iso, alpha_ap, ap_tables, nap, nfid, &a));
     MCPM_REQUIRE(p, (dvel == nullptr) == (dvel_bar == nullptr), MCPM_E_ARG, "mcpm_observe_pos_ap_vjp_f32: dvel and dvel_bar go together");
     MCPM_REQUIRE(p, ap_mode == MCPM_AP_NONE || alpha_bar, MCPM_E_ARG, "mcpm_observe_pos_ap_vjp_f32: alpha_bar is required with Alcock-Paczynski");
-    Obs og = make_obs(p, geom, flags, nchi, ngrow);
-    Ap ap;
-    MCPM_TRY(make_ap(p, "mcpm_observe_pos_ap_vjp_f32", og.curved, og.lightcone, nchi, ap_mode, alpha_iso, alpha_ap, ap_tables, nap, nfid, &ap));
-    Tables tb{tables, tables ? tables + nchi : nullptr, tables ? tables + 2 * nchi : nullptr,
-              tables ? tables + 2 * nchi + ngrow : nullptr, tables ? tables + 2 * nchi + 2 * ngrow : nullptr};
     DetSum s;
     const unsigned nb = (unsigned)((n + 255) / 256);
     const int nred = ap_mode == MCPM_AP_NONE ? 1 : 3;
     StageTimer st_(p, ST_LPT, (dvel ? 84.0 : 60.0) * n);
     MCPM_TRY(mcpm_det_begin(p, nred, nb, &s));
-#define K(MO, AP) observe_vjp_kernel<MO, AP><<<nb, 256, 0, p->stream>>>(p->g, og, tb, ap, pos, vel, dvel, n, out_bar, pos_bar, vel_bar, dvel_bar, s.P)
+#define K(MO, AP) observe_vjp_kernel<MO, AP><<<nb, 256, 0, p->stream>>>(p->g, a.og, a.tb, a.ap, pos, vel, dvel, n, out_bar, pos_bar, vel_bar, dvel_bar, s.P)
     OBS_DISPATCH(K, mode, ap_mode);
 #undef K
     MCPM_LAUNCH_CHECK(p, "observe_vjp_kernel");
@@ -524,18 +525,14 @@ int mcpm_lightcone_tables_vjp_f32(mcpm_plan *p, const float *r0, int64_t n, cons
                                   const float *g_bar, const float *g2_bar, const float *dg2dg_bar, double *table_bar) {
     if (!p) return MCPM_E_ARG;
     MCPM_REQUIRE(p, r0 && tables && g_bar && table_bar && n > 0 && nchi >= 2 && ngrow >= 2, MCPM_E_ARG, "mcpm_lightcone_tables_vjp_f32: bad argument");
-    const size_t ntot = (size_t)nchi + 4 * (size_t)ngrow;
-    MCPM_REQUIRE(p, ntot + MCPM_RED_TABLES_TAIL <= MCPM_RED_TABLES_END - MCPM_RED_TABLES && ntot * sizeof(double) <= 60 * 1024, MCPM_E_ARG, "mcpm_lightcone_tables_vjp_f32: tables exceed the accumulators");
-    // integer accumulators and the maxima: the plan's reduction scratch (free between the model-side calls)
-    unsigned long long *acc = reinterpret_cast<unsigned long long *>(p->reduce + MCPM_RED_TABLES);
-    unsigned *mx = reinterpret_cast<unsigned *>(acc + ntot);
-    MCPM_HIP(p, hipMemsetAsync(acc, 0, (ntot + 4) * sizeof(double), p->stream));
-    const unsigned nb = (unsigned)std::min<int64_t>((n + 255) / 256, 2048);
-    lightcone_tables_vjp_kernel<0><<<nb, 256, 0, p->stream>>>(r0, n, tables, nchi, ngrow, g_bar, g2_bar, dg2dg_bar, mx, acc);
-    lightcone_tables_vjp_kernel<1><<<nb, 256, ntot * sizeof(double), p->stream>>>(r0, n, tables, nchi, ngrow, g_bar, g2_bar, dg2dg_bar, mx, acc);
-    lc_scale_kernel<<<(unsigned)((ntot + 255) / 256), 256, 0, p->stream>>>(acc, mx, (int)ntot, nchi, nchi + ngrow, nchi + 2 * ngrow, nchi + 3 * ngrow, table_bar);
+    TabSum t;
+    MCPM_TRY(mcpm_tab_begin(p, "mcpm_lightcone_tables_vjp_f32", MCPM_RED_TABLES, (size_t)nchi + 4 * (size_t)ngrow, n, &t));
+    lightcone_tables_vjp_kernel<0><<<t.nb, 256, 0, p->stream>>>(r0, n, tables, nchi, ngrow, g_bar, g2_bar, dg2dg_bar, t.mx, t.acc);
     MCPM_LAUNCH_CHECK(p, "lightcone_tables_vjp_kernel");
-    return MCPM_OK;
+    lightcone_tables_vjp_kernel<1><<<t.nb, 256, t.lds, p->stream>>>(r0, n, tables, nchi, ngrow, g_bar, g2_bar, dg2dg_bar, t.mx, t.acc);
+    MCPM_LAUNCH_CHECK(p, "lightcone_tables_vjp_kernel");
+    const int kind_end[5] = {nchi, nchi + ngrow, nchi + 2 * ngrow, nchi + 3 * ngrow, t.ntot};      // chi, g, g2, f, f2
+    return mcpm_tab_finish(p, t, kind_end, 5, table_bar);
 }
 
 // Observation side: table cotangents of gf_p = a2g(a_p) a2f(a_p), a_p = chi2a(|P_p|) inside mcpm_observe_pos_f32 (light-cone bit) and
@@ -546,33 +543,24 @@ int mcpm_observe_pos_ap_tables_vjp_f32(mcpm_plan *p, const float *pos, const flo
                                        double alpha_iso, double alpha_ap, const double *ap_tables, int nap, int nfid, const float *out_bar,
                                        double *table_bar) {
     if (!p) return MCPM_E_ARG;
-    MCPM_REQUIRE(p, pos && vel && geom && out_bar && table_bar && n > 0, MCPM_E_ARG, "mcpm_observe_pos_ap_tables_vjp_f32: bad argument");
-    MCPM_REQUIRE(p, mode == MCPM_POS_ABSOLUTE || (mode == MCPM_POS_LATTICE && n == p->Np), MCPM_E_ARG, "mcpm_observe_pos_ap_tables_vjp_f32: bad pos_mode / count");
     const bool lc = (flags & 2) != 0;
     MCPM_REQUIRE(p, lc || ap_mode == MCPM_AP_AUTO, MCPM_E_ARG, "mcpm_observe_pos_ap_tables_vjp_f32: light cone only (flags bit 1, tables), or automatic Alcock-Paczynski");
-    MCPM_REQUIRE(p, !lc || (tables && nchi >= 2 && ngrow >= 2), MCPM_E_ARG, "mcpm_observe_pos_ap_tables_vjp_f32: light cone needs the tables");
     if (!lc) nchi = nap, ngrow = 0;      // the accumulator's layout: the Alcock-Paczynski look-up's chi nodes alone
-    const size_t ntot = (size_t)nchi + 2 * (size_t)ngrow;
-    MCPM_REQUIRE(p, ntot + MCPM_RED_TABLES_TAIL <= MCPM_RED_TABLES_END - MCPM_RED_TABLES && ntot * sizeof(double) <= 60 * 1024, MCPM_E_ARG, "mcpm_observe_pos_ap_tables_vjp_f32: tables exceed the accumulators");
-    Obs og = make_obs(p, geom, flags, nchi, ngrow);
-    Ap ap;
-    MCPM_TRY(make_ap(p, "mcpm_observe_pos_ap_tables_vjp_f32", og.curved, og.lightcone, nchi, ap_mode, alpha_iso, alpha_ap, ap_tables, nap, nfid, &ap));
-    Tables tb{tables, tables ? tables + nchi : nullptr, tables ? tables + 2 * nchi : nullptr,
-              tables ? tables + 2 * nchi + ngrow : nullptr, tables ? tables + 2 * nchi + 2 * ngrow : nullptr};
-    unsigned long long *acc = reinterpret_cast<unsigned long long *>(p->reduce + MCPM_RED_TABLES);
-    unsigned *mx = reinterpret_cast<unsigned *>(acc + ntot);
-    MCPM_HIP(p, hipMemsetAsync(acc, 0, (ntot + 4) * sizeof(double), p->stream));
-    const unsigned nb = (unsigned)std::min<int64_t>((n + 255) / 256, 2048);
+    ObsArgs a;
+    MCPM_TRY(obs_args(p, "mcpm_observe_pos_ap_tables_vjp_f32", out_bar && table_bar, pos, vel, n, mode, geom, flags, tables, nchi, ngrow, ap_mode,
+                      alpha_iso, alpha_ap, ap_tables, nap, nfid, &a));
+    TabSum t;
+    MCPM_TRY(mcpm_tab_begin(p, "mcpm_observe_pos_ap_tables_vjp_f32", MCPM_RED_TABLES, (size_t)nchi + 2 * (size_t)ngrow, n, &t));
     StageTimer st_(ap_mode == MCPM_AP_NONE ? nullptr : p, ST_LPT, 60.0 * n);      // the mode-none light-cone call stays unbooked, as before
-#define K(MO, AP)                                                                                                                    \
-    observe_tables_vjp_kernel<MO, AP, 0><<<nb, 256, 0, p->stream>>>(p->g, og, tb, ap, pos, vel, dvel, n, out_bar, mx, acc);              \
-    observe_tables_vjp_kernel<MO, AP, 1><<<nb, 256, ntot * sizeof(double), p->stream>>>(p->g, og, tb, ap, pos, vel, dvel, n, out_bar, mx, acc)
+#define K(MO, AP)                                                                                                                             \
+    observe_tables_vjp_kernel<MO, AP, 0><<<t.nb, 256, 0, p->stream>>>(p->g, a.og, a.tb, a.ap, pos, vel, dvel, n, out_bar, t.mx, t.acc);       \
+    MCPM_LAUNCH_CHECK(p, "observe_tables_vjp_kernel");                                                                                        \
+    observe_tables_vjp_kernel<MO, AP, 1><<<t.nb, 256, t.lds, p->stream>>>(p->g, a.og, a.tb, a.ap, pos, vel, dvel, n, out_bar, t.mx, t.acc); \
+    MCPM_LAUNCH_CHECK(p, "observe_tables_vjp_kernel")
     OBS_DISPATCH(K, mode, ap_mode);
 #undef K
-    // kinds 0, 1, 2 = chi, g, f (the scale kernel's last two boundaries coincide with the end)
-    lc_scale_kernel<<<(unsigned)((ntot + 255) / 256), 256, 0, p->stream>>>(acc, mx, (int)ntot, nchi, nchi + ngrow, (int)ntot, (int)ntot, table_bar);
-    MCPM_LAUNCH_CHECK(p, "observe_tables_vjp_kernel");
-    return MCPM_OK;
+    const int kind_end[3] = {nchi, nchi + ngrow, t.ntot};      // chi, g, f
+    return mcpm_tab_finish(p, t, kind_end, 3, table_bar);
 }
 
 int mcpm_observe_pos_tables_vjp_f32(mcpm_plan *p, const float *pos, const float *vel, const float *dvel, int64_t n, int mode,

@@ -7,8 +7,7 @@
 // observe.hip), so every output is bitwise the same call after call.
 #include "mcpm_internal.h"
 #include "reduce_dev.h"
-
-#include <algorithm>
+#include "tables_dev.h"
 
 #define PNG_TWO_PI 6.283185307179586f
 
@@ -172,54 +171,26 @@ __global__ __launch_bounds__(256) void png_vjp_out_kernel(Geom g, float kx, floa
     tbar[idx] = tb;
 }
 
-// table cotangent: tbar[k] goes to the nodes (lo, lo + 1) of its bracket with the weights (1 - w, w).  Summed as integers so that the
-// result does not depend on the order: PASS 0 takes the maximum |contribution| (bits of a float rounded up, atomicMax), PASS 1 rounds
-// each one to 2^(e - 30) units (2^e above that maximum) and adds it with 64-bit integer LDS / global atomics; png_scale_kernel
-// scales the integers back.  A non-finite contribution makes the whole table NaN.
+// table cotangent: tbar[k] goes to the nodes (lo, lo + 1) of its bracket with the weights (1 - w, w), summed as integers so that the result
+// does not depend on the order (tables_dev.h, ORDER-INDEPENDENT SUMS; one kind).  A non-finite contribution makes the whole table NaN.
 template <int PASS>
 __global__ __launch_bounds__(256) void png_table_vjp_kernel(Geom g, float kx, float ky, float kz, const double *__restrict__ ks,
                                                             const double *__restrict__ tt, int nt, const double *__restrict__ tbar, int64_t Mh,
                                                             unsigned *__restrict__ mxbits, unsigned long long *__restrict__ acc) {
     extern __shared__ unsigned long long png_sh[];
-    double mx = 0., sc = 0.;
+    Acc<1> A;
+    acc_begin(A, png_sh, nt, mxbits, PASS);
     bool bad = false;
-    if (PASS) {
-        const int be = (int)(*mxbits >> 23);      // biased exponent of the maximum: max < 2^(be - 126)
-        sc = (be == 0 || be >= 255) ? 0. : __longlong_as_double((long long)(1023 + 30 - (be - 126)) << 52);
-        for (int i = threadIdx.x; i < nt; i += 256) png_sh[i] = 0ull;
-        __syncthreads();
-    }
     for (int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x; idx < Mh; idx += (int64_t)gridDim.x * 256) {
         const PMode m = png_decode(g, kx, ky, kz, (uint32_t)idx);
         const TNode b = png_interp(m.k, ks, tt, nt);
         if (b.lo < 0) continue;
-        const double v = tbar[idx], c0 = v * (1. - b.w), c1 = v * b.w;
-        if (PASS == 0) {
-            bad = bad || !(v == v);
-            mx = fmax(mx, fmax(fabs(c0), fabs(c1)));
-        } else {
-            if (c0 != 0.) atomicAdd(png_sh + b.lo, (unsigned long long)__double2ll_rn(c0 * sc));
-            if (c1 != 0.) atomicAdd(png_sh + b.lo + 1, (unsigned long long)__double2ll_rn(c1 * sc));
-        }
+        const double v = tbar[idx];
+        bad = bad || !(v == v);
+        acc_add<PASS>(A, 0, 0, b.lo, v * (1. - b.w));
+        acc_add<PASS>(A, 0, 0, b.lo + 1, v * b.w);
     }
-    if (PASS == 0) {
-        unsigned bits = (bad || !(mx < 3.0e38)) ? 0x7fc00000u : __float_as_uint(__double2float_ru(mx));
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) bits = max(bits, (unsigned)__shfl_xor((int)bits, o));
-        if ((threadIdx.x & 63) == 0 && bits) atomicMax(mxbits, bits);
-    } else {
-        __syncthreads();
-        for (int i = threadIdx.x; i < nt; i += 256)
-            if (png_sh[i] != 0ull) atomicAdd(acc + i, png_sh[i]);
-    }
-}
-
-__global__ void png_scale_kernel(const unsigned long long *__restrict__ acc, const unsigned *__restrict__ mxbits, int nt, double *__restrict__ out) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= nt) return;
-    const int be = (int)(*mxbits >> 23);
-    if (be >= 255) { out[i] = __longlong_as_double(0x7ff8000000000000ll); return; }
-    out[i] = be == 0 ? 0. : (double)(long long)acc[i] * __longlong_as_double((long long)(1023 - 30 + (be - 126)) << 52);
+    acc_end<PASS>(A, nt, mxbits, acc, bad);
 }
 
 // ---- PNG terms of the Lagrangian bias weights (montecosmo/bricks.py:413-441) -----------------------------------------------------
@@ -438,13 +409,14 @@ int mcpm_png_add_vjp_f32(mcpm_plan *p, const float *lin_mesh, const float *out, 
     MCPM_REQUIRE(p, lin_mesh && ks && trans && ntab >= 2 && lin_mesh_bar && fnl_bar && trans_bar, MCPM_E_ARG, "mcpm_png_add_vjp_f32: bad argument");
     MCPM_REQUIRE(p, out_bar ? (out && phi && mean) : (phi_bar != nullptr), MCPM_E_ARG,
                  "mcpm_png_add_vjp_f32: out_bar needs out, phi and mean; without out_bar, phi_bar is the cotangent to pull back");
-    MCPM_REQUIRE(p, ntab <= MCPM_RED_PNG_NTAB, MCPM_E_ARG, "mcpm_png_add_vjp_f32: table exceeds the accumulators");
     MCPM_REQUIRE(p, !p->g.xslab, MCPM_E_UNSUPPORTED, "mcpm_png_add_vjp_f32: not slab-decomposed");
     const int64_t M = p->M, Mh = p->Mh;
     const unsigned nbk = (unsigned)((Mh + 255) / 256), nbr = (unsigned)((M + 255) / 256);
-    // plan scalars (the map in mcpm_internal.h): S0, S1; behind them ntab integer accumulators of the table cotangent, then the bits of the maximum
-    unsigned long long *acc = reinterpret_cast<unsigned long long *>(p->reduce + MCPM_RED_PNG_ACC);
-    unsigned *mx = reinterpret_cast<unsigned *>(acc + ntab);
+    // the table cotangent's accumulators, cleared here so that an oversized table is refused before anything is written.  They lie behind the
+    // plan scalars S0, S1 of this call (the map in mcpm_internal.h): NOTHING between here and png_table_vjp_kernel may touch plan->reduce beyond
+    // MCPM_RED_SCALARS (the det sums keep their partials in plan->part, the transforms use no reduction scratch)
+    TabSum t;
+    MCPM_TRY(mcpm_tab_begin(p, "mcpm_png_add_vjp_f32", MCPM_RED_PNG_ACC, (size_t)ntab, Mh, &t));
     const float *psib = phi_bar;      // without out_bar, phi_bar alone is pulled back: no C2R, no sums, fNL_bar = 0
     if (out_bar) {
         float *pb = p->rho;
@@ -476,13 +448,11 @@ int mcpm_png_add_vjp_f32(mcpm_plan *p, const float *lin_mesh, const float *out, 
                                                    (const float2 *)out, (const float2 *)out_bar, (const float2 *)p->spec1,
                                                    (const float2 *)spec2, (float2 *)lin_mesh_bar, tbar, Mh);
     MCPM_LAUNCH_CHECK(p, "png_vjp_out_kernel");
-    MCPM_HIP(p, hipMemsetAsync(acc, 0, ((size_t)ntab + 1) * sizeof(double), p->stream));
-    const unsigned nbt = (unsigned)std::min<int64_t>((Mh + 255) / 256, 2048);
-    png_table_vjp_kernel<0><<<nbt, 256, 0, p->stream>>>(p->g, kpx, kpy, kpz, ks, trans, ntab, tbar, Mh, mx, acc);
-    png_table_vjp_kernel<1><<<nbt, 256, (size_t)ntab * sizeof(double), p->stream>>>(p->g, kpx, kpy, kpz, ks, trans, ntab, tbar, Mh, mx, acc);
-    png_scale_kernel<<<(unsigned)((ntab + 255) / 256), 256, 0, p->stream>>>(acc, mx, ntab, trans_bar);
+    png_table_vjp_kernel<0><<<t.nb, 256, 0, p->stream>>>(p->g, kpx, kpy, kpz, ks, trans, ntab, tbar, Mh, t.mx, t.acc);
     MCPM_LAUNCH_CHECK(p, "png_table_vjp_kernel");
-    return MCPM_OK;
+    png_table_vjp_kernel<1><<<t.nb, 256, t.lds, p->stream>>>(p->g, kpx, kpy, kpz, ks, trans, ntab, tbar, Mh, t.mx, t.acc);
+    MCPM_LAUNCH_CHECK(p, "png_table_vjp_kernel");
+    return mcpm_tab_finish(p, t, &ntab, 1, trans_bar);
 }
 
 }  // extern "C"

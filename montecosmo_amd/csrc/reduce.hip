@@ -1,4 +1,5 @@
-// Second stage of the deterministic f64 grid sums (first stage: reduce_dev.h): the scratch, the fold kernel and its launcher.
+// Second stages kept in one place: the fold of the deterministic f64 grid sums (first stage: reduce_dev.h) with its scratch and launcher, and the
+// host side of the order-independent integer table sums (device side: tables_dev.h) with its scale kernel.
 #include <algorithm>
 
 #include "mcpm_internal.h"
@@ -89,5 +90,43 @@ int mcpm_det_begin(mcpm_plan *p, int K, unsigned nblk, DetSum *s) {
 int mcpm_det_fold(mcpm_plan *p, const DetSum &s, int K, double scale, const DetOuts &outs) {
     det_fold_kernel<<<det_R(s.nblk), 256, 0, p->stream>>>(s.P, s.nblk, K, det_Q(p), det_ticket(p), scale, outs);
     MCPM_LAUNCH_CHECK(p, "det_fold_kernel");      // on failure mcpm_fail marks the ticket stale
+    return MCPM_OK;
+}
+
+// ---- the order-independent integer table sums (the rule: tables_dev.h, ORDER-INDEPENDENT SUMS) ----------------------------------------
+// out[i] = integer sum scaled back by its kind's 2^(e - 30); e0 .. e3: one past the last entry of kinds 0 .. 3 (ntot for a kind the sum
+// does not have).  A non-finite maximum makes the whole kind NaN.
+__global__ void tab_scale_kernel(const unsigned long long *__restrict__ acc, const unsigned *__restrict__ mxbits, int ntot, int e0, int e1,
+                                 int e2, int e3, double *__restrict__ out) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= ntot) return;
+    const int k = i < e0 ? 0 : (i < e1 ? 1 : (i < e2 ? 2 : (i < e3 ? 3 : 4)));
+    const int be = (int)(mxbits[k] >> 23);
+    if (be >= 255) { out[i] = __longlong_as_double(0x7ff8000000000000ll); return; }
+    out[i] = be == 0 ? 0. : (double)(long long)acc[i] * __longlong_as_double((long long)(1023 - 30 + (be - 126)) << 52);
+}
+
+int mcpm_tab_begin(mcpm_plan *p, const char *who, int region, size_t ntot, int64_t nelem, TabSum *t) {
+    const bool png = region == MCPM_RED_PNG_ACC;
+    MCPM_REQUIRE(p, png || region == MCPM_RED_TABLES, MCPM_E_ARG, std::string(who) + ": not a region of the table sums");
+    const size_t cap = png ? MCPM_RED_PNG_NTAB : MCPM_RED_TABLES_END - MCPM_RED_TABLES - MCPM_RED_TAB_TAIL;
+    MCPM_REQUIRE(p, ntot <= cap, MCPM_E_ARG, std::string(who) + (png ? ": table exceeds the accumulators" : ": tables exceed the accumulators"));
+    // the plan's reduction scratch is free between the model-side calls (the map in mcpm_internal.h)
+    t->acc = reinterpret_cast<unsigned long long *>(p->reduce + region);
+    t->mx = reinterpret_cast<unsigned *>(t->acc + ntot);
+    t->ntot = (int)ntot;
+    t->nb = (unsigned)std::min<int64_t>((nelem + 255) / 256, 2048);
+    t->lds = ntot * sizeof(unsigned long long);
+    MCPM_HIP(p, hipMemsetAsync(t->acc, 0, (ntot + MCPM_RED_TAB_TAIL) * sizeof(double), p->stream));
+    return MCPM_OK;
+}
+
+int mcpm_tab_finish(mcpm_plan *p, const TabSum &t, const int *kind_end, int nkinds, double *out) {
+    static_assert(MCPM_TAB_KINDS == 5, "tab_scale_kernel takes the four inner boundaries of five kinds");
+    MCPM_REQUIRE(p, nkinds >= 1 && nkinds <= MCPM_TAB_KINDS && kind_end[nkinds - 1] == t.ntot, MCPM_E_ARG, "table sum: bad kind boundaries");
+    int e[MCPM_TAB_KINDS - 1];
+    for (int k = 0; k < MCPM_TAB_KINDS - 1; ++k) e[k] = k < nkinds ? kind_end[k] : t.ntot;
+    tab_scale_kernel<<<(unsigned)((t.ntot + 255) / 256), 256, 0, p->stream>>>(t.acc, t.mx, t.ntot, e[0], e[1], e[2], e[3], out);
+    MCPM_LAUNCH_CHECK(p, "tab_scale_kernel");
     return MCPM_OK;
 }

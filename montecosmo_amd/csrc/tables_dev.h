@@ -1,8 +1,10 @@
 // Table look-ups shared by the kernels that read the growth / distance tables per particle or per cell (observe.hip, kaiser.hip):
-// clamped linear interpolation in float64 with its bracket and slope, and the order-independent integer sums that contract per-element
-// cotangents into the small cotangents of the tables.
+// clamped linear interpolation in float64 with its bracket and slope, and the device side of the order-independent integer sums that
+// contract per-element cotangents into the small cotangents of the tables (those two and png.hip).
 #pragma once
 #include <hip/hip_runtime.h>
+
+#include "mcpm_internal.h"
 
 namespace {
 
@@ -17,6 +19,16 @@ __device__ __forceinline__ double interp1(double x, const double *xp, const doub
     }
     slope = (fp[hi] - fp[lo]) / (xp[hi] - xp[lo]);
     return fp[lo] + slope * (x - xp[lo]);
+}
+
+// The light-cone tables as the entry points receive them (device float64): chi[nchi] ascending, a(chi)[nchi], a[ngrow], g[ngrow], f[ngrow]
+struct LcTables {
+    const double *chi, *a_of_chi, *a, *g, *f;
+    int nchi, ngrow;
+};
+__host__ inline LcTables lc_tables(const double *t, int nchi, int ngrow) {
+    if (!t) return LcTables{nullptr, nullptr, nullptr, nullptr, nullptr, nchi, ngrow};
+    return LcTables{t, t + nchi, t + 2 * nchi, t + 2 * nchi + ngrow, t + 2 * nchi + 2 * ngrow, nchi, ngrow};
 }
 
 // ---- cotangents of the look-up TABLES (light cone: how the cosmology enters; model.py:740, :781, bricks.py:750-768) -----------
@@ -61,32 +73,36 @@ __device__ __forceinline__ void interp_at(const Interp &b, const double *xp, con
 // by nature), pass 1 rounds each contribution to 2^(e - 30) units (2^e >= that maximum, so a contribution is below 2^30 and a table
 // entry holds 2^32 of them) and adds it with 64-bit integer LDS / global atomics, and a last kernel scales the integers back.
 // Resolution: 10^-9 of the largest contribution per term.  A non-finite maximum makes the whole table NaN.
-#define LC_KINDS 5
+// The host side of a sum is mcpm_tab_begin / mcpm_tab_finish (mcpm_internal.h; reduce.hip keeps the scale kernel).  NK: the number of
+// kinds (tables with a maximum of their own) the producer kernel has, at most MCPM_TAB_KINDS.
+template <int NK>
 struct Acc {      // PASS 0: per-thread maxima;  PASS 1: integer accumulators in LDS
-    double mx[LC_KINDS];
+    double mx[NK];
     unsigned long long *sh;
-    double scale[LC_KINDS];
+    double scale[NK];
 };
-template <int PASS>
-__device__ __forceinline__ void acc_add(Acc &A, int kind, int off, int idx, double v) {
+template <int PASS, int NK>
+__device__ __forceinline__ void acc_add(Acc<NK> &A, int kind, int off, int idx, double v) {
     if (PASS == 0) A.mx[kind] = fmax(A.mx[kind], fabs(v));      // (fmax drops a NaN operand: the callers' `bad` flag catches it)
     else if (v != 0.) atomicAdd(A.sh + off + idx, (unsigned long long)__double2ll_rn(v * A.scale[kind]));
 }
-template <int PASS>
-__device__ __forceinline__ void scatter_fp(Acc &A, int kind, int off, const Interp &b, double ybar) {
+template <int PASS, int NK>
+__device__ __forceinline__ void scatter_fp(Acc<NK> &A, int kind, int off, const Interp &b, double ybar) {
     acc_add<PASS>(A, kind, off, b.lo, ybar * (1. - b.t));
     acc_add<PASS>(A, kind, off, b.lo + 1, ybar * b.t);
 }
 // ... and, for a look-up whose NODES move with the cosmology (chi -> a), into the node table's accumulator
-template <int PASS>
-__device__ __forceinline__ void scatter_xp(Acc &A, int kind, int off, const Interp &b, double ybar) {
+template <int PASS, int NK>
+__device__ __forceinline__ void scatter_xp(Acc<NK> &A, int kind, int off, const Interp &b, double ybar) {
     acc_add<PASS>(A, kind, off, b.lo, -ybar * b.slope * (1. - b.t));
     acc_add<PASS>(A, kind, off, b.lo + 1, -ybar * b.slope * b.t);
 }
 // mxbits: float bits (rounded up) of the maxima, one per kind; a NaN / inf contribution sets 0x7f800000 or above
-__device__ __forceinline__ void acc_begin(Acc &A, unsigned long long *sh, int ntot, const unsigned *mxbits, int pass) {
+template <int NK>
+__device__ __forceinline__ void acc_begin(Acc<NK> &A, unsigned long long *sh, int ntot, const unsigned *mxbits, int pass) {
+    static_assert(NK >= 1 && NK <= MCPM_TAB_KINDS, "kinds of a table sum");
     A.sh = sh;
-    for (int k = 0; k < LC_KINDS; ++k) {
+    for (int k = 0; k < NK; ++k) {
         A.mx[k] = 0.;
         const int be = pass ? (int)(mxbits[k] >> 23) : 0;                 // biased exponent of the maximum: max < 2^(be - 126)
         A.scale[k] = (be == 0 || be >= 255) ? 0. : __longlong_as_double((long long)(1023 + 30 - (be - 126)) << 52);      // 2^(30 - e)
@@ -96,10 +112,10 @@ __device__ __forceinline__ void acc_begin(Acc &A, unsigned long long *sh, int nt
         __syncthreads();
     }
 }
-template <int PASS>
-__device__ __forceinline__ void acc_end(Acc &A, int ntot, unsigned *mxbits, unsigned long long *out, bool bad) {
+template <int PASS, int NK>
+__device__ __forceinline__ void acc_end(Acc<NK> &A, int ntot, unsigned *mxbits, unsigned long long *out, bool bad) {
     if (PASS == 0) {
-        for (int k = 0; k < LC_KINDS; ++k) {
+        for (int k = 0; k < NK; ++k) {
             unsigned b = bad ? 0x7fc00000u : __float_as_uint(__double2float_ru(A.mx[k]));
             if (!(A.mx[k] < 3.0e38)) b = 0x7fc00000u;
 #pragma unroll
@@ -111,16 +127,6 @@ __device__ __forceinline__ void acc_end(Acc &A, int ntot, unsigned *mxbits, unsi
         for (int i = threadIdx.x; i < ntot; i += blockDim.x)
             if (A.sh[i] != 0ull) atomicAdd(out + i, A.sh[i]);
     }
-}
-// out[i] = integer sum scaled back; kind_end[k]: one past the last entry of kind k
-__global__ void lc_scale_kernel(const unsigned long long *__restrict__ acc, const unsigned *__restrict__ mxbits, int ntot, int e0, int e1,
-                                int e2, int e3, double *__restrict__ out) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= ntot) return;
-    const int k = i < e0 ? 0 : (i < e1 ? 1 : (i < e2 ? 2 : (i < e3 ? 3 : 4)));
-    const int be = (int)(mxbits[k] >> 23);
-    if (be >= 255) { out[i] = __longlong_as_double(0x7ff8000000000000ll); return; }
-    out[i] = be == 0 ? 0. : (double)(long long)acc[i] * __longlong_as_double((long long)(1023 - 30 + (be - 126)) << 52);
 }
 
 }  // namespace
