@@ -763,6 +763,27 @@ int mcpm_footprint_u8(mcpm_plan *plan, const float *pos, int64_t n, const float 
 /* masked_sum: out2 (device, 2 doubles) = float64 sum of mesh[i] over mask[i] != 0, and the number of such cells; n cells. */
 int mcpm_masked_sum_f64(mcpm_plan *plan, const float *mesh, const unsigned char *mask, int64_t n, double *out2);
 
+/* ---- isokinetic integrator of the MCLMC / MAMS samplers (montecosmo/samplers.py:285-583 drive blackjax's; mclmc.hip) -------------
+   Passes over one flat float32 DEVICE state vector of length d (scalars first, then the mesh: samplers.FlatLogDensity).  Shape-free:
+   the plan lends its stream and reduction scratch.  The pointers need not be 16-byte aligned (a view such as q[1:] serves; aligned
+   ones take 16-byte accesses).  Every output is bitwise the same call after call (fixed-order float64 sums, no floating-point atomic).
+
+   kick_drift: the velocity update B(eps_kick) for the gradient g of the LOG density under the diagonal metric s = sqrt(inverse_mass)
+     (float32, NULL = identity), then, if q is not NULL, the drift q += eps_drift s u'.  With gt = s g (formed in float64),
+     gamma = sqrt(sum gt^2), n = sqrt(sum u^2), c = sum(u gt) / (gamma n), delta = eps_kick gamma / (d - 1), zeta = exp(-delta) and
+     D = max((1 + c) + (1 - c) zeta^2, 1e-300):
+         u' = [ (1 - zeta)(1 + zeta + c (1 - zeta)) gt / gamma + 2 zeta u / n ] / D,   dK = (d - 1)(delta - ln 2 + ln D),
+     which is (u + e (sinh delta + c (cosh delta - 1))) / (cosh delta + c sinh delta), e = gt / gamma, free of overflow.  u may arrive
+     un-normalised (after a partial refresh u += nu z): the update divides by its measured norm, |u'| = 1.  gamma = 0: u' = u / n,
+     dK = 0, the drift still happens.  stats (DEVICE double[4]): [0..2] = sum gt^2, sum u gt, sum u^2 are STORED, dK is ADDED to [3]
+     (the caller zeroes it once per transition and reads it at the end).  u' and q' are formed in float64 and rounded once.
+     d < 2 or a NULL u / g / stats: MCPM_E_ARG. */
+int mcpm_mclmc_kick_drift_f32(mcpm_plan *plan, float *u, float *q, const float *g, const float *s, int64_t d, double eps_kick,
+                              double eps_drift, double *stats);
+/* moments: the warm-up's running moments on DEVICE float64 arrays, xavg = gamma xavg + w q and x2avg = gamma x2avg + w q^2, each
+     product and sum rounded on its own (q^2 is exact in float64). */
+int mcpm_mclmc_moments_f64(mcpm_plan *plan, const float *q, int64_t d, double gamma, double w, double *xavg, double *x2avg);
+
 /* RK4 on atab = logspace(log10_amin, 0, steps); writes seven host arrays of length `steps`. */
 int mcpm_growth_table(double Omega_m, double Omega_de, double Omega_k, double w0, double wa,
                       double log10_amin, int steps, double *a, double *g, double *f, double *h, double *g2,

@@ -496,3 +496,390 @@ def mclmc_sample(logdensity_and_grad, q0, n_warmup=200, n_samples=200, desired_e
             callback(it, info)
     return {"samples": samples, "step_size": eps, "L": L, "infos": infos, "seconds": time.perf_counter() - t0,
             "last_state": {"sampler": "mclmc", "q": q.clone(), "u": u.clone(), "step_size": eps, "L": L, "rng": rng.get_state()}}
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# Preconditioned MCLMC and MAMS (montecosmo/samplers.py:285-583: mclmc_warmup / mclmc_run / mams_warmup / mams_run, which
+# drive blackjax) on one integrator object.  The diagonal metric enters as s = sqrt(inverse_mass): the force is s g, the
+# drift s u.  Two back ends, one interface: 'hip' runs the fused kernels of csrc/mclmc.hip on float32 device vectors (two
+# passes per velocity update, the sums and the energy stay on the device until the end of the transition), 'torch' runs
+# the same formulas through torch ops on any dtype and device.
+class _TorchIntegrator:
+    backend = "torch"
+
+    def __init__(self, q, inverse_mass=None):
+        self.d, self.dtype, self.device = q.numel(), q.dtype, q.device
+        self.dK = 0.0
+        self.set_inverse_mass(inverse_mass)
+
+    def set_inverse_mass(self, inverse_mass):
+        self.s = None if inverse_mass is None else torch.sqrt(inverse_mass.to(device=self.device, dtype=torch.float64)).to(self.dtype)
+
+    def kick_drift(self, u, q, g, eps_kick, eps_drift):
+        """In place: u <- B(eps_kick) u for the gradient g, then q += eps_drift s u' (q may be None).  Adds the kinetic
+        energy change to the running sum `read_dK` returns.  u need not be normalised."""
+        gt = g.double() if self.s is None else self.s.double() * g.double()
+        ud = u.double()
+        gg, ug, uu = float(torch.dot(gt, gt)), float(torch.dot(ud, gt)), float(torch.dot(ud, ud))
+        n = math.sqrt(uu)
+        if gg > 0.0:
+            gam = math.sqrt(gg)
+            c = ug / (gam * n)
+            delta = eps_kick * gam / (self.d - 1)
+            z = math.exp(-delta)
+            D = max((1.0 + c) + (1.0 - c) * z * z, 1e-300)
+            ca, cb = (1.0 - z) * (1.0 + z + c * (1.0 - z)) / (gam * D), 2.0 * z / (n * D)
+            self.dK += (self.d - 1) * (delta - math.log(2.0) + math.log(D))
+            u.copy_(ca * gt + cb * ud)
+        else:
+            u.copy_(ud / n)
+        if q is not None:
+            su = u.double() if self.s is None else self.s.double() * u.double()
+            q.copy_(q.double() + eps_drift * su)
+
+    def refresh(self, u, nu, rng):
+        """Partial refresh u += nu z (left un-normalised: the next kick divides by the norm it measures)."""
+        u.add_(torch.randn(u.shape, dtype=u.dtype, device=u.device, generator=rng.torch_gen(u.device)), alpha=nu)
+
+    def new_moments(self):
+        return (torch.zeros(self.d, dtype=torch.float64, device=self.device), torch.zeros(self.d, dtype=torch.float64, device=self.device))
+
+    def moments(self, q, gamma, w, xavg, x2avg):
+        """In place: xavg = gamma xavg + w q, x2avg = gamma x2avg + w q^2 (float64)."""
+        qd = q.double()
+        xavg.mul_(gamma).add_(w * qd)
+        x2avg.mul_(gamma).add_(w * (qd * qd))
+
+    def zero_dK(self):
+        self.dK = 0.0
+
+    def read_dK(self):
+        """The kinetic energy change summed since `zero_dK`."""
+        return self.dK
+
+
+class _HipIntegrator(_TorchIntegrator):
+    backend = "hip"
+
+    def __init__(self, q, inverse_mass=None):
+        from . import nbody
+        if not (q.is_cuda and q.dtype == torch.float32 and q.is_contiguous() and q.dim() == 1):
+            raise ValueError("backend='hip' serves flat contiguous float32 device tensors")
+        self.plan = nbody.get_plan((8, 8, 8))      # shape-free passes: the plan lends its stream and reduction scratch
+        self.stats = torch.zeros(4, dtype=torch.float64, device=q.device)
+        super().__init__(q, inverse_mass)
+
+    def set_inverse_mass(self, inverse_mass):
+        super().set_inverse_mass(inverse_mass)
+        if self.s is not None:
+            self.s = self.s.contiguous()
+
+    def kick_drift(self, u, q, g, eps_kick, eps_drift):
+        self.plan.call("mcpm_mclmc_kick_drift_f32", u, q, g if g.is_contiguous() else g.contiguous(), self.s, self.d, float(eps_kick),
+                       float(eps_drift), self.stats)
+
+    def moments(self, q, gamma, w, xavg, x2avg):
+        self.plan.call("mcpm_mclmc_moments_f64", q, self.d, float(gamma), float(w), xavg, x2avg)
+
+    def zero_dK(self):
+        self.stats[3:].zero_()
+
+    def read_dK(self):
+        return float(self.stats[3])      # the transition's one read-back: 8 bytes
+
+
+def hip_backend_applies(q):
+    """Whether backend='auto' takes the HIP kernels for this state vector (float32, contiguous, on the device)."""
+    return bool(q.is_cuda and q.dtype == torch.float32 and q.is_contiguous() and q.dim() == 1 and q.numel() >= 2)
+
+
+def make_integrator(q, inverse_mass=None, backend="auto"):
+    """The integrator object of the samplers below for states like `q`: backend 'hip', 'torch' or 'auto' ('hip' where it
+    applies).  Interface: kick_drift, refresh, moments, zero_dK / read_dK."""
+    if backend == "auto":
+        backend = "hip" if hip_backend_applies(q) else "torch"
+    if backend == "hip":
+        return _HipIntegrator(q, inverse_mass)
+    if backend == "torch":
+        return _TorchIntegrator(q, inverse_mass)
+    raise ValueError(f"backend must be 'auto', 'hip' or 'torch', not {backend!r}")
+
+
+def mclachlan_step(integ, fn, q, u, lp, g, eps):
+    """One McLachlan minimal-norm step B(lam eps) A(eps/2) B((1-2 lam) eps) A(eps/2) B(lam eps) under the integrator's
+    metric, IN PLACE on q and u; (lp, g) belong to the incoming q.  Returns (lp', g', energy change)."""
+    lam = _MCLACHLAN
+    integ.zero_dK()
+    integ.kick_drift(u, q, g, lam * eps, 0.5 * eps)
+    lp1, g1 = fn(q)
+    integ.kick_drift(u, q, g1, (1 - 2 * lam) * eps, 0.5 * eps)
+    lp2, g2 = fn(q)
+    integ.kick_drift(u, None, g2, lam * eps, 0.0)
+    if not math.isfinite(lp1):
+        return lp2, g2, float("nan")
+    return lp2, g2, integ.read_dK() - (lp2 - lp)
+
+
+def _unit_normal(q, rng):
+    u = torch.randn(q.shape, dtype=q.dtype, device=q.device, generator=rng.torch_gen(q.device))
+    return u / torch.linalg.vector_norm(u)
+
+
+def _mclmc_transition(integ, fn, st, eps, L, rng):
+    """One MCLMC transition on the chain state `st` (dict q, u, lp, g): a McLachlan step, then the partial refresh
+    u += nu z.  A blown-up step is rejected (st unchanged).  Returns the energy change (nan when rejected)."""
+    q, u = st["q"].clone(), st["u"].clone()
+    lp, g, dE = mclachlan_step(integ, fn, q, u, st["lp"], st["g"], eps)
+    if not (math.isfinite(dE) and math.isfinite(lp)):
+        return float("nan")
+    nu = math.sqrt((math.exp(2.0 * eps / L) - 1.0) / q.numel())
+    integ.refresh(u, nu, rng)
+    st.update(q=q, u=u, lp=lp, g=g)
+    return dE
+
+
+def _mams_transition(integ, fn, st, eps, L, rng):
+    """One MAMS transition: fresh u on the sphere, n = max(1, ceil(U (2 L / eps - 1))) McLachlan steps without refresh,
+    accepted with probability min(1, exp(-dE)).  A rejection leaves q, lp and g as they are.  Returns
+    (acceptance probability, n)."""
+    u = _unit_normal(st["q"], rng)
+    n = max(1, math.ceil(rng.random() * (2.0 * L / eps - 1.0)))
+    q, lp, g, dE = st["q"].clone(), st["lp"], st["g"], 0.0
+    for _ in range(n):
+        lp, g, de = mclachlan_step(integ, fn, q, u, lp, g, eps)
+        dE += de
+        if not math.isfinite(dE):
+            break
+    acc = min(1.0, math.exp(min(0.0, -dE))) if (math.isfinite(dE) and math.isfinite(lp)) else 0.0
+    if rng.random() < acc:
+        st.update(q=q, lp=lp, g=g)
+    st["u"] = u
+    return acc, n
+
+
+def _unit(u):
+    return u / torch.linalg.vector_norm(u)
+
+
+def _config(config, d, eps0):
+    config = dict(config or {})
+    L = float(config["L"]) if config.get("L") is not None else math.sqrt(d)
+    eps = float(config["step_size"]) if config.get("step_size") is not None else eps0
+    return L, eps, config.get("inverse_mass")
+
+
+def _variance(xavg, x2avg, wsum):
+    return (x2avg / wsum - (xavg / wsum) ** 2).clamp_min(0.0)
+
+
+def _start(fn, q0, rng):
+    q = q0.clone()
+    lp, g = fn(q)
+    return {"q": q, "u": _unit_normal(q, rng), "lp": lp, "g": g}
+
+
+def _state_out(sampler, st, eps, L, inverse_mass, rng):
+    # 'u' is stored normalised; the chain itself carries the refreshed, un-normalised direction into its next kick, and 'u_raw' (on the
+    # host, as `save_run` leaves the rest) is that vector, from which a continued chain repeats the uninterrupted one bit for bit
+    return {"sampler": sampler, "q": st["q"].clone(), "u": _unit(st["u"]), "u_raw": st["u"].detach().cpu(), "step_size": eps, "L": L,
+            "rng": rng.get_state(), "inverse_mass": None if inverse_mass is None else inverse_mass.clone()}
+
+
+def mclmc_warmup(logdensity_and_grad, q0, n_steps, config=None, desired_energy_var=5e-4, diagonal_preconditioning=False, seed=0,
+                 backend="auto"):
+    """Tunes MCLMC (`blackjax.mclmc_find_L_and_step_size` as the reference calls it, samplers.py:318-337: frac_tune1 =
+    frac_tune2 = 0.5, no ESS stage).  `config`: dict(L, step_size, inverse_mass) to start from (defaults: sqrt(d),
+    sqrt(d) / 1000, identity).  `n_steps` is the total number of transitions spent.  First half: the step size is driven to
+    an energy-error variance per dimension of `desired_energy_var` (the predictor of `mclmc_sample`); second half: the same,
+    and the running moments of the position.  At the end, without preconditioning, L = sqrt(sum var).  With it,
+    inverse_mass = var, L = sqrt(d), and a third stage (one third of the second's length) re-tunes the step size under the
+    new metric with fresh averages.  Returns (state, config); `state` goes to `mclmc_run`."""
+    rng = _Rng(seed)
+    d = q0.numel()
+    L, eps, inverse_mass = _config(config, d, math.sqrt(d) / 1e4 * 10.0)
+    integ = make_integrator(q0, inverse_mass, backend)
+    st = _start(logdensity_and_grad, q0, rng)
+    n_steps = int(n_steps)
+    if diagonal_preconditioning:      # n1 + n2 + n2 // 3 = n_steps, n1 = n2 up to rounding (the reference's num_steps formula)
+        n2 = int(round(n_steps / (2.0 + 1.0 / 3.0)))
+        n3 = n2 // 3
+        n1 = max(n_steps - n2 - n3, 0)
+    else:
+        n1 = n_steps // 2
+        n2, n3 = n_steps - n1, 0
+    neff, sigma_xi = 150.0, 1.5
+    gamma = (neff - 1.0) / (neff + 1.0)
+    c_avg = w_sum = wx_sum = 0.0
+    xavg = x2avg = None
+    for it in range(n_steps):
+        if it == n1 + n2 and n3 > 0:
+            c_avg = w_sum = 0.0      # third stage: fresh step-size averages under the new metric
+        dE = _mclmc_transition(integ, logdensity_and_grad, st, eps, L, rng)
+        if not math.isfinite(dE):
+            eps *= 0.5
+            continue
+        xi = dE * dE / (d * desired_energy_var) + 1e-8
+        w = math.exp(-0.5 * (math.log(xi) / (6.0 * sigma_xi)) ** 2)
+        c_avg = gamma * c_avg + w * xi / eps ** 6
+        w_sum = gamma * w_sum + w
+        eps = (c_avg / w_sum) ** (-1.0 / 6.0)
+        if n1 <= it < n1 + n2:
+            if xavg is None:
+                xavg, x2avg = integ.new_moments()
+            integ.moments(st["q"], gamma, w, xavg, x2avg)
+            wx_sum = gamma * wx_sum + w
+        if it == n1 + n2 - 1 and xavg is not None and wx_sum > 0:
+            var = _variance(xavg, x2avg, wx_sum)
+            if diagonal_preconditioning:
+                inverse_mass = var.clamp_min(1e-30).to(q0.dtype)
+                integ.set_inverse_mass(inverse_mass)
+                L = math.sqrt(d)
+            else:
+                Lnew = math.sqrt(float(var.sum()))
+                if math.isfinite(Lnew) and Lnew > 0:
+                    L = Lnew
+    config = {"L": L, "step_size": eps, "inverse_mass": inverse_mass}
+    return _state_out("mclmc", st, eps, L, inverse_mass, rng), config
+
+
+def _run(kind, transition, logdensity_and_grad, state, config, n_samples, thinning, seed, keep, callback, backend):
+    rng = _Rng(seed) if seed is not None else _Rng.from_state(state["rng"])
+    q = state["q"].clone()
+    d = q.numel()
+    config = config if config is not None else state
+    L, eps = float(config["L"]), float(config["step_size"])
+    inverse_mass = config.get("inverse_mass")
+    if inverse_mass is not None:
+        inverse_mass = inverse_mass.to(q.device)
+    integ = make_integrator(q, inverse_mass, backend)
+    lp, g = logdensity_and_grad(q)
+    st = {"q": q, "u": state["u_raw" if "u_raw" in state else "u"].clone().to(q.device), "lp": lp, "g": g}
+    thinning = int(thinning)
+    samples, infos = [], []
+    t0 = time.perf_counter()
+    for it in range(int(n_samples)):
+        info = transition(integ, logdensity_and_grad, st, eps, L, rng, thinning, d)
+        samples.append(keep(st["q"]) if keep is not None else st["q"].clone())
+        info.update(step_size=eps, L=L, warmup=False, logdensity=st["lp"])
+        infos.append(info)
+        if callback is not None:
+            callback(it, info)
+    return {"samples": samples, "step_size": eps, "L": L, "inverse_mass": inverse_mass, "infos": infos, "seconds": time.perf_counter() - t0,
+            "backend": integ.backend, "last_state": _state_out(kind, st, eps, L, inverse_mass, rng)}
+
+
+def _mclmc_thinned(integ, fn, st, eps, L, rng, thinning, d):
+    s2 = 0.0
+    for _ in range(thinning):
+        dE = _mclmc_transition(integ, fn, st, eps, L, rng)
+        s2 += dE * dE
+    rms = math.sqrt(s2 / thinning) if math.isfinite(s2) else float("nan")
+    return {"energy_change": rms, "mse_per_dim": rms * rms / d, "n_evals": 2 * thinning}
+
+
+def _mams_thinned(integ, fn, st, eps, L, rng, thinning, d):
+    acc, n = 0.0, 0
+    for _ in range(thinning):
+        a, k = _mams_transition(integ, fn, st, eps, L, rng)
+        acc, n = acc + a, n + k
+    return {"acceptance_rate": acc / thinning, "accept_stat": acc / thinning, "n_steps": n, "n_evals": 2 * n}
+
+
+def mclmc_run(logdensity_and_grad, state, config=None, n_samples=200, thinning=1, seed=None, keep=None, callback=None, backend="auto"):
+    """`n_samples` kept states of MCLMC from `state` (of `mclmc_warmup`, or a previous run's `last_state`) under `config`
+    (dict(L, step_size, inverse_mass); None: the values `state` carries), every `thinning`-th transition kept.  Per kept
+    state `energy_change` is the RMS of the skipped steps' energy changes, `mse_per_dim` its square over d and `n_evals` =
+    2 thinning (samplers.py:379-400).  seed=None continues the random streams of `state` (a chain continued from a saved
+    state repeats the uninterrupted one bit for bit); a seed starts fresh ones.  The result has `mclmc_sample`'s shape;
+    `last_state` also carries `inverse_mass`."""
+    return _run("mclmc", _mclmc_thinned, logdensity_and_grad, state, config, n_samples, thinning, seed, keep, callback, backend)
+
+
+def mams_warmup(logdensity_and_grad, q0, n_steps, config=None, target_acc_rate=0.65, diagonal_preconditioning=False, seed=0,
+                backend="auto"):
+    """Tunes MAMS, the Metropolis-adjusted microcanonical sampler (samplers.py:432-497).  Schedule of `mclmc_warmup` (two
+    halves, plus a third of the second under a new metric), with the step size tuned by dual averaging of the acceptance
+    probability to `target_acc_rate` (samplers.py:481) and plain running moments in the second stage: L = sqrt(sum var), or
+    inverse_mass = var and L = sqrt(d).  Defaults: L = sqrt(d), step size sqrt(d) / 64 (samplers.py:447).
+    The number of steps of a trajectory is n = max(1, ceil(U (2 L / eps - 1))), mean L / eps; blackjax's `rescale`
+    interpolates for non-integer arguments, which this does not.  Only L_proposal_factor = inf (no refresh inside a
+    trajectory) is built.  Returns (state, config)."""
+    rng = _Rng(seed)
+    d = q0.numel()
+    L, eps, inverse_mass = _config(config, d, math.sqrt(d) / 64.0)
+    integ = make_integrator(q0, inverse_mass, backend)
+    st = _start(logdensity_and_grad, q0, rng)
+    n_steps = int(n_steps)
+    if diagonal_preconditioning:
+        n2 = int(round(n_steps / (2.0 + 1.0 / 3.0)))
+        n3 = n2 // 3
+        n1 = max(n_steps - n2 - n3, 0)
+    else:
+        n1 = n_steps // 2
+        n2, n3 = n_steps - n1, 0
+    da = DualAveraging(eps, target=target_acc_rate)
+    xavg = x2avg = None
+    cnt = 0
+    for it in range(n_steps):
+        if it == n1 + n2 and n3 > 0:
+            da = DualAveraging(eps, target=target_acc_rate)
+        acc, _ = _mams_transition(integ, logdensity_and_grad, st, eps, L, rng)
+        eps = da.update(acc)
+        if n1 <= it < n1 + n2:
+            if xavg is None:
+                xavg, x2avg = integ.new_moments()
+            integ.moments(st["q"], 1.0, 1.0, xavg, x2avg)
+            cnt += 1
+        if it == n1 + n2 - 1 and cnt > 1:
+            eps = da.final()
+            var = _variance(xavg, x2avg, float(cnt))
+            if diagonal_preconditioning:
+                inverse_mass = var.clamp_min(1e-30).to(q0.dtype)
+                integ.set_inverse_mass(inverse_mass)
+                L = math.sqrt(d)
+            else:
+                Lnew = math.sqrt(float(var.sum()))
+                if math.isfinite(Lnew) and Lnew > 0:
+                    L = Lnew
+    if n_steps > 0:
+        eps = da.final()
+    config = {"L": L, "step_size": eps, "inverse_mass": inverse_mass}
+    return _state_out("mams", st, eps, L, inverse_mass, rng), config
+
+
+def mams_run(logdensity_and_grad, state, config=None, n_samples=200, thinning=1, seed=None, keep=None, callback=None, backend="auto"):
+    """`n_samples` kept states of MAMS (see `mams_warmup` for the transition).  `infos` carry `acceptance_rate`, `n_steps`
+    and `n_evals` = 2 n_steps; thinning averages the first and sums the other two (samplers.py:543-551).  Otherwise as
+    `mclmc_run`."""
+    return _run("mams", _mams_thinned, logdensity_and_grad, state, config, n_samples, thinning, seed, keep, callback, backend)
+
+
+def collapse_configs(configs, eval_per_ess=1e3):
+    """The chains' configs collapsed to one shared config (montecosmo/script.py:141-144): the median step size,
+    L = 0.4 eval_per_ess / 2 step_size, the element-wise median inverse mass (None when no chain has one)."""
+    def median(x):      # over the chain axis, the mean of the middle two for an even count (torch.quantile caps its input's size)
+        x, n = torch.sort(x.double(), dim=0).values, x.shape[0]
+        return x[n // 2] if n % 2 else 0.5 * (x[n // 2 - 1] + x[n // 2])
+    eps = float(median(torch.tensor([float(c["step_size"]) for c in configs], dtype=torch.float64)))
+    ims = [c.get("inverse_mass") for c in configs]
+    inverse_mass = None
+    if any(m is not None for m in ims):
+        ref = next(m for m in ims if m is not None)
+        inverse_mass = median(torch.stack([torch.ones_like(ref) if m is None else m.to(ref.device) for m in ims])).to(ref.dtype)
+    return {"L": 0.4 * eval_per_ess / 2.0 * eps, "step_size": eps, "inverse_mass": inverse_mass}
+
+
+def chain_sampler(kind="mclmc", **warmup_kw):
+    """Adapter for `sample_and_save`: a callable with the signature of `mclmc_sample` that warms up (`mclmc_warmup` /
+    `mams_warmup` with `warmup_kw`) unless it is handed a state, then runs `mclmc_run` / `mams_run`.  Keywords thinning, seed,
+    keep, callback and backend pass through `sample_and_save`."""
+    warmup, run = {"mclmc": (mclmc_warmup, mclmc_run), "mams": (mams_warmup, mams_run)}[kind]
+
+    def sampler(logdensity_and_grad, q0, n_warmup=200, n_samples=200, state=None, seed=0, backend="auto", **kw):
+        config = None
+        if state is None:
+            state, config = warmup(logdensity_and_grad, q0, n_warmup, seed=seed, backend=backend, **warmup_kw)
+        elif q0 is not None:
+            state = dict(state, q=state["q"].to(q0.device), u=state["u"].to(q0.device))
+        return run(logdensity_and_grad, state, config, n_samples, backend=backend, **kw)
+    return sampler
