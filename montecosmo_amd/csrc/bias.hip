@@ -9,7 +9,8 @@
 // between are mcpm_read_f32 / mcpm_paint_f32.
 #include "mcpm_internal.h"
 #include "reduce_dev.h"
-#include "bias_dev.h"      // mode decoder, the 10-multiplier table, bias_spectra_kernel and its adjoint
+#include "tables_dev.h"    // the table look-ups of power_mult_kernel and interp_kernel
+#include "bias_dev.h"      // the 10-multiplier table, bias_spectra_kernel and its adjoint, on the mode decoder of kmode_dev.h
 
 namespace {
 
@@ -149,26 +150,13 @@ __global__ __launch_bounds__(256) void bias_vjp_particles_kernel(const float *__
     block_partial<1>(v, part, gridDim.x, blockIdx.x);
 }
 
-// jnp.interp(x, xp, fp, left=0, right=0) on float64 device tables
-__device__ __forceinline__ double interp_zero(double x, const double *xp, const double *fp, int n) {
-    if (x < xp[0] || x > xp[n - 1]) return 0.;
-    int lo = 0, hi = n - 1;
-    while (hi - lo > 1) {
-        const int mid = (lo + hi) >> 1;
-        if (xp[mid] <= x) lo = mid; else hi = mid;
-    }
-    return fp[lo] + (fp[hi] - fp[lo]) / (xp[hi] - xp[lo]) * (x - xp[lo]);
-}
-
 // out = in * sqrt(amp * P(|k|)), P linearly interpolated from (ks, pows), zero outside the table (bricks.py:83-100, :149-154)
-__global__ __launch_bounds__(256) void power_mult_kernel(Geom g, float kx, float ky, float kz, double amp,
-                                                         const double *__restrict__ ks, const double *__restrict__ pows, int nt,
+__global__ __launch_bounds__(256) void power_mult_kernel(KGeom kg, double amp, Table pw,
                                                          const float2 *__restrict__ in, float2 *__restrict__ out, int64_t Mh) {
     const uint32_t idx = blockIdx.x * 256u + threadIdx.x;
     if (idx >= Mh) return;
-    const BMode m = bdecode(g, kx, ky, kz, idx);
-    const double k = sqrt((double)m.k[0] * m.k[0] + (double)m.k[1] * m.k[1] + (double)m.k[2] * m.k[2]);
-    const float t = (float)sqrt(amp * interp_zero(k, ks, pows, nt));
+    const KMode m = kdecode(kg, idx);
+    const float t = (float)sqrt(amp * interp_zero(m.kn, pw).t);
     const float2 v = in[idx];
     out[idx] = make_float2(t * v.x, t * v.y);
 }
@@ -178,19 +166,8 @@ __global__ __launch_bounds__(256) void interp_kernel(const float *__restrict__ x
                                                      const double *__restrict__ fp, int nt, float scale, float *__restrict__ out) {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
-    const double v = (double)x[i];
-    double r;
-    if (v <= xp[0]) r = fp[0];
-    else if (v >= xp[nt - 1]) r = fp[nt - 1];
-    else {
-        int lo = 0, hi = nt - 1;
-        while (hi - lo > 1) {
-            const int mid = (lo + hi) >> 1;
-            if (xp[mid] <= v) lo = mid; else hi = mid;
-        }
-        r = fp[lo] + (fp[hi] - fp[lo]) / (xp[hi] - xp[lo]) * (v - xp[lo]);
-    }
-    out[i] = scale * (float)r;
+    double slope;
+    out[i] = scale * (float)interp1((double)x[i], xp, fp, nt, slope);
 }
 
 // light-cone LPT (nbody.py:652-666 with a of shape (N,1)): dpos = g F1 - g2 F2, vel = F1 - c F2, per-particle (g, g2, c)
@@ -232,13 +209,13 @@ __global__ __launch_bounds__(256) void lpt_combine_vjp_kernel(const float *__res
     gtb[3 * i + 2] = cb;
 }
 
-int fields_group(mcpm_plan *p, const float *lin_mesh, float kx, float ky, float kz, int group, float *spec, float *real) {
+int fields_group(mcpm_plan *p, const float *lin_mesh, const KGeom &kg, int group, float *spec, float *real) {
     const unsigned nb = (unsigned)((p->Mh + 255) / 256);
     const float scale = 1.f / (float)p->M;
     if (group == 0)
-        bias_spectra_kernel<0><<<nb, 256, 0, p->stream>>>(p->g, kx, ky, kz, scale, (const float2 *)lin_mesh, (float2 *)spec, p->Mh);
+        bias_spectra_kernel<0><<<nb, 256, 0, p->stream>>>(kg, scale, (const float2 *)lin_mesh, (float2 *)spec, p->Mh);
     else
-        bias_spectra_kernel<1><<<nb, 256, 0, p->stream>>>(p->g, kx, ky, kz, scale, (const float2 *)lin_mesh, (float2 *)spec, p->Mh);
+        bias_spectra_kernel<1><<<nb, 256, 0, p->stream>>>(kg, scale, (const float2 *)lin_mesh, (float2 *)spec, p->Mh);
     MCPM_LAUNCH_CHECK(p, "bias_spectra_kernel");
     return mcpm_fft_c2r(p, spec, real, group == 0 ? 6 : 4);
 }
@@ -254,17 +231,18 @@ extern "C" {
 int mcpm_bias_fields_save_f32(mcpm_plan *p, const float *lin_mesh, float kpx, float kpy, float kpz, float *fields7, float *hess6) {
     if (!p) return MCPM_E_ARG;
     MCPM_REQUIRE(p, lin_mesh && fields7, MCPM_E_ARG, "mcpm_bias_fields_f32: null buffer");
-    MCPM_REQUIRE(p, !p->g.xslab, MCPM_E_UNSUPPORTED, "mcpm_bias_fields_f32: not slab-decomposed");
+    KGeom kg;
+    MCPM_TRY(kgeom_arg(p, "mcpm_bias_fields_f32", kpx, kpy, kpz, &kg));
     const int64_t M = p->M;
     float *spec = p->spec, *r6 = hess6 ? hess6 : p->fmesh;  // scratch: 6 plain spectra, 6 of the 9 real meshes
-    MCPM_TRY(fields_group(p, lin_mesh, kpx, kpy, kpz, 0, spec, r6));
+    MCPM_TRY(fields_group(p, lin_mesh, kg, 0, spec, r6));
     {
         StageTimer st_(p, ST_LPT, 32.0 * M);
         shear_combine_kernel<<<(unsigned)((M + 255) / 256), 256, 0, p->stream>>>(r6, M, fields7 + M, fields7 + 2 * M);
         MCPM_LAUNCH_CHECK(p, "shear_combine_kernel");
     }
     MCPM_HIP(p, hipMemcpyAsync(fields7, r6, sizeof(float) * M, hipMemcpyDeviceToDevice, p->stream));
-    MCPM_TRY(fields_group(p, lin_mesh, kpx, kpy, kpz, 1, spec, fields7 + 3 * M));
+    MCPM_TRY(fields_group(p, lin_mesh, kg, 1, spec, fields7 + 3 * M));
     return MCPM_OK;
 }
 
@@ -274,22 +252,22 @@ int mcpm_bias_fields_f32(mcpm_plan *p, const float *lin_mesh, float kpx, float k
 
 // cotangents of the 7 fields -> cotangent of lin_mesh (real-pair convention, irfftn multiplicity weights); hess6: what
 // mcpm_bias_fields_save_f32 left (read only), or NULL: delta and the Hessian meshes are recomputed from lin_mesh
-static int bias_fields_vjp(mcpm_plan *p, const float *lin_mesh, float kpx, float kpy, float kpz, const float *hess6, const float *fields7_bar,
+static int bias_fields_vjp(mcpm_plan *p, const float *lin_mesh, const KGeom &kg, const float *hess6, const float *fields7_bar,
                            float *lin_mesh_bar) {
     const int64_t M = p->M, Mh = p->Mh;
     const unsigned nb = (unsigned)((Mh + 255) / 256);
     const float scale = 1.f / (float)M;
     float *spec = p->spec, *r6 = p->fmesh;
-    if (!hess6) MCPM_TRY(fields_group(p, lin_mesh, kpx, kpy, kpz, 0, spec, r6));   // recompute delta and the Hessian meshes
+    if (!hess6) MCPM_TRY(fields_group(p, lin_mesh, kg, 0, spec, r6));   // recompute delta and the Hessian meshes
     shear_combine_vjp_kernel<<<(unsigned)((M + 255) / 256), 256, 0, p->stream>>>(hess6 ? hess6 : r6, r6, M, fields7_bar, fields7_bar + M, fields7_bar + 2 * M);
     MCPM_LAUNCH_CHECK(p, "shear_combine_vjp_kernel");
     MCPM_TRY(mcpm_fft_r2c(p, r6, spec, 6));
-    bias_spectra_vjp_kernel<0><<<nb, 256, 0, p->stream>>>(p->g, kpx, kpy, kpz, scale, (const float2 *)spec, (float2 *)lin_mesh_bar, Mh, 0);
+    bias_spectra_vjp_kernel<0><<<nb, 256, 0, p->stream>>>(kg, scale, (const float2 *)spec, (float2 *)lin_mesh_bar, Mh, 0);
     MCPM_LAUNCH_CHECK(p, "bias_spectra_vjp_kernel");
     // rocFFT may overwrite a C2R / R2C input: work on a copy of the caller's cotangent meshes
     MCPM_HIP(p, hipMemcpyAsync(r6, fields7_bar + 3 * M, sizeof(float) * 4 * M, hipMemcpyDeviceToDevice, p->stream));
     MCPM_TRY(mcpm_fft_r2c(p, r6, spec, 4));
-    bias_spectra_vjp_kernel<1><<<nb, 256, 0, p->stream>>>(p->g, kpx, kpy, kpz, scale, (const float2 *)spec, (float2 *)lin_mesh_bar, Mh, 1);
+    bias_spectra_vjp_kernel<1><<<nb, 256, 0, p->stream>>>(kg, scale, (const float2 *)spec, (float2 *)lin_mesh_bar, Mh, 1);
     MCPM_LAUNCH_CHECK(p, "bias_spectra_vjp_kernel");
     return MCPM_OK;
 }
@@ -298,16 +276,18 @@ int mcpm_bias_fields_vjp_f32(mcpm_plan *p, const float *lin_mesh, float kpx, flo
                              float *lin_mesh_bar) {
     if (!p) return MCPM_E_ARG;
     MCPM_REQUIRE(p, lin_mesh && fields7_bar && lin_mesh_bar, MCPM_E_ARG, "mcpm_bias_fields_vjp_f32: null buffer");
-    MCPM_REQUIRE(p, !p->g.xslab, MCPM_E_UNSUPPORTED, "mcpm_bias_fields_vjp_f32: not slab-decomposed");
-    return bias_fields_vjp(p, lin_mesh, kpx, kpy, kpz, nullptr, fields7_bar, lin_mesh_bar);
+    KGeom kg;
+    MCPM_TRY(kgeom_arg(p, "mcpm_bias_fields_vjp_f32", kpx, kpy, kpz, &kg));
+    return bias_fields_vjp(p, lin_mesh, kg, nullptr, fields7_bar, lin_mesh_bar);
 }
 
 int mcpm_bias_fields_vjp_saved_f32(mcpm_plan *p, float kpx, float kpy, float kpz, const float *hess6, const float *fields7_bar,
                                    float *lin_mesh_bar) {
     if (!p) return MCPM_E_ARG;
     MCPM_REQUIRE(p, hess6 && fields7_bar && lin_mesh_bar, MCPM_E_ARG, "mcpm_bias_fields_vjp_saved_f32: null buffer");
-    MCPM_REQUIRE(p, !p->g.xslab, MCPM_E_UNSUPPORTED, "mcpm_bias_fields_vjp_saved_f32: not slab-decomposed");
-    return bias_fields_vjp(p, nullptr, kpx, kpy, kpz, hess6, fields7_bar, lin_mesh_bar);
+    KGeom kg;
+    MCPM_TRY(kgeom_arg(p, "mcpm_bias_fields_vjp_saved_f32", kpx, kpy, kpz, &kg));
+    return bias_fields_vjp(p, nullptr, kg, hess6, fields7_bar, lin_mesh_bar);
 }
 
 // reads (raw values of the 7 fields at the particles: dr, s2r, s3r, lr (n each), gr (n,3)) -> weights (n), dvel (n,3).
@@ -369,10 +349,12 @@ int mcpm_bias_weights_vjp_f32(mcpm_plan *p, int64_t n, const float *dr, const fl
 int mcpm_power_mult_f32(mcpm_plan *p, const float *in, float kpx, float kpy, float kpz, double amp, const double *ks,
                         const double *pows, int ntab, float *out) {
     if (!p) return MCPM_E_ARG;
-    MCPM_REQUIRE(p, in && out && ks && pows && ntab >= 2, MCPM_E_ARG, "mcpm_power_mult_f32: bad argument");
+    Table pw;
+    MCPM_REQUIRE(p, in && out, MCPM_E_ARG, "mcpm_power_mult_f32: bad argument");
+    MCPM_TRY(table_arg(p, "mcpm_power_mult_f32", ks, pows, ntab, &pw));
     StageTimer st_(p, ST_KSPACE, 16.0 * p->Mh);
-    power_mult_kernel<<<(unsigned)((p->Mh + 255) / 256), 256, 0, p->stream>>>(p->g, kpx, kpy, kpz, amp, ks, pows, ntab,
-                                                                             (const float2 *)in, (float2 *)out, p->Mh);
+    power_mult_kernel<<<(unsigned)((p->Mh + 255) / 256), 256, 0, p->stream>>>(KGeom{p->g, {kpx, kpy, kpz}}, amp, pw, (const float2 *)in,
+                                                                             (float2 *)out, p->Mh);
     MCPM_LAUNCH_CHECK(p, "power_mult_kernel");
     return MCPM_OK;
 }

@@ -1,43 +1,15 @@
-// Mesh-side spectral machinery of the bias expansions, shared by bias.hip (Lagrangian) and eulerian.hip (Eulerian): the mode decoder,
-// the 10-multiplier table {1, k_i k_j / k^2 (5), -k^2, i k_c (3)} with numpy irfftn's Hermitian projection, and the spectra kernels
-// out[s] = scale m_s in with their adjoint.  Wavevectors in h/Mpc: k_cell * kphys[axis].
+// Mesh-side spectral machinery of the bias expansions, shared by bias.hip (Lagrangian) and eulerian.hip (Eulerian): on the mode decoder
+// of kmode_dev.h, the 10-multiplier table {1, k_i k_j / k^2 (5), -k^2, i k_c (3)} with numpy irfftn's Hermitian projection, and the
+// spectra kernels out[s] = scale m_s in with their adjoint.
 #pragma once
-#include "mcpm_internal.h"
-
-#define TWO_PI 6.283185307179586f
+#include "kmode_dev.h"
 
 namespace {
-
-__device__ __forceinline__ float kfreq(int i, int n) {
-    int s = (i < (n + 1) / 2) ? i : i - n;
-    return TWO_PI * (float)s / (float)n;
-}
-
-struct BMode {
-    float k[3];     // physical wavevector
-    bool nyq[3], special;
-    float zw;
-};
-__device__ __forceinline__ BMode bdecode(const Geom &g, float kx, float ky, float kz, uint32_t idx) {
-    BMode m;
-    const int iz = idx % (uint32_t)g.nzh;
-    const uint32_t r = idx / (uint32_t)g.nzh;
-    const int iy = r % (uint32_t)g.ny, ix = r / (uint32_t)g.ny;
-    m.k[0] = kfreq(ix, g.nx) * kx;
-    m.k[1] = kfreq(iy, g.ny) * ky;
-    m.k[2] = TWO_PI * (float)iz / (float)g.nz * kz;
-    m.nyq[0] = !(g.nx & 1) && ix == g.nx / 2;
-    m.nyq[1] = !(g.ny & 1) && iy == g.ny / 2;
-    m.nyq[2] = iz == g.nz / 2;
-    m.special = iz == 0 || m.nyq[2];
-    m.zw = m.special ? 1.f : 2.f;
-    return m;
-}
 
 // the 10 multipliers y_s = irfftn(m_s X): real part re[s] (s = 0..6) or imaginary part im (s = 7..9)
 //  0: 1   1: kx kx/k2   2: ky ky/k2   3: kx ky/k2   4: kx kz/k2   5: ky kz/k2   6: -k2   7..9: i k_c
 // `herm`: apply numpy irfftn's projection on the kz = 0 / Nyquist planes (odd number of Nyquist factors -> 0)
-__device__ __forceinline__ void multipliers(const BMode &m, bool herm, float (&re)[7], float (&im)[3]) {
+__device__ __forceinline__ void multipliers(const KMode &m, bool herm, float (&re)[7], float (&im)[3]) {
     const float k2 = m.k[0] * m.k[0] + m.k[1] * m.k[1] + m.k[2] * m.k[2];
     const float ik2 = k2 == 0.f ? 0.f : 1.f / k2;
     const bool pr = herm && m.special;
@@ -54,11 +26,11 @@ __device__ __forceinline__ void multipliers(const BMode &m, bool herm, float (&r
 
 // GROUP 0: spectra 0..5 (6 outputs), GROUP 1: spectra 6..9 (4 outputs); out[s] = scale * m_s * in
 template <int GROUP>
-__global__ __launch_bounds__(256) void bias_spectra_kernel(Geom g, float kx, float ky, float kz, float scale,
+__global__ __launch_bounds__(256) void bias_spectra_kernel(KGeom kg, float scale,
                                                            const float2 *__restrict__ in, float2 *__restrict__ out, int64_t Mh) {
     const uint32_t idx = blockIdx.x * 256u + threadIdx.x;
     if (idx >= Mh) return;
-    const BMode m = bdecode(g, kx, ky, kz, idx);
+    const KMode m = kdecode(kg, idx);
     float re[7], im[3];
     multipliers(m, true, re, im);
     const float2 v = in[idx];
@@ -74,12 +46,12 @@ __global__ __launch_bounds__(256) void bias_spectra_kernel(Geom g, float kx, flo
 
 // out (+)= scale * zw * sum_s conj(m_s) in[s]   (adjoint of irfftn o multiply; un-projected multipliers)
 template <int GROUP>
-__global__ __launch_bounds__(256) void bias_spectra_vjp_kernel(Geom g, float kx, float ky, float kz, float scale,
+__global__ __launch_bounds__(256) void bias_spectra_vjp_kernel(KGeom kg, float scale,
                                                                const float2 *__restrict__ in, float2 *__restrict__ out,
                                                                int64_t Mh, int accumulate) {
     const uint32_t idx = blockIdx.x * 256u + threadIdx.x;
     if (idx >= Mh) return;
-    const BMode m = bdecode(g, kx, ky, kz, idx);
+    const KMode m = kdecode(kg, idx);
     float re[7], im[3];
     multipliers(m, false, re, im);
     float ar = 0.f, ai = 0.f;

@@ -24,11 +24,11 @@ struct Coef6 {
 };
 
 // out[0] = scale (-k^2) in, out[1] = scale phi (phi may be NULL: one spectrum)
-__global__ __launch_bounds__(256) void eul_lap_phi_kernel(Geom g, float kx, float ky, float kz, float scale, const float2 *__restrict__ in,
+__global__ __launch_bounds__(256) void eul_lap_phi_kernel(KGeom kg, float scale, const float2 *__restrict__ in,
                                                           const float2 *__restrict__ phi, float2 *__restrict__ out, int64_t Mh) {
     const uint32_t idx = blockIdx.x * 256u + threadIdx.x;
     if (idx >= Mh) return;
-    const BMode m = bdecode(g, kx, ky, kz, idx);
+    const KMode m = kdecode(kg, idx);
     float re[7], im[3];
     multipliers(m, true, re, im);
     const float2 v = in[idx];
@@ -40,11 +40,13 @@ __global__ __launch_bounds__(256) void eul_lap_phi_kernel(Geom g, float kx, floa
 }
 
 // adjoint: mk_bar += scale zw (-k^2) in[0] (its zero mode set to 0: the forward pass drops that mode), phi_bar = scale zw in[1]
+// (kphys arrives as three scalars here: handed over inside KGeom, the compiler pairs other components of k^2 = k0 k0 + k1 k1 + k2 k2 into its
+// packed multiply, another product is the one fused into the sum, and mk_bar changes in its last bit)
 __global__ __launch_bounds__(256) void eul_lap_phi_vjp_kernel(Geom g, float kx, float ky, float kz, float scale, const float2 *__restrict__ in,
                                                               float2 *__restrict__ mk_bar, float2 *__restrict__ phi_bar, int64_t Mh) {
     const uint32_t idx = blockIdx.x * 256u + threadIdx.x;
     if (idx >= Mh) return;
-    const BMode m = bdecode(g, kx, ky, kz, idx);
+    const KMode m = kdecode(KGeom{g, {kx, ky, kz}}, idx);
     float re[7], im[3];
     multipliers(m, false, re, im);
     const float s = scale * m.zw;
@@ -158,17 +160,18 @@ int mcpm_eulerian_bias_f32(mcpm_plan *p, const float *matter_k, const float *phi
                            float *w, float *saved, double *moments) {
     if (!p) return MCPM_E_ARG;
     MCPM_REQUIRE(p, matter_k && coef6 && w && saved && moments, MCPM_E_ARG, "mcpm_eulerian_bias_f32: null buffer");
-    MCPM_REQUIRE(p, !p->g.xslab, MCPM_E_UNSUPPORTED, "mcpm_eulerian_bias_f32: not slab-decomposed");
+    KGeom kg;
+    MCPM_TRY(kgeom_arg(p, "mcpm_eulerian_bias_f32", kpx, kpy, kpz, &kg));
     const int64_t M = p->M, Mh = p->Mh;
     const unsigned nbh = (unsigned)((Mh + 255) / 256), nb = (unsigned)((M + 255) / 256);
     const float scale = 1.f / (float)M;
     const Coef6 B{coef6[0], coef6[1], coef6[2], coef6[3], coef6[4], coef6[5]};
     float *spec = p->spec;
-    bias_spectra_kernel<0><<<nbh, 256, 0, p->stream>>>(p->g, kpx, kpy, kpz, scale, (const float2 *)matter_k, (float2 *)spec, Mh);
+    bias_spectra_kernel<0><<<nbh, 256, 0, p->stream>>>(kg, scale, (const float2 *)matter_k, (float2 *)spec, Mh);
     MCPM_LAUNCH_CHECK(p, "bias_spectra_kernel");
     MCPM_HIP(p, hipMemsetAsync(spec, 0, sizeof(float2), p->stream));      // the zero mode of d (the Hessian multipliers vanish there already)
     MCPM_TRY(mcpm_fft_c2r(p, spec, saved, 6));
-    eul_lap_phi_kernel<<<nbh, 256, 0, p->stream>>>(p->g, kpx, kpy, kpz, scale, (const float2 *)matter_k, (const float2 *)phi_k, (float2 *)spec, Mh);
+    eul_lap_phi_kernel<<<nbh, 256, 0, p->stream>>>(kg, scale, (const float2 *)matter_k, (const float2 *)phi_k, (float2 *)spec, Mh);
     MCPM_LAUNCH_CHECK(p, "eul_lap_phi_kernel");
     MCPM_TRY(mcpm_fft_c2r(p, spec, saved + 6 * M, phi_k ? 2 : 1));
     DetSum s;
@@ -191,7 +194,8 @@ int mcpm_eulerian_bias_vjp_f32(mcpm_plan *p, const float *saved, const double *m
     if (!p) return MCPM_E_ARG;
     MCPM_REQUIRE(p, saved && moments && coef6 && w_bar && matter_k_bar && coef_bar && (!has_phi || phi_k_bar), MCPM_E_ARG,
                  "mcpm_eulerian_bias_vjp_f32: null buffer");
-    MCPM_REQUIRE(p, !p->g.xslab, MCPM_E_UNSUPPORTED, "mcpm_eulerian_bias_vjp_f32: not slab-decomposed");
+    KGeom kg;
+    MCPM_TRY(kgeom_arg(p, "mcpm_eulerian_bias_vjp_f32", kpx, kpy, kpz, &kg));
     const int64_t M = p->M, Mh = p->Mh;
     const unsigned nbh = (unsigned)((Mh + 255) / 256), nb = (unsigned)((M + 255) / 256);
     const float scale = 1.f / (float)M;
@@ -214,7 +218,7 @@ int mcpm_eulerian_bias_vjp_f32(mcpm_plan *p, const float *saved, const double *m
         MCPM_LAUNCH_CHECK(p, "eul_vjp_cells_kernel");
     }
     MCPM_TRY(mcpm_fft_r2c(p, r, spec, 6));
-    bias_spectra_vjp_kernel<0><<<nbh, 256, 0, p->stream>>>(p->g, kpx, kpy, kpz, scale, (const float2 *)spec, (float2 *)matter_k_bar, Mh, 0);
+    bias_spectra_vjp_kernel<0><<<nbh, 256, 0, p->stream>>>(kg, scale, (const float2 *)spec, (float2 *)matter_k_bar, Mh, 0);
     MCPM_LAUNCH_CHECK(p, "bias_spectra_vjp_kernel");
     MCPM_TRY(mcpm_fft_r2c(p, r + 6 * M, spec, has_phi ? 2 : 1));
     eul_lap_phi_vjp_kernel<<<nbh, 256, 0, p->stream>>>(p->g, kpx, kpy, kpz, scale, (const float2 *)spec, (float2 *)matter_k_bar,

@@ -19,6 +19,7 @@
 #include "mcpm_internal.h"
 
 #include "fft_dev.h"
+#include "kmode_dev.h"
 
 // ------------------------------------------------------------------------------------------------
 // z passes: contiguous lines, two real lines per complex transform
@@ -252,8 +253,6 @@ __global__ __launch_bounds__(ColShape<N>::THREADS) void ycol_kernel(FGeom g, con
     }
 }
 
-#define MCPM_TWO_PI 6.283185307179586f
-
 // y pass that also applies the y / z force factors, so that only TWO spectra travel between the y and x passes:
 // the x pass produces A = IFFTx(-i kx L X) and G = IFFTx(-i L X), and the force spectra are A, ky G, kz G
 // (ky = 0 at its Nyquist on the kz = 0 / Nyquist planes, kz = 0 at its Nyquist: the Hermitian projection).
@@ -272,12 +271,12 @@ __global__ __launch_bounds__((ColShape<N, ML>::THREADS)) void ycol2_kernel(
     const cf *ib = in + li.plane(plane) + kzi;
     cf *ob = out + lo.plane(plane) + kzi;
     const bool special = (kzi == 0) || (kzi == g.nz / 2);
-    const float fz = (kzi == g.nz / 2) ? 0.f : MCPM_TWO_PI * (float)kzi / (float)g.nz;
+    const float fz = (kzi == g.nz / 2) ? 0.f : TWO_PI * (float)kzi / (float)g.nz;
     // one transform at a time (load, FFT, store) keeps the kernel at two workgroups per CU; offsets are recomputed
     // (a shift, a mask, a multiply) rather than held in registers
 #define ioff(m) ((uint32_t)((u + T * (m)) >> li.lgYB) * (uint32_t)li.SB + (uint32_t)((u + T * (m)) & (li.YB - 1)) * (uint32_t)g.nzp)
 #define ooff(m) ((uint32_t)((u + T * (m)) >> lo.lgYB) * (uint32_t)lo.SB + (uint32_t)((u + T * (m)) & (lo.YB - 1)) * (uint32_t)g.nzp)
-#define fy(m) ((special && (u + T * (m)) == N / 2) ? 0.f : MCPM_TWO_PI * (float)((u + T * (m)) < N / 2 ? (u + T * (m)) : (u + T * (m)) - N) / (float)N)
+#define fy(m) ((special && (u + T * (m)) == N / 2) ? 0.f : TWO_PI * (float)((u + T * (m)) < N / 2 ? (u + T * (m)) : (u + T * (m)) - N) / (float)N)
     const cf zero = mkc(0.f, 0.f);
     TL tile{l};
     cf v[8];
@@ -342,12 +341,7 @@ __global__ __launch_bounds__((ColShape<N, ML>::THREADS)) void ycol2_kernel(
 #undef fy
 }
 
-// k-space multipliers (nbody.py:109-163 with fd_order = inf), wavevectors from indices
-__device__ __forceinline__ float kfreq_i(int i, int n) {
-    int s = (i < (n + 1) / 2) ? i : i - n;
-    return MCPM_TWO_PI * (float)s / (float)n;
-}
-
+// k-space multipliers (nbody.py:109-163 with fd_order = inf), wavevectors from indices (kfreq: kmode_dev.h)
 // MODE 0: in (1 spectrum) -> forward x FFT -> {-i kx L X, -i L X} -> inverse x FFT -> out (2 spectra: A and G)
 // MODE 1: in (2 spectra a, b) -> forward x FFT -> i kx L FFTx(a) + i L FFTx(b) -> inverse x FFT -> out (1 spectrum)
 // (L = -scale/k^2; the y pass applies ky, kz: ycol2_kernel.)
@@ -368,9 +362,9 @@ __global__ __launch_bounds__((ColShape<N, ML>::THREADS)) void xfused_kernel(FGeo
     // element offsets (complex units, < 2^31): one-spectrum side and three-spectra side (without the c*SC term)
     uint32_t o1[8], o3[8];
     float sx[8], L[8];
-    const float ky = kfreq_i(iy, g.ny), kz = MCPM_TWO_PI * (float)kzi / (float)g.nz;
+    const float ky = kfreq(iy, g.ny), kz = TWO_PI * (float)kzi / (float)g.nz;
     const bool special = (kzi == 0) || (kzi == g.nz / 2);
-    const float dkx = MCPM_TWO_PI / (float)N;
+    const float dkx = TWO_PI / (float)N;
 #pragma unroll
     for (int m = 0; m < 8; ++m) {
         const int x = u + T * m;
@@ -451,11 +445,11 @@ __global__ __launch_bounds__(ColShape<N>::THREADS) void xspec_kernel(FGeom g, co
     const uint32_t off0 = (uint32_t)yl * g.nzp + kzi, xs = (uint32_t)xl.NYL * g.nzp;
     uint32_t os[8], o3[8];
     float kx[8], L[8];
-    const float ky = kfreq_i(iy, g.ny), kz = MCPM_TWO_PI * (float)kzi / (float)g.nz;
+    const float ky = kfreq(iy, g.ny), kz = TWO_PI * (float)kzi / (float)g.nz;
     const bool special = (kzi == 0) || (kzi == g.nz / 2);
     const bool nyq_y = iy == g.ny / 2, nyq_z = kzi == g.nz / 2;
     const float zw = special ? 1.f : 2.f;
-    const float dkx = MCPM_TWO_PI / (float)N;
+    const float dkx = TWO_PI / (float)N;
 #pragma unroll
     for (int m = 0; m < 8; ++m) {
         const int x = u + T * m;

@@ -1,6 +1,6 @@
 // Posterior of the initial field under the fiducial flat-sky Kaiser model, given the observed contrast (montecosmo/bricks.py:234-247,
 // kaiser_posterior; :159-164, lin2white; model.py:1444-1477, kaiser_post): where the reference's drivers start their chains.  Per stored
-// mode of the plan's half-spectrum, |k| in h/Mpc as power_mult_kernel forms it:
+// mode of the plan's half-spectrum, k in h/Mpc from the decoder of kmode_dev.h:
 //   mu     = safe_div(k . los, |k|)
 //   P      = amp * interp(|k|; ks, pows)            (0 outside the table)
 //   p      = P * cell_power                         (power in cell units)
@@ -10,47 +10,24 @@
 //   white[b] = scale_field * safe_div(sqrt(temp) stds noise[b] + means, sqrt(P))       (0 where P = 0, k = 0 included)
 // One thread per stored mode: the per-mode factors (the table search among them) are formed once in float64 and the chains are a loop
 // inside the thread.  A streaming pass: no LDS, no atomics, no reductions, so every output is bitwise the same call after call.
-#include "mcpm_internal.h"
-
-#define KP_TWO_PI 6.283185307179586f
+#include "tables_dev.h"
+#include "kmode_dev.h"
 
 namespace {
-
-__device__ __forceinline__ float kp_kfreq(int i, int n) {
-    const int s = (i < (n + 1) / 2) ? i : i - n;
-    return KP_TWO_PI * (float)s / (float)n;
-}
-
-// jnp.interp(x, xp, fp, left=0, right=0) on float64 device tables (interp_zero of bias.hip)
-__device__ __forceinline__ double kp_interp_zero(double x, const double *__restrict__ xp, const double *__restrict__ fp, int n) {
-    if (x < xp[0] || x > xp[n - 1]) return 0.;
-    int lo = 0, hi = n - 1;
-    while (hi - lo > 1) {
-        const int mid = (lo + hi) >> 1;
-        if (xp[mid] <= x) lo = mid; else hi = mid;
-    }
-    return fp[lo] + (fp[hi] - fp[lo]) / (xp[hi] - xp[lo]) * (x - xp[lo]);
-}
 
 struct KPost {
     double amp, los[3], g, f, b1E, var_noise, temp, scale_field, cell_power;
 };
 
-__global__ __launch_bounds__(256) void kaiser_post_kernel(Geom g, float kx, float ky, float kz, KPost q, const double *__restrict__ ks,
-                                                          const double *__restrict__ pows, int nt, const float2 *__restrict__ dobs,
+__global__ __launch_bounds__(256) void kaiser_post_kernel(KGeom kg, KPost q, Table pw, const float2 *__restrict__ dobs,
                                                           const float2 *__restrict__ noise, int n_chains, float2 *__restrict__ white,
                                                           float2 *__restrict__ means, float *__restrict__ stds, int64_t Mh) {
     const uint32_t idx = blockIdx.x * 256u + threadIdx.x;
     if (idx >= Mh) return;
-    // the wavevector as bdecode (bias.hip) forms it: float components, float64 norm
-    const int iz = idx % (uint32_t)g.nzh;
-    const uint32_t r = idx / (uint32_t)g.nzh;
-    const int iy = r % (uint32_t)g.ny, ix = r / (uint32_t)g.ny;
-    const double k0 = (double)(kp_kfreq(ix, g.nx) * kx), k1 = (double)(kp_kfreq(iy, g.ny) * ky),
-                 k2 = (double)(KP_TWO_PI * (float)iz / (float)g.nz * kz);
-    const double k = sqrt(k0 * k0 + k1 * k1 + k2 * k2);
+    const KMode m = kdecode(kg, idx);
+    const double k0 = (double)m.k[0], k1 = (double)m.k[1], k2 = (double)m.k[2], k = m.kn;
     const double mu = k == 0. ? 0. : (k0 * q.los[0] + k1 * q.los[1] + k2 * q.los[2]) / k;
-    const double P = q.amp * kp_interp_zero(k, ks, pows, nt);
+    const double P = q.amp * interp_zero(k, pw).t;
     const double p = P * q.cell_power;
     const double boost = q.g * (q.b1E + q.f * mu * mu);
     const double s2 = p / (1. + boost * boost / q.var_noise * p);
@@ -86,15 +63,18 @@ int mcpm_kaiser_post_c64(mcpm_plan *p, const float *delta_obs, const float *nois
                          double b1E, double var_noise, double temp, double scale_field, double cell_power, float *white, float *means,
                          float *stds) {
     if (!p) return MCPM_E_ARG;
-    MCPM_REQUIRE(p, delta_obs && ks && pows && ntab >= 2 && n_chains >= 1, MCPM_E_ARG, "mcpm_kaiser_post_c64: bad argument");
+    KGeom kg;
+    Table pw;
+    MCPM_TRY(table_arg(p, "mcpm_kaiser_post_c64", ks, pows, ntab, &pw));
+    MCPM_REQUIRE(p, delta_obs && n_chains >= 1, MCPM_E_ARG, "mcpm_kaiser_post_c64: bad argument");
     MCPM_REQUIRE(p, white || means || stds, MCPM_E_ARG, "mcpm_kaiser_post_c64: no output requested");
     MCPM_REQUIRE(p, var_noise > 0. && temp >= 0. && cell_power > 0. && amp >= 0., MCPM_E_ARG,
                  "mcpm_kaiser_post_c64: var_noise and cell_power must be positive, temp and amp non-negative");
     MCPM_REQUIRE(p, noise || temp == 0., MCPM_E_ARG, "mcpm_kaiser_post_c64: noise may be NULL only with temp = 0");
-    MCPM_REQUIRE(p, !p->g.xslab, MCPM_E_UNSUPPORTED, "mcpm_kaiser_post_c64: not slab-decomposed");
+    MCPM_TRY(kgeom_arg(p, "mcpm_kaiser_post_c64", kpx, kpy, kpz, &kg));
     const KPost q{amp, {los_x, los_y, los_z}, g, f, b1E, var_noise, temp, scale_field, cell_power};
     StageTimer st_(p, ST_KSPACE, (8.0 + 16.0 * n_chains) * p->Mh);
-    kaiser_post_kernel<<<(unsigned)((p->Mh + 255) / 256), 256, 0, p->stream>>>(p->g, kpx, kpy, kpz, q, ks, pows, ntab, (const float2 *)delta_obs,
+    kaiser_post_kernel<<<(unsigned)((p->Mh + 255) / 256), 256, 0, p->stream>>>(kg, q, pw, (const float2 *)delta_obs,
                                                                               temp == 0. ? nullptr : (const float2 *)noise, n_chains,
                                                                               (float2 *)white, (float2 *)means, stds, p->Mh);
     MCPM_LAUNCH_CHECK(p, "kaiser_post_kernel");

@@ -9,14 +9,10 @@
 // forward kernels apply that projection explicitly: on those two planes a factor (i k_a) changes sign
 // under k -> -k unless index a sits at its Nyquist, hence a multiplier with an odd number of Nyquist
 // factors projects to 0 and everything else is unchanged.  Output is identical to numpy's.
-#include "mcpm_internal.h"
+#include "kmode_dev.h"      // 2 pi, sfreq / kfreq and the index split; the decoder below is the force multipliers' own
 
-#define TWO_PI 6.283185307179586f
+namespace {
 
-__device__ __forceinline__ int sfreq(int i, int n) { return (i < (n + 1) / 2) ? i : i - n; }  // n * fftfreq(n)[i]
-__device__ __forceinline__ float kfreq(int i, int n) {  // 2*pi*fftfreq(n)[i]
-    return TWO_PI * (float)sfreq(i, n) / (float)n;
-}
 // sin(pi t / n) with the argument reduced in integers to [-pi/2, pi/2]: sinf of a float k near +-pi loses the relative
 // accuracy of sin k (1.2e-5 next to the Nyquist mode of a 1024 axis), the reduced argument keeps it.
 __device__ __forceinline__ float sinpi_frac(int t, int n) {
@@ -75,10 +71,8 @@ template <int LAP, int GRAD>
 __device__ __forceinline__ Mode decode(const KArgs &a, uint32_t idx) {
     Mode m;
     const Geom &g = a.g;
-    m.iz = idx % (uint32_t)g.nzh;
-    uint32_t r = idx / (uint32_t)g.nzh;
-    m.iy = r % (uint32_t)g.ny;
-    m.ix = r / (uint32_t)g.ny;
+    const Idx3 i3 = ksplit(g, idx);
+    m.ix = i3.ix, m.iy = i3.iy, m.iz = i3.iz;
     const int sx = sfreq(m.ix, g.nx), sy = sfreq(m.iy, g.ny);
     float kx = TWO_PI * (float)sx / (float)g.nx, ky = TWO_PI * (float)sy / (float)g.ny, kz = TWO_PI * (float)m.iz / (float)g.nz;
     float kk = lap_term<LAP>(kx) + lap_term<LAP>(ky) + lap_term<LAP>(kz);
@@ -208,9 +202,7 @@ __global__ __launch_bounds__(256) void kspace_phase_kernel(Geom g, float scale, 
                                                            float2 *__restrict__ out, int64_t Mh) {
     uint32_t idx = blockIdx.x * 256u + threadIdx.x;
     if (idx >= Mh) return;
-    const int iz = idx % (uint32_t)g.nzh;
-    const uint32_t r = idx / (uint32_t)g.nzh;
-    const int iy = r % (uint32_t)g.ny, ix = r / (uint32_t)g.ny;
+    const auto [ix, iy, iz] = ksplit(g, idx);
     const float kx = kfreq(ix, g.nx), ky = kfreq(iy, g.ny), kz = TWO_PI * (float)iz / (float)g.nz;
     float m = scale;
     if (deconv > 0) {
@@ -266,7 +258,9 @@ __global__ __launch_bounds__(256) void hessian_combine_vjp_kernel(const float *h
     hb[5 * M + i] = b * (h00 + h11);
 }
 
-static bool fd_ok(int fd) { return fd == MCPM_FD_INF || fd == MCPM_FD_2 || fd == MCPM_FD_4; }
+bool fd_ok(int fd) { return fd == MCPM_FD_INF || fd == MCPM_FD_2 || fd == MCPM_FD_4; }
+
+}  // namespace
 
 #define DISPATCH_FD(lap, grad, KERNEL, ...)                                                   \
     do {                                                                                      \

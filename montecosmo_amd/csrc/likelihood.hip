@@ -5,9 +5,9 @@
 #include "mcpm_internal.h"
 #include "reduce_dev.h"
 #include "cgh_dev.h"
+#include "kmode_dev.h"      // 2 pi and sfreq: this file's wavevector is (2 pi s) / box, not the decoder's
 
 #define LIK_HALF_LOG2PI_D 0.91893853320467274
-#define LIK_TWO_PI 6.283185307179586f
 
 namespace {
 
@@ -234,11 +234,6 @@ __global__ __launch_bounds__(256) void lik_real_phi_kernel(int64_t n, const floa
     block_partial<6>(v, part, gridDim.x, blockIdx.x);
 }
 
-__device__ __forceinline__ float lik_kfreq(int i, int n) {      // fftfreq: index n/2 of a full axis is -n/2
-    const int s = (i < (n + 1) / 2) ? i : i - n;
-    return LIK_TWO_PI * (float)s;
-}
-
 // 'fourier_gauss' (model.py:875-886): obs_rg[r] ~ Normal(cgh2rg(Y)[r], sigma), sigma = |s_e + s_k2e k^2 + s_kmu2e (k mu)^2| sqrt(selec)
 // laid out by cgh2rg(norm = "amp"): both real elements of a mode take that mode's sigma.  k mu = k . los (mu = k . los / |k| with
 // mu = 0 at k = 0, where k mu = 0 either way), so no division is formed.  One thread per STORED mode: rg2cgh's rule (cgh_source) names
@@ -258,7 +253,7 @@ __global__ __launch_bounds__(256) void lik_fourier_kernel(int nx, int ny, int nz
         const int k = (int)(idx % nzc);
         const int64_t t = idx / nzc;
         const int j = (int)(t % ny), i = (int)(t / ny);
-        const float k0 = lik_kfreq(i, nx) / bx, k1 = lik_kfreq(j, ny) / by, k2 = LIK_TWO_PI * (float)k / bz;      // h/Mpc
+        const float k0 = TWO_PI * (float)sfreq(i, nx) / bx, k1 = TWO_PI * (float)sfreq(j, ny) / by, k2 = TWO_PI * (float)k / bz;      // h/Mpc
         const float kk = k0 * k0 + k1 * k1 + k2 * k2, kl = k0 * lx + k1 * ly + k2 * lz, kl2 = kl * kl;
         const float lin = s_e + s_k2e * kk + s_kmu2e * kl2, al = fabsf(lin), sigma = al * sqsel;
         const float sg = (lin > 0.f ? 1.f : (lin < 0.f ? -1.f : 0.f)) * sqsel;

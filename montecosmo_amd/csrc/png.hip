@@ -1,79 +1,36 @@
 // Local primordial non-Gaussianity of the initial field (montecosmo/bricks.py:108-141, add_png) and its VJP:
 //   u = safe_div(lin, t(|k|)),  phi = irfftn(u),  psi = phi + fNL (phi^2 - <phi^2>),  out = t(|k|) rfftn(psi)
 // t = the phi -> delta transfer function, linearly interpolated from a 256-point DEVICE float64 table inside the k-space kernels
-// (zero outside the table, like power_mult_kernel: no mesh-sized table exists anywhere).  <phi^2> and the two sums of the adjoint
+// (interp_zero of tables_dev.h at the |k| of kmode_dev.h's decoder: no mesh-sized table exists anywhere).  <phi^2> and the two sums of the adjoint
 // are grid reductions in float64 with the fixed-order fold of reduce_dev.h; the cotangent of the table entries is scattered to the
 // two bracketing nodes with the interpolation weights and summed as integers (the scheme of lightcone_tables_vjp_kernel,
 // observe.hip), so every output is bitwise the same call after call.
 #include "mcpm_internal.h"
 #include "reduce_dev.h"
 #include "tables_dev.h"
-
-#define PNG_TWO_PI 6.283185307179586f
+#include "kmode_dev.h"
 
 namespace {
 
-__device__ __forceinline__ float png_kfreq(int i, int n) {
-    const int s = (i < (n + 1) / 2) ? i : i - n;
-    return PNG_TWO_PI * (float)s / (float)n;
-}
-
-struct PMode {
-    double k;      // |k| in h/Mpc (the arithmetic of power_mult_kernel)
-    float zw;      // irfftn multiplicity of the mode: 1 on the kz = 0 / Nyquist planes, 2 elsewhere
-};
-__device__ __forceinline__ PMode png_decode(const Geom &g, float kx, float ky, float kz, uint32_t idx) {
-    const int iz = idx % (uint32_t)g.nzh;
-    const uint32_t r = idx / (uint32_t)g.nzh;
-    const int iy = r % (uint32_t)g.ny, ix = r / (uint32_t)g.ny;
-    const float k0 = png_kfreq(ix, g.nx) * kx, k1 = png_kfreq(iy, g.ny) * ky, k2 = PNG_TWO_PI * (float)iz / (float)g.nz * kz;
-    PMode m;
-    m.k = sqrt((double)k0 * k0 + (double)k1 * k1 + (double)k2 * k2);
-    m.zw = (iz == 0 || iz == g.nz / 2) ? 1.f : 2.f;
-    return m;
-}
-
-// jnp.interp(x, xp, fp, left=0, right=0) with its bracket: lo < 0 outside the table (t = 0, no node receives a cotangent)
-struct TNode {
-    int lo;
-    double w, t;      // t = (1 - w) fp[lo] + w fp[lo + 1]
-};
-__device__ __forceinline__ TNode png_interp(double x, const double *__restrict__ xp, const double *__restrict__ fp, int n) {
-    TNode r;
-    r.lo = -1, r.w = 0., r.t = 0.;
-    if (x < xp[0] || x > xp[n - 1]) return r;
-    int lo = 0, hi = n - 1;
-    while (hi - lo > 1) {
-        const int mid = (lo + hi) >> 1;
-        if (xp[mid] <= x) lo = mid; else hi = mid;
-    }
-    r.lo = lo;
-    r.w = (x - xp[lo]) / (xp[hi] - xp[lo]);
-    r.t = fp[lo] + (fp[hi] - fp[lo]) / (xp[hi] - xp[lo]) * (x - xp[lo]);
-    return r;
-}
-
 // ---- forward ---------------------------------------------------------------------------------------------------------------
 // out = scale * safe_div(in, t)      (scale = 1 / M: the C2R behind it is unnormalised);  lap: times -|k|^2 (the Laplacian of phi)
-__global__ __launch_bounds__(256) void png_div_kernel(Geom g, float kx, float ky, float kz, const double *__restrict__ ks,
-                                                      const double *__restrict__ tt, int nt, float scale, int lap,
+__global__ __launch_bounds__(256) void png_div_kernel(KGeom kg, Table tt, float scale, int lap,
                                                       const float2 *__restrict__ in, float2 *__restrict__ out, int64_t Mh) {
     const uint32_t idx = blockIdx.x * 256u + threadIdx.x;
     if (idx >= Mh) return;
-    const PMode m = png_decode(g, kx, ky, kz, idx);
-    const float t = (float)png_interp(m.k, ks, tt, nt).t;
-    if (lap) scale *= -(float)(m.k * m.k);
+    const KMode m = kdecode(kg, idx);
+    const float t = (float)interp_zero(m.kn, tt).t;
+    if (lap) scale *= -(float)(m.kn * m.kn);
     const float2 v = in[idx];
     out[idx] = t == 0.f ? make_float2(0.f, 0.f) : make_float2(scale * (v.x / t), scale * (v.y / t));
 }
 
 // in place: io *= t
-__global__ __launch_bounds__(256) void png_mult_kernel(Geom g, float kx, float ky, float kz, const double *__restrict__ ks,
-                                                       const double *__restrict__ tt, int nt, float2 *__restrict__ io, int64_t Mh) {
+__global__ __launch_bounds__(256) void png_mult_kernel(KGeom kg, Table tt, float2 *__restrict__ io, int64_t Mh) {
     const uint32_t idx = blockIdx.x * 256u + threadIdx.x;
     if (idx >= Mh) return;
-    const PMode m = png_decode(g, kx, ky, kz, idx);
-    const float t = (float)png_interp(m.k, ks, tt, nt).t;
+    const KMode m = kdecode(kg, idx);
+    const float t = (float)interp_zero(m.kn, tt).t;
     const float2 v = io[idx];
     io[idx] = make_float2(t * v.x, t * v.y);
 }
@@ -101,13 +58,12 @@ __global__ __launch_bounds__(256) void png_quad_kernel(const float *__restrict__
 // ---- adjoint ---------------------------------------------------------------------------------------------------------------
 // cotangent of Psi = rfftn(psi) from the cotangent of out, ready for the unnormalised C2R that is the adjoint of rfftn under the
 // real-pair convention: the doubly counted modes are halved first (the C2R applies irfftn's multiplicity weights)
-__global__ __launch_bounds__(256) void png_vjp_in_kernel(Geom g, float kx, float ky, float kz, const double *__restrict__ ks,
-                                                         const double *__restrict__ tt, int nt, const float2 *__restrict__ ob,
+__global__ __launch_bounds__(256) void png_vjp_in_kernel(KGeom kg, Table tt, const float2 *__restrict__ ob,
                                                          float2 *__restrict__ out, int64_t Mh) {
     const uint32_t idx = blockIdx.x * 256u + threadIdx.x;
     if (idx >= Mh) return;
-    const PMode m = png_decode(g, kx, ky, kz, idx);
-    const float t = (float)png_interp(m.k, ks, tt, nt).t * (m.zw == 2.f ? 0.5f : 1.f);
+    const KMode m = kdecode(kg, idx);
+    const float t = (float)interp_zero(m.kn, tt).t * (m.zw == 2.f ? 0.5f : 1.f);
     const float2 v = ob[idx];
     out[idx] = make_float2(t * v.x, t * v.y);
 }
@@ -139,18 +95,17 @@ __global__ __launch_bounds__(256) void png_quad_vjp_kernel(const float *__restri
 
 // u_bar = zw / M * (R2C(phi_bar) - k^2 R2C(lap_phi_bar))  ->  lin_bar = safe_div(u_bar, t), and the per-mode cotangent of t from both of its uses:
 //   multiply  out = t Psi:  Re(conj(out_bar) Psi),  Psi = out / t;      divide  u = lin / t:  -Re(conj(u_bar) lin) / t^2
-__global__ __launch_bounds__(256) void png_vjp_out_kernel(Geom g, float kx, float ky, float kz, const double *__restrict__ ks,
-                                                          const double *__restrict__ tt, int nt, float scale, const float2 *__restrict__ lin,
+__global__ __launch_bounds__(256) void png_vjp_out_kernel(KGeom kg, Table tt, float scale, const float2 *__restrict__ lin,
                                                           const float2 *__restrict__ out, const float2 *__restrict__ ob,
                                                           const float2 *__restrict__ spec, const float2 *__restrict__ spec2,
                                                           float2 *__restrict__ lin_bar, double *__restrict__ tbar, int64_t Mh) {
     const uint32_t idx = blockIdx.x * 256u + threadIdx.x;
     if (idx >= Mh) return;
-    const PMode m = png_decode(g, kx, ky, kz, idx);
-    const float t = (float)png_interp(m.k, ks, tt, nt).t;
+    const KMode m = kdecode(kg, idx);
+    const float t = (float)interp_zero(m.kn, tt).t;
     float2 s = spec[idx];
     if (spec2) {      // u also feeds lap phi = irfftn(-k^2 u): both cotangents meet here, before the single divide by t
-        const float k2 = (float)(m.k * m.k);
+        const float k2 = (float)(m.kn * m.kn);
         const float2 s2 = spec2[idx];
         s.x -= k2 * s2.x, s.y -= k2 * s2.y;
     }
@@ -174,23 +129,22 @@ __global__ __launch_bounds__(256) void png_vjp_out_kernel(Geom g, float kx, floa
 // table cotangent: tbar[k] goes to the nodes (lo, lo + 1) of its bracket with the weights (1 - w, w), summed as integers so that the result
 // does not depend on the order (tables_dev.h, ORDER-INDEPENDENT SUMS; one kind).  A non-finite contribution makes the whole table NaN.
 template <int PASS>
-__global__ __launch_bounds__(256) void png_table_vjp_kernel(Geom g, float kx, float ky, float kz, const double *__restrict__ ks,
-                                                            const double *__restrict__ tt, int nt, const double *__restrict__ tbar, int64_t Mh,
+__global__ __launch_bounds__(256) void png_table_vjp_kernel(KGeom kg, Table tt, const double *__restrict__ tbar, int64_t Mh,
                                                             unsigned *__restrict__ mxbits, unsigned long long *__restrict__ acc) {
     extern __shared__ unsigned long long png_sh[];
     Acc<1> A;
-    acc_begin(A, png_sh, nt, mxbits, PASS);
+    acc_begin(A, png_sh, tt.n, mxbits, PASS);
     bool bad = false;
     for (int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x; idx < Mh; idx += (int64_t)gridDim.x * 256) {
-        const PMode m = png_decode(g, kx, ky, kz, (uint32_t)idx);
-        const TNode b = png_interp(m.k, ks, tt, nt);
+        const KMode m = kdecode(kg, (uint32_t)idx);
+        const TNode b = interp_zero(m.kn, tt);
         if (b.lo < 0) continue;
         const double v = tbar[idx];
         bad = bad || !(v == v);
         acc_add<PASS>(A, 0, 0, b.lo, v * (1. - b.w));
         acc_add<PASS>(A, 0, 0, b.lo + 1, v * b.w);
     }
-    acc_end<PASS>(A, nt, mxbits, acc, bad);
+    acc_end<PASS>(A, tt.n, mxbits, acc, bad);
 }
 
 // ---- PNG terms of the Lagrangian bias weights (montecosmo/bricks.py:413-441) -----------------------------------------------------
@@ -291,14 +245,17 @@ extern "C" {
 int mcpm_png_phi_f32(mcpm_plan *p, const float *lin_mesh, float kpx, float kpy, float kpz, const double *ks, const double *trans, int ntab,
                      float *phi, float *lap_phi) {
     if (!p) return MCPM_E_ARG;
-    MCPM_REQUIRE(p, lin_mesh && ks && trans && ntab >= 2 && phi && lap_phi, MCPM_E_ARG, "mcpm_png_phi_f32: bad argument");
-    MCPM_REQUIRE(p, !p->g.xslab, MCPM_E_UNSUPPORTED, "mcpm_png_phi_f32: not slab-decomposed");
+    KGeom kg;
+    Table tt;
+    MCPM_REQUIRE(p, lin_mesh && phi && lap_phi, MCPM_E_ARG, "mcpm_png_phi_f32: bad argument");
+    MCPM_TRY(table_arg(p, "mcpm_png_phi_f32", ks, trans, ntab, &tt));
+    MCPM_TRY(kgeom_arg(p, "mcpm_png_phi_f32", kpx, kpy, kpz, &kg));
     const int64_t Mh = p->Mh;
     const unsigned nbk = (unsigned)((Mh + 255) / 256);
     for (int lap = 0; lap < 2; ++lap) {
         {
             StageTimer st_(p, ST_KSPACE, 16.0 * Mh);
-            png_div_kernel<<<nbk, 256, 0, p->stream>>>(p->g, kpx, kpy, kpz, ks, trans, ntab, 1.f / (float)p->M, lap, (const float2 *)lin_mesh,
+            png_div_kernel<<<nbk, 256, 0, p->stream>>>(kg, tt, 1.f / (float)p->M, lap, (const float2 *)lin_mesh,
                                                        (float2 *)p->spec1, Mh);
             MCPM_LAUNCH_CHECK(p, "png_div_kernel");
         }
@@ -311,10 +268,13 @@ int mcpm_png_phi_f32(mcpm_plan *p, const float *lin_mesh, float kpx, float kpy, 
 int mcpm_png_div_f32(mcpm_plan *p, const float *in, float kpx, float kpy, float kpz, const double *ks, const double *trans, int ntab, float scale,
                      float *out) {
     if (!p) return MCPM_E_ARG;
-    MCPM_REQUIRE(p, in && ks && trans && ntab >= 2 && out, MCPM_E_ARG, "mcpm_png_div_f32: bad argument");
-    MCPM_REQUIRE(p, !p->g.xslab, MCPM_E_UNSUPPORTED, "mcpm_png_div_f32: not slab-decomposed");
+    KGeom kg;
+    Table tt;
+    MCPM_REQUIRE(p, in && out, MCPM_E_ARG, "mcpm_png_div_f32: bad argument");
+    MCPM_TRY(table_arg(p, "mcpm_png_div_f32", ks, trans, ntab, &tt));
+    MCPM_TRY(kgeom_arg(p, "mcpm_png_div_f32", kpx, kpy, kpz, &kg));
     StageTimer st_(p, ST_KSPACE, 16.0 * p->Mh);
-    png_div_kernel<<<(unsigned)((p->Mh + 255) / 256), 256, 0, p->stream>>>(p->g, kpx, kpy, kpz, ks, trans, ntab, scale, 0, (const float2 *)in,
+    png_div_kernel<<<(unsigned)((p->Mh + 255) / 256), 256, 0, p->stream>>>(kg, tt, scale, 0, (const float2 *)in,
                                                                           (float2 *)out, p->Mh);
     MCPM_LAUNCH_CHECK(p, "png_div_kernel");
     return MCPM_OK;
@@ -370,14 +330,17 @@ int mcpm_png_weights_vjp_f32(mcpm_plan *p, int64_t n, const float *dr, const flo
 int mcpm_png_add_f32(mcpm_plan *p, const float *lin_mesh, float kpx, float kpy, float kpz, const double *ks, const double *trans, int ntab,
                      float fnl, int phi_given, float *phi, float *out, double *mean_out) {
     if (!p) return MCPM_E_ARG;
-    MCPM_REQUIRE(p, lin_mesh && ks && trans && ntab >= 2 && phi && out, MCPM_E_ARG, "mcpm_png_add_f32: bad argument");
-    MCPM_REQUIRE(p, !p->g.xslab, MCPM_E_UNSUPPORTED, "mcpm_png_add_f32: not slab-decomposed");
+    KGeom kg;
+    Table tt;
+    MCPM_REQUIRE(p, lin_mesh && phi && out, MCPM_E_ARG, "mcpm_png_add_f32: bad argument");
+    MCPM_TRY(table_arg(p, "mcpm_png_add_f32", ks, trans, ntab, &tt));
+    MCPM_TRY(kgeom_arg(p, "mcpm_png_add_f32", kpx, kpy, kpz, &kg));
     const int64_t M = p->M, Mh = p->Mh;
     const unsigned nbk = (unsigned)((Mh + 255) / 256), nbr = (unsigned)((M + 255) / 256);
     if (!phi_given) {
         {
             StageTimer st_(p, ST_KSPACE, 16.0 * Mh);
-            png_div_kernel<<<nbk, 256, 0, p->stream>>>(p->g, kpx, kpy, kpz, ks, trans, ntab, 1.f / (float)M, 0, (const float2 *)lin_mesh,
+            png_div_kernel<<<nbk, 256, 0, p->stream>>>(kg, tt, 1.f / (float)M, 0, (const float2 *)lin_mesh,
                                                        (float2 *)p->spec1, Mh);
             MCPM_LAUNCH_CHECK(p, "png_div_kernel");
         }
@@ -397,7 +360,7 @@ int mcpm_png_add_f32(mcpm_plan *p, const float *lin_mesh, float kpx, float kpy, 
     if (mean_out) MCPM_HIP(p, hipMemcpyAsync(mean_out, mean, sizeof(double), hipMemcpyDeviceToDevice, p->stream));
     MCPM_TRY(mcpm_fft_r2c(p, p->rho, out, 1));
     StageTimer st_(p, ST_KSPACE, 16.0 * Mh);
-    png_mult_kernel<<<nbk, 256, 0, p->stream>>>(p->g, kpx, kpy, kpz, ks, trans, ntab, (float2 *)out, Mh);
+    png_mult_kernel<<<nbk, 256, 0, p->stream>>>(kg, tt, (float2 *)out, Mh);
     MCPM_LAUNCH_CHECK(p, "png_mult_kernel");
     return MCPM_OK;
 }
@@ -406,10 +369,13 @@ int mcpm_png_add_vjp_f32(mcpm_plan *p, const float *lin_mesh, const float *out, 
                          float kpz, const double *ks, const double *trans, int ntab, float fnl, const float *out_bar, const float *phi_bar,
                          const float *lap_phi_bar, float *lin_mesh_bar, double *fnl_bar, double *trans_bar) {
     if (!p) return MCPM_E_ARG;
-    MCPM_REQUIRE(p, lin_mesh && ks && trans && ntab >= 2 && lin_mesh_bar && fnl_bar && trans_bar, MCPM_E_ARG, "mcpm_png_add_vjp_f32: bad argument");
+    KGeom kg;
+    Table tt;
+    MCPM_REQUIRE(p, lin_mesh && lin_mesh_bar && fnl_bar && trans_bar, MCPM_E_ARG, "mcpm_png_add_vjp_f32: bad argument");
+    MCPM_TRY(table_arg(p, "mcpm_png_add_vjp_f32", ks, trans, ntab, &tt));
     MCPM_REQUIRE(p, out_bar ? (out && phi && mean) : (phi_bar != nullptr), MCPM_E_ARG,
                  "mcpm_png_add_vjp_f32: out_bar needs out, phi and mean; without out_bar, phi_bar is the cotangent to pull back");
-    MCPM_REQUIRE(p, !p->g.xslab, MCPM_E_UNSUPPORTED, "mcpm_png_add_vjp_f32: not slab-decomposed");
+    MCPM_TRY(kgeom_arg(p, "mcpm_png_add_vjp_f32", kpx, kpy, kpz, &kg));
     const int64_t M = p->M, Mh = p->Mh;
     const unsigned nbk = (unsigned)((Mh + 255) / 256), nbr = (unsigned)((M + 255) / 256);
     // the table cotangent's accumulators, cleared here so that an oversized table is refused before anything is written.  They lie behind the
@@ -422,7 +388,7 @@ int mcpm_png_add_vjp_f32(mcpm_plan *p, const float *lin_mesh, const float *out, 
         float *pb = p->rho;
         {
             StageTimer st_(p, ST_KSPACE, 16.0 * Mh);
-            png_vjp_in_kernel<<<nbk, 256, 0, p->stream>>>(p->g, kpx, kpy, kpz, ks, trans, ntab, (const float2 *)out_bar, (float2 *)p->spec1, Mh);
+            png_vjp_in_kernel<<<nbk, 256, 0, p->stream>>>(kg, tt, (const float2 *)out_bar, (float2 *)p->spec1, Mh);
             MCPM_LAUNCH_CHECK(p, "png_vjp_in_kernel");
         }
         MCPM_TRY(mcpm_fft_c2r(p, p->spec1, pb, 1));
@@ -444,13 +410,13 @@ int mcpm_png_add_vjp_f32(mcpm_plan *p, const float *lin_mesh, const float *out, 
     if (spec2) MCPM_TRY(mcpm_fft_r2c(p, lap_phi_bar, spec2, 1));
     double *tbar = reinterpret_cast<double *>(p->spec);      // Mh doubles of the six-spectrum scratch
     StageTimer st_(p, ST_KSPACE, 56.0 * Mh);
-    png_vjp_out_kernel<<<nbk, 256, 0, p->stream>>>(p->g, kpx, kpy, kpz, ks, trans, ntab, 1.f / (float)M, (const float2 *)lin_mesh,
+    png_vjp_out_kernel<<<nbk, 256, 0, p->stream>>>(kg, tt, 1.f / (float)M, (const float2 *)lin_mesh,
                                                    (const float2 *)out, (const float2 *)out_bar, (const float2 *)p->spec1,
                                                    (const float2 *)spec2, (float2 *)lin_mesh_bar, tbar, Mh);
     MCPM_LAUNCH_CHECK(p, "png_vjp_out_kernel");
-    png_table_vjp_kernel<0><<<t.nb, 256, 0, p->stream>>>(p->g, kpx, kpy, kpz, ks, trans, ntab, tbar, Mh, t.mx, t.acc);
+    png_table_vjp_kernel<0><<<t.nb, 256, 0, p->stream>>>(kg, tt, tbar, Mh, t.mx, t.acc);
     MCPM_LAUNCH_CHECK(p, "png_table_vjp_kernel");
-    png_table_vjp_kernel<1><<<t.nb, 256, t.lds, p->stream>>>(p->g, kpx, kpy, kpz, ks, trans, ntab, tbar, Mh, t.mx, t.acc);
+    png_table_vjp_kernel<1><<<t.nb, 256, t.lds, p->stream>>>(kg, tt, tbar, Mh, t.mx, t.acc);
     MCPM_LAUNCH_CHECK(p, "png_table_vjp_kernel");
     return mcpm_tab_finish(p, t, &ntab, 1, trans_bar);
 }

@@ -1,5 +1,6 @@
 // Table look-ups shared by the kernels that read the growth / distance tables per particle or per cell (observe.hip, kaiser.hip):
-// clamped linear interpolation in float64 with its bracket and slope, and the device side of the order-independent integer sums that
+// clamped linear interpolation in float64 with its bracket and slope, the zero-outside look-up of the k-space kernels (bias.hip, png.hip,
+// kaiser_post.hip) with the Table argument they take, and the device side of the order-independent integer sums that
 // contract per-element cotangents into the small cotangents of the tables (those two and png.hip).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -19,6 +20,39 @@ __device__ __forceinline__ double interp1(double x, const double *xp, const doub
     }
     slope = (fp[hi] - fp[lo]) / (xp[hi] - xp[lo]);
     return fp[lo] + slope * (x - xp[lo]);
+}
+
+// One table of the k-space kernels as they take it by value: n nodes x ascending and values f, device float64
+struct Table {
+    const double *x, *f;
+    int n;
+};
+// the entry points' side of it, with the check they all make
+__host__ inline int table_arg(mcpm_plan *p, const char *who, const double *x, const double *f, int n, Table *t) {
+    MCPM_REQUIRE(p, x && f && n >= 2, MCPM_E_ARG, std::string(who) + ": bad argument");
+    *t = Table{x, f, n};
+    return MCPM_OK;
+}
+// jnp.interp(x, xp, fp, left=0, right=0) with its bracket: lo < 0 outside the table (t = 0, no node receives a cotangent)
+struct TNode {
+    int lo;
+    double w, t;      // t = (1 - w) fp[lo] + w fp[lo + 1]
+};
+__device__ __forceinline__ TNode interp_zero(double x, const Table &tb) {
+    const double *__restrict__ xp = tb.x, *__restrict__ fp = tb.f;
+    const int n = tb.n;
+    TNode r;
+    r.lo = -1, r.w = 0., r.t = 0.;
+    if (x < xp[0] || x > xp[n - 1]) return r;
+    int lo = 0, hi = n - 1;
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if (xp[mid] <= x) lo = mid; else hi = mid;
+    }
+    r.lo = lo;
+    r.w = (x - xp[lo]) / (xp[hi] - xp[lo]);
+    r.t = fp[lo] + (fp[hi] - fp[lo]) / (xp[hi] - xp[lo]) * (x - xp[lo]);
+    return r;
 }
 
 // The light-cone tables as the entry points receive them (device float64): chi[nchi] ascending, a(chi)[nchi], a[ngrow], g[ngrow], f[ngrow]

@@ -1,7 +1,8 @@
-"""The mesh-side model kernels (csrc/bias.hip, csrc/png.hip) through the ABI at odd nx, ny and half-spectrum sizes that are no multiple
+"""The mesh-side model kernels (csrc/bias.hip, csrc/png.hip, csrc/kaiser_post.hip, csrc/eulerian.hip) through the ABI at odd nx, ny and half-spectrum sizes that are no multiple
 of a workgroup: mcpm_plan_create takes any nx, ny >= 2 and an even nz, and the kernels' mode decode has a Nyquist branch
 `!(n & 1) && i == n / 2` that no even mesh separates from `i == n / 2`.  Every axis has its own box length, so swapped axes cannot pass.
-Reference: tests/_bias_f64.py in float64 (k = 2 pi fftfreq(n) n / box, numpy's irfftn: an odd axis has no Nyquist plane).
+Reference: tests/_bias_f64.py, tests/_kaiser_post_f64.py and tests/_eulerian_f64.py in float64 (k = 2 pi fftfreq(n) n / box, numpy's irfftn:
+an odd axis has no Nyquist plane).
 
 Gates.  Forward: max |error| over a mesh / rms of that mesh (a single wrong mode is several percent of the rms on meshes this small) within
 4 x the same quantity of the float32 restatement (float32 multipliers with their 1 / M, complex64 products, float64 transforms): the rule of
@@ -16,6 +17,8 @@ import pytest
 pytestmark = pytest.mark.gpu
 
 import _bias_f64 as bf  # noqa: E402
+import _eulerian_f64 as ef  # noqa: E402
+import _kaiser_post_f64 as kpf  # noqa: E402
 from _sentinel import Buffers, gate, dev_sum, equal  # noqa: E402
 
 CASES = [((9, 15, 8), (90., 120., 100.)),      # both odd; Mh = 675: two full workgroups and a tail of 163
@@ -224,5 +227,123 @@ def test_png_phi_add_and_vjp(gpu, case):
     _fd_check(errs, f"png_add_vjp[{sid(case)}]-fNL", lambda f: Lx(X64, f=f), fNL, 1.0, float(scal[0]), cn)
     dirn = trans * rng.standard_normal(nt)
     _fd_check(errs, f"png_add_vjp[{sid(case)}]-table", lambda tr: Lx(X64, tr=tr), trans, dirn, float((scal[1:] * dirn).sum()), cn)
+    B.check_tails()
+    assert not errs, errs
+
+
+def _kaiser_post32(d, noise, shape, box, ks, pows, amp, los, g, f, b1E, var_noise, temp, scale_field, cell_power):
+    """The float32 restatement of kaiser_post_kernel: float32 wavevector components, their norm and every per-mode factor in float64, the
+    factors rounded to float32 and applied to the complex64 fields in float32.  -> white (chains first), means, stds."""
+    k = [c.astype(np.float64) for c in bf.kvec(shape, box, F32)]
+    kn = np.sqrt(k[0] * k[0] + k[1] * k[1] + k[2] * k[2])
+    mu = kpf.o.safe_div(k[0] * los[0] + k[1] * los[1] + k[2] * los[2], kn)
+    P = amp * np.interp(kn, ks, pows, left=0., right=0.)
+    p, boost = P * cell_power, g * (b1E + f * mu * mu)
+    s2 = p / (1. + boost * boost / var_noise * p)
+    sd, mfac = np.sqrt(s2), s2 * boost / var_noise
+    wfac = kpf.o.safe_div(scale_field, np.sqrt(P))
+    cm, cn = (wfac * mfac).astype(F32), (wfac * np.sqrt(temp) * sd).astype(F32)
+    return cm * d + cn * noise, mfac.astype(F32) * d, sd.astype(F32)
+
+
+@pytest.mark.parametrize("case", CASES, ids=sid)
+def test_kaiser_post(gpu, case):
+    """mcpm_kaiser_post_c64 with two chains, a line of sight along no axis and a power table over part of the mesh's |k| range: white, means
+    and stds exactly zero outside the table (k = 0 among the modes below it), within 4 x the float32 restatement elsewhere."""
+    import torch
+    from oracle import background as obg
+    plan, rng, shape, box, kp, X, M, Mh = _setup(case, 34)
+    ks, km = _table(shape, box, 0.31, 0.79)
+    pows = 3.0e2 * (ks / ks[4]) / (1 + (ks / ks[4]) ** 2.6)
+    cosmo, a, sigma8, b1E, var_noise, temp, sf, nc = obg.Planck18(), 0.7, 0.8, 1.6, 0.35, 0.5, 7 / 8, 2
+    los = np.array([0.48, -0.6, 0.64])
+    g, f, cell_power = float(kpf.o.a2g(cosmo, a)), float(kpf.o.a2f(cosmo, a)), float(np.prod(kp))
+    noise = (rng.standard_normal((nc,) + X.shape) + 1j * rng.standard_normal((nc,) + X.shape)).astype(np.complex64)
+    B = Buffers()
+    Xd, Nd = B.inp(X), B.inp(noise)
+    tab = torch.from_numpy(np.concatenate([ks, pows])).cuda()
+
+    def call():
+        white, means, stds = B.out(noise.shape, np.complex64), B.out(X.shape, np.complex64), B.out(X.shape)
+        plan.call("mcpm_kaiser_post_c64", Xd, Nd, nc, *kp, sigma8 ** 2, tab, tab[len(ks):], len(ks), *[float(l) for l in los], g, f, b1E,
+                  var_noise, temp, sf, cell_power, white, means, stds)
+        return [white, means, stds]
+    got_t = call()
+    assert equal(got_t, call())
+    white, means, stds = (t.cpu().numpy() for t in got_t)
+    X64 = X.astype(np.complex128)
+    m64, s64 = kpf.kaiser_posterior(X64, cosmo, a, np.array(box), var_noise, b1E, los, sigma8, (ks, pows))
+    w64 = np.stack([sf * kpf.lin2white(sigma8, temp ** .5 * s64 * noise[b].astype(np.complex128) + m64, shape, np.array(box), (ks, pows))
+                    for b in range(nc)])
+    w32, m32, s32 = _kaiser_post32(X, noise, shape, box, ks, pows, sigma8 ** 2, los, g, f, b1E, var_noise, temp, sf, cell_power)
+    outside = (km < ks[0]) | (km > ks[-1])
+    assert outside[0, 0, 0] and not s64[outside].any() and (s64[~outside] > 0).all()
+    assert not white[:, outside].any() and not means[outside].any() and not stds[outside].any(), "modes outside the table must be exactly zero"
+    errs = []
+    _gate_rel(errs, f"kaiser_post[{sid(case)}]-white", white, w64, w32)
+    _gate_rel(errs, f"kaiser_post[{sid(case)}]-means", means, m64, m32)
+    _gate_rel(errs, f"kaiser_post[{sid(case)}]-stds", stds, s64, s32)
+    B.check_tails()
+    assert not errs, errs
+
+
+@pytest.mark.parametrize("case", CASES, ids=sid)
+def test_eulerian_bias_and_vjp(gpu, case):
+    """mcpm_eulerian_bias_f32 and mcpm_eulerian_bias_vjp_f32, without and with phi_k."""
+    import ctypes as C
+    plan, rng, shape, box, kp, X, M, Mh = _setup(case, 35)
+    Pk = np.fft.rfftn(rng.standard_normal(shape)).astype(np.complex64)
+    coef = [float(F32(c)) for c in (1.7, 0.4, -0.3, 0.2, 0.5, 0.35)]
+    coef_c = (C.c_float * 6)(*coef)
+    wb = rng.standard_normal(shape).astype(F32)
+    wb64, X64, P64 = wb.astype(np.float64), X.astype(np.complex128), Pk.astype(np.complex128)
+    cn = np.linalg.norm(wb64)
+    B = Buffers()
+    Xd, Pd, wbd = B.inp(X), B.inp(Pk), B.cot(wb.reshape(-1))
+    errs = []
+    for phi in (False, True):
+        tag = f"eulerian[{sid(case)}]-{'phi' if phi else 'nophi'}"
+        P, P_64 = (Pk, P64) if phi else (None, None)
+
+        def forward():
+            w, saved, mom = B.out((M,)), B.out(((8 if phi else 7) * M,)), B.out((2,), np.float64)
+            plan.call("mcpm_eulerian_bias_f32", Xd, Pd if phi else None, *kp, coef_c, w, saved, mom)
+            return [w, saved, mom]
+
+        def vjp(fw):
+            mb, pb, cb = B.out(X.shape, np.complex64), B.out(X.shape, np.complex64) if phi else None, B.out((6,), np.float64)
+            plan.call("mcpm_eulerian_bias_vjp_f32", fw[1], fw[2], int(phi), *kp, coef_c, wbd, mb, pb, cb)
+            return [mb, pb, cb]
+        fw = forward()
+        assert equal(fw, forward())
+        (w64, mom64), (w32, _) = ef.eulerian_bias(X, P, box, coef), ef.eulerian_bias(X, P, box, coef, dtype=F32)
+        _gate_rel(errs, f"{tag}-w", fw[0].cpu().numpy().reshape(shape), w64, w32)
+        (f64, p64), (f32, p32) = ef.fields(X, P, box), ef.fields(X, P, box, dtype=F32)
+        row = lambda a, b: (a.astype(np.float64) * b.astype(np.float64) / M).reshape(1, -1)
+        mom = fw[2].cpu().numpy()
+        gate(errs, f"{tag}-d2", mom[0], mom64[0], dev_sum(row(f32[0], f32[0]), row(f64[0], f64[0]))[0])
+        if phi:
+            gate(errs, f"{tag}-phid", mom[1], mom64[1], dev_sum(row(p32, f32[0]), row(p64, f64[0]))[0])
+        else:
+            assert mom[1] == 0.
+        bar = vjp(fw)
+        assert equal(bar, vjp(fw))
+        mb, cb = bar[0].cpu().numpy().astype(np.complex128), bar[2].cpu().numpy()
+        assert np.isfinite(mb.view(np.float64)).all() and np.isfinite(cb).all() and mb[0, 0, 0] == 0
+        if not phi:
+            assert cb[4] == 0. and cb[5] == 0.
+
+        def L(x=X64, p=P_64, c=coef):
+            y = ef.eulerian_bias(x, p, box, c)[0]
+            return float((y * wb64).sum()), y
+        for j in range(2):
+            d = np.fft.rfftn(rng.standard_normal(shape))
+            _fd_check(errs, f"{tag}-matter_k-dir{j}", lambda x: L(x=x), X64, d, _pair(mb, d), cn)
+            if phi:
+                pb = bar[1].cpu().numpy().astype(np.complex128)
+                assert np.isfinite(pb.view(np.float64)).all()
+                _fd_check(errs, f"{tag}-phi_k-dir{j}", lambda p: L(p=p), P64, d, _pair(pb, d), cn)
+        dirn = rng.standard_normal(6) * ([1, 1, 1, 1, 1, 1] if phi else [1, 1, 1, 1, 0, 0])
+        _fd_check(errs, f"{tag}-coef", lambda c: L(c=c), np.array(coef), dirn, float((cb * dirn).sum()), cn)
     B.check_tails()
     assert not errs, errs
