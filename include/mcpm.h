@@ -374,6 +374,11 @@ int mcpm_bullfrog_step_vjp_from_f32(mcpm_plan *plan, const float *pos_in, const 
        gradient, but this repair is exact only to rounding (one ulp of max(|v_bar|, |tau' pos_bar|) per element).
      - mcpm_step_adjoint_particles*_f32 (hinted) keep v_bar in vel_bar and write the force cotangent to plan memory
        (mcpm_plan_chained_fb).
+     - A hint lives until the plan's next adjoint-step entry point RETURNS, with success or with an error: a call that fails
+       (its argument checks included) takes the hint with it, so a later step never finds one that was not meant for it.  An
+       entry point that is not an adjoint step ends a hint pending at its entry: mcpm_nbody_bf_vjp_f32 (it sets its own hints
+       from its second step on) and mcpm_lpt_vjp*_f32.  A pending CARRY is another matter: it is data in the caller's vel_bar and
+       keeps the repair above, after an error too.
    Only valid when the caller does not modify the cotangents in between; reading vel_bar in between shows the sum. */
 int mcpm_plan_hint_next_adjoint(mcpm_plan *plan, double beta_next, double tau_next);
 /* After a hinted mcpm_step_adjoint_particles_f32: *fb = plan-owned F_bar = beta (v_bar + tau x_bar) (Np x 3 floats) of the

@@ -707,6 +707,7 @@ static int step_adjoint_particles(mcpm_plan *p, const float *pos_in, const float
 static int lpt_vjp_host(mcpm_plan *p, const float *init_mesh, int lpt_order, const double *lpt_scalars, const float *dpos_bar, const float *vel_bar,
                         float *init_mesh_bar, int lap_fd, int grad_fd, const float *saved, double *scalar_bars) {
     double *sb = p->reduce + MCPM_RED_SCALARS;
+    p->hint_set = 0;      // not an adjoint step: a hint pending at entry ends here instead of reaching a later, unrelated step
     MCPM_HIP(p, hipMemsetAsync(sb, 0, sizeof(double) * 3, p->stream));
     MCPM_TRY(lpt_vjp_device(p, init_mesh, lpt_order, lpt_scalars, dpos_bar, vel_bar, init_mesh_bar, sb, lap_fd, grad_fd, saved));
     if (scalar_bars) {
@@ -900,6 +901,7 @@ int mcpm_nbody_bf_vjp_f32(mcpm_plan *p, const float *init_mesh, int n_steps, con
     const size_t nbars = 2 * (size_t)n_steps + MCPM_RED_SWEEP_TAIL;
     MCPM_HIP(p, hipMemsetAsync(alpha_bar, 0, sizeof(double) * nbars, p->stream));
     p->fb_valid = 0;
+    p->hint_set = 0;      // the sweep sets its own hints: one left pending by the caller is not meant for its first step
     for (int i = n_steps - 1; i >= 0; --i) {
         if (i > 0) MCPM_TRY(mcpm_plan_hint_next_adjoint(p, beta[i - 1], dg));
         // the first reverse step READS the loss cotangents where the caller has them and writes the running ones (no copy of 24 N bytes)

@@ -125,6 +125,9 @@ struct mcpm_plan {
     //     Pending until that call matches it (same pointers, same scalars as float) or any other adjoint-step call turns it back.
     //   fb_* (mcpm_step_adjoint_particles*_f32 + mcpm_plan_chained_fb: callers that compose the step, slabs): the kernel also
     //     wrote F_bar' = beta' u' to plan scratch and vel_bar is the true v_bar.
+    // Who resets hint_set: the adjoint particle kernel's launcher that consumes it; mcpm_fail (any failing call on the plan, so an
+    // adjoint step that fails its argument checks takes its hint with it); mcpm_nbody_bf_vjp_f32 and mcpm_lpt_vjp*_f32 at entry (not
+    // adjoint steps); the pitch probe.  fx_src (above) goes with it in mcpm_fail.
     int hint_set, fb_valid, carry_valid;
     float hint_beta, hint_tau, fb_beta, fb_tau, carry_beta, carry_tau;
     const void *fb_xb, *fb_vb, *carry_xb, *carry_vb;

@@ -10,6 +10,10 @@ int mcpm_fail(mcpm_plan *plan, int code, const std::string &msg) {
     if (plan) {
         plan->err = msg;
         if (code == MCPM_E_HIP) plan->det_stale = 1;      // a deterministic sum may not have run to its end (reduce.hip)
+        // a hint lives until the next adjoint-step entry point returns, with an error too: the call that failed may have been the one
+        // it was meant for, and no later call may find it (nor a weight maximum announced for an array that was never painted)
+        plan->hint_set = 0;
+        plan->fx_src = nullptr;
     } else {
         g_mcpm_create_error = msg;
     }
