@@ -13,8 +13,14 @@
 // reshuffling -- that is what lets the k-space multiply sit between them in registers.
 //   * z passes: lines are contiguous; two real lines ride one complex FFT (a + i b), split / merged with the
 //     Hermitian mirror through LDS.
-//   * y / x passes: a workgroup owns 16 adjacent kz columns of one (x or y) plane so every global access is a
-//     128-byte row segment; lines sit "line-fastest" in LDS, which keeps the exchanges bank-conflict free.
+//   * y / x passes: a workgroup owns 16 (one-column fused x pass: 8) adjacent kz columns of one (x or y) plane so every
+//     global access is a 128-byte (64-byte) row segment; lines sit "line-fastest" in LDS, which keeps the exchanges
+//     bank-conflict free.  The factor-carrying y passes and the forward fused x pass give every thread TWO adjacent
+//     columns (kz = 2j, 2j+1) up to N = 512: two independent line FFTs side by side that share the stage twiddles, every
+//     global access of a spectrum point 16 bytes per lane (a row segment is 8 lanes), every LDS exchange one 16-byte
+//     access per pair, half the threads for the same lines (ColShape; which pass runs which shape: col_pairs).
+//     In those passes every fused multiply-add is written out and -ffp-contract is off, so that a line rounds the same
+//     whatever shape holds it: the results are bit for bit those of the one-column forms.
 // Spectra live in a padded internal layout [nx][ny][nzp], nzp = nz/2 + 16, so that those segments are aligned.
 #include "mcpm_internal.h"
 
@@ -64,7 +70,8 @@ struct XLayout {
 // has its own L2: with 8 kz columns per workgroup a row segment is 64 bytes, HALF a 128-byte line, so in launch order the two
 // workgroups that share every line of their columns run on different XCDs and the line is fetched from HBM twice
 // (profiles/r01_pmc_traffic.json: 2.4 GB moved by the fused x pass for 1.6 GB of spectra).  Remapped, each XCD works a
-// contiguous run of (y row, kz block) pairs, so the neighbour's half line is an L2 hit.
+// contiguous run of (y row, kz block) pairs, so the neighbour's half line is an L2 hit.  (Only the 8-column forms need it: a
+// 16-column workgroup owns whole lines and runs in launch order, x_fused.)
 __device__ __forceinline__ void col_block(int remap, unsigned &bx, unsigned &by) {
     bx = blockIdx.x, by = blockIdx.y;
     if (remap) {
@@ -216,12 +223,47 @@ __global__ __launch_bounds__(256) void zinv3_il_kernel(FGeom g, const cf *__rest
 
 // ------------------------------------------------------------------------------------------------
 // column passes (y or x): 16 adjacent kz columns per workgroup
-template <int N, int ML = 16>
+// NL = kz columns per thread.  NL = 2: a thread owns the adjacent columns kz = 2j, 2j+1 of its block and runs their two line
+// FFTs side by side, so that every global access of a spectrum point is 16 bytes per lane (a 128-byte row segment is 8 lanes,
+// a wave instruction covers 8 segments) and the workgroup has half the threads for the same lines.
+template <int N, int ML = 16, int NL = 1>
 struct ColShape {
     static constexpr int T = FftShape<N>::T;
-    static constexpr int LINES = (1024 / T) < ML ? (1024 / T) : ML;
-    static constexpr int THREADS = T * LINES;
+    static constexpr int LINES = (1024 * NL / T) < ML ? (1024 * NL / T) : ML;
+    static constexpr int TCOLS = LINES / NL;   // thread-columns
+    static constexpr int THREADS = T * TCOLS;
 };
+// The pitch nzp is even and a pair starts at an even kz, so a pair is 16-byte aligned.  nzh = nz/2 + 1 is odd: the last pair
+// holds the Nyquist column and the first pad column (nzh < nzp: in bounds).  The pad column is never read -- it may hold
+// anything -- and takes part as a line of zeros; what a pass stores there is the transform of zeros.  Nothing reads it.
+template <int NL>
+__device__ __forceinline__ void ld_cols(cf (&v)[NL][8], int m, const cf *p, const bool (&ok)[NL]) {
+    if (NL == 1) v[0][m] = ok[0] ? *p : mkc(0.f, 0.f);
+    else {
+        const cf2 z = {0.f, 0.f, 0.f, 0.f};
+        const cf2 t = ok[0] ? *reinterpret_cast<const cf2 *>(p) : z;
+        v[0][m] = t.xy;
+        v[NL - 1][m] = ok[NL - 1] ? t.zw : mkc(0.f, 0.f);
+    }
+}
+template <int NL, bool NT>
+__device__ __forceinline__ void st_pair(cf *p, const cf (&o)[NL]) {
+    if (NL == 1) {
+        if (NT) NTSTORE(o[0], p);
+        else *p = o[0];
+    } else {
+        const cf2 t = __builtin_shufflevector(o[0], o[NL - 1], 0, 1, 2, 3);
+        if (NT) NTSTORE(t, reinterpret_cast<cf2 *>(p));
+        else *reinterpret_cast<cf2 *>(p) = t;
+    }
+}
+template <int NL, bool NT>
+__device__ __forceinline__ void st_cols(cf *p, const cf (&v)[NL][8], int m) {
+    cf o[NL];
+#pragma unroll
+    for (int i = 0; i < NL; ++i) o[i] = v[i][m];
+    st_pair<NL, NT>(p, o);
+}
 
 // FFT along y for every (plane, kz); in == out allowed when both layouts are equal
 template <int N, int SIGN>
@@ -258,81 +300,101 @@ __global__ __launch_bounds__(ColShape<N>::THREADS) void ycol_kernel(FGeom g, con
 // (ky = 0 at its Nyquist on the kz = 0 / Nyquist planes, kz = 0 at its Nyquist: the Hermitian projection).
 //   EXPAND  (inverse): in = {A, G} -> out = {IFFTy A, IFFTy(ky G), kz IFFTy G}
 //   CONTRACT (forward, adjoint): in = {a, b, c} -> out = {FFTy a, ky FFTy b + kz FFTy c}
-template <int N, bool EXPAND, int ML>
-__global__ __launch_bounds__((ColShape<N, ML>::THREADS)) void ycol2_kernel(
+template <int N, bool EXPAND, int ML, int NL>
+__global__ __launch_bounds__((ColShape<N, ML, NL>::THREADS)) void ycol2_kernel(
     FGeom g, const cf *__restrict__ in, cf *__restrict__ out, YLayout li, YLayout lo, const cf *__restrict__ W, int parts) {
-    constexpr int T = ColShape<N, ML>::T, LINES = ColShape<N, ML>::LINES;
+#pragma clang fp contract(off)   // the one fused multiply-add is written out (see fft8)
+    constexpr int T = ColShape<N, ML, NL>::T, LINES = ColShape<N, ML, NL>::LINES, TC = ColShape<N, ML, NL>::TCOLS;
     typedef Tile<N, LINES, true> TL;
-    __shared__ cf lds[TL::FLOATS2];
-    const int l = threadIdx.x % LINES, u = threadIdx.x / LINES;
-    const int kzi = blockIdx.x * LINES + l;
-    const bool ok = kzi < g.nzh;
+    __shared__ __attribute__((aligned(16))) cf lds[TL::FLOATS2];
+    const int l = (threadIdx.x % TC) * NL, u = threadIdx.x / TC;
+    const int kz0 = blockIdx.x * LINES + l;
     const int plane = li.X0 + blockIdx.y;                    // local x plane; component c adds c * BS
-    const cf *ib = in + li.plane(plane) + kzi;
-    cf *ob = out + lo.plane(plane) + kzi;
-    const bool special = (kzi == 0) || (kzi == g.nz / 2);
-    const float fz = (kzi == g.nz / 2) ? 0.f : TWO_PI * (float)kzi / (float)g.nz;
-    // one transform at a time (load, FFT, store) keeps the kernel at two workgroups per CU; offsets are recomputed
+    const cf *ib = in + li.plane(plane) + kz0;
+    cf *ob = out + lo.plane(plane) + kz0;
+    bool ok[NL], special[NL];
+    float fz[NL];
+#pragma unroll
+    for (int i = 0; i < NL; ++i) {   // only the kz factors differ between a thread's columns
+        const int kzi = kz0 + i;
+        ok[i] = kzi < g.nzh;
+        special[i] = (kzi == 0) || (kzi == g.nz / 2);
+        fz[i] = (kzi == g.nz / 2) ? 0.f : TWO_PI * (float)kzi / (float)g.nz;
+    }
+    // one transform at a time (load, FFT, store) keeps the register count down; offsets are recomputed
     // (a shift, a mask, a multiply) rather than held in registers
 #define ioff(m) ((uint32_t)((u + T * (m)) >> li.lgYB) * (uint32_t)li.SB + (uint32_t)((u + T * (m)) & (li.YB - 1)) * (uint32_t)g.nzp)
 #define ooff(m) ((uint32_t)((u + T * (m)) >> lo.lgYB) * (uint32_t)lo.SB + (uint32_t)((u + T * (m)) & (lo.YB - 1)) * (uint32_t)g.nzp)
-#define fy(m) ((special && (u + T * (m)) == N / 2) ? 0.f : TWO_PI * (float)((u + T * (m)) < N / 2 ? (u + T * (m)) : (u + T * (m)) - N) / (float)N)
-    const cf zero = mkc(0.f, 0.f);
+#define fy(i, m) ((special[i] && (u + T * (m)) == N / 2) ? 0.f : TWO_PI * (float)((u + T * (m)) < N / 2 ? (u + T * (m)) : (u + T * (m)) - N) / (float)N)
     TL tile{l};
-    cf v[8];
+    cf v[NL][8];
     // parts (uniform): bit 0 = the spectrum-0 transform, bit 1 = the other two (they travel in separate all-to-alls)
     if (EXPAND) {
         if (parts & 1) {
 #pragma unroll
-            for (int m = 0; m < 8; ++m) v[m] = ok ? ib[ioff(m)] : zero;
+            for (int m = 0; m < 8; ++m) ld_cols<NL>(v, m, &ib[ioff(m)], ok);
             fft_line<N, +1>(v, lds, W, u, tile);
-            if (ok) {
+            if (ok[0]) {
 #pragma unroll
-                for (int m = 0; m < 8; ++m) NTSTORE(v[m], &ob[ooff(m)]);
+                for (int m = 0; m < 8; ++m) st_cols<NL, true>(&ob[ooff(m)], v, m);
             }
         }
         if (!(parts & 2)) return;
-        cf gq[8];
+        cf gq[NL][8];
+        float f[NL][8];
 #pragma unroll
         for (int m = 0; m < 8; ++m) {
-            gq[m] = ok ? ib[li.BS + ioff(m)] : zero;
-            const float f = fy(m);
-            v[m] = mkc(f * gq[m].x, f * gq[m].y);
-        }
-        fft_line<N, +1>(v, lds, W, u, tile);
-        if (ok) {
+            ld_cols<NL>(gq, m, &ib[li.BS + ioff(m)], ok);
 #pragma unroll
-            for (int m = 0; m < 8; ++m) NTSTORE(v[m], &ob[lo.BS + ooff(m)]);
+            for (int i = 0; i < NL; ++i) {
+                f[i][m] = fy(i, m);
+                v[i][m] = gq[i][m];
+            }
+        }
+        fft_line_scaled<N, +1>(v, f, lds, W, u, tile);   // IFFTy(ky G): the factor rides the first butterflies
+        if (ok[0]) {
+#pragma unroll
+            for (int m = 0; m < 8; ++m) st_cols<NL, true>(&ob[lo.BS + ooff(m)], v, m);
         }
         fft_line<N, +1>(gq, lds, W, u, tile);
-        if (ok) {
+        if (ok[0]) {
 #pragma unroll
-            for (int m = 0; m < 8; ++m) NTSTORE(mkc(fz * gq[m].x, fz * gq[m].y), &ob[2 * lo.BS + ooff(m)]);
+            for (int m = 0; m < 8; ++m) {
+                cf o[NL];
+#pragma unroll
+                for (int i = 0; i < NL; ++i) o[i] = mkc(fz[i] * gq[i][m].x, fz[i] * gq[i][m].y);
+                st_pair<NL, true>(&ob[2 * lo.BS + ooff(m)], o);
+            }
         }
     } else {
         if (parts & 1) {
 #pragma unroll
-            for (int m = 0; m < 8; ++m) v[m] = ok ? ib[ioff(m)] : zero;
+            for (int m = 0; m < 8; ++m) ld_cols<NL>(v, m, &ib[ioff(m)], ok);
             fft_line<N, -1>(v, lds, W, u, tile);
-            if (ok) {
+            if (ok[0]) {
 #pragma unroll
-                for (int m = 0; m < 8; ++m) ob[ooff(m)] = v[m];
+                for (int m = 0; m < 8; ++m) st_cols<NL, false>(&ob[ooff(m)], v, m);
             }
         }
         if (!(parts & 2)) return;
-        cf c[8];
+        cf c[NL][8];
 #pragma unroll
         for (int m = 0; m < 8; ++m) {
-            v[m] = ok ? ib[li.BS + ioff(m)] : zero;
-            c[m] = ok ? ib[2 * li.BS + ioff(m)] : zero;
+            ld_cols<NL>(v, m, &ib[li.BS + ioff(m)], ok);
+            ld_cols<NL>(c, m, &ib[2 * li.BS + ioff(m)], ok);
         }
         fft_line<N, -1>(v, lds, W, u, tile);
         fft_line<N, -1>(c, lds, W, u, tile);
-        if (ok) {
+        if (ok[0]) {
 #pragma unroll
             for (int m = 0; m < 8; ++m) {
-                const float f = fy(m);
-                ob[lo.BS + ooff(m)] = mkc(f * v[m].x + fz * c[m].x, f * v[m].y + fz * c[m].y);
+                cf o[NL];
+#pragma unroll
+                for (int i = 0; i < NL; ++i) {
+                    const float f = fy(i, m);
+                    o[i] = mkc(fmaf(fz[i], c[i][m].x, f * v[i][m].x), fmaf(fz[i], c[i][m].y, f * v[i][m].y));
+                }
+                st_pair<NL, false>(&ob[lo.BS + ooff(m)], o);
             }
         }
     }
@@ -347,75 +409,92 @@ __global__ __launch_bounds__((ColShape<N, ML>::THREADS)) void ycol2_kernel(
 // (L = -scale/k^2; the y pass applies ky, kz: ycol2_kernel.)
 // The multiplier of component c at mode (kx, ky, kz) is s_c * (-i), s_c = k_c * (-scale/k^2), Hermitian-projected:
 // on the kz = 0 / Nyquist planes a component whose own index sits at Nyquist is dropped (kspace.hip header).
-template <int N, int MODE, int ML>
-__global__ __launch_bounds__((ColShape<N, ML>::THREADS)) void xfused_kernel(FGeom g, const cf *__restrict__ in, cf *__restrict__ out,
-                                                                          XLayout xl, float scale, const cf *__restrict__ W) {
-    constexpr int T = ColShape<N, ML>::T, LINES = ColShape<N, ML>::LINES;
+template <int N, int MODE, int ML, int NL>
+__global__ __launch_bounds__((ColShape<N, ML, NL>::THREADS)) void xfused_kernel(FGeom g, const cf *__restrict__ in, cf *__restrict__ out,
+                                                                              XLayout xl, float scale, const cf *__restrict__ W) {
+#pragma clang fp contract(off)   // the fused multiply-adds are written out (see fft8)
+    constexpr int T = ColShape<N, ML, NL>::T, LINES = ColShape<N, ML, NL>::LINES, TC = ColShape<N, ML, NL>::TCOLS;
     typedef Tile<N, LINES, true> TL;
-    __shared__ cf lds[TL::FLOATS2];
-    const int l = threadIdx.x % LINES, u = threadIdx.x / LINES;
+    __shared__ __attribute__((aligned(16))) cf lds[TL::FLOATS2];
+    const int l = (threadIdx.x % TC) * NL, u = threadIdx.x / TC;
     unsigned bx, by;
     col_block(xl.remap, bx, by);
-    const int kzi = bx * LINES + l, yl = by, iy = xl.iy0 + yl;
-    const bool ok = kzi < g.nzh;
-    const uint32_t off0 = (uint32_t)yl * g.nzp + kzi, xs = (uint32_t)xl.NYL * g.nzp;
+    const int kz0 = bx * LINES + l, yl = by, iy = xl.iy0 + yl;
+    const uint32_t off0 = (uint32_t)yl * g.nzp + kz0, xs = (uint32_t)xl.NYL * g.nzp;
     // element offsets (complex units, < 2^31): one-spectrum side and three-spectra side (without the c*SC term)
     uint32_t o1[8], o3[8];
-    float sx[8], L[8];
-    const float ky = kfreq(iy, g.ny), kz = TWO_PI * (float)kzi / (float)g.nz;
-    const bool special = (kzi == 0) || (kzi == g.nz / 2);
+    float sx[NL][8], L[NL][8];
+    bool ok[NL];
+    const float ky = kfreq(iy, g.ny);
     const float dkx = TWO_PI / (float)N;
 #pragma unroll
     for (int m = 0; m < 8; ++m) {
         const int x = u + T * m;
         o1[m] = xl.off(x, xs) + off0;      // the one-spectrum side is in the same rank-blocked (and chunked) layout
         o3[m] = o1[m];
-        const float kx = dkx * (float)(x < N / 2 ? x : x - N);
-        const float kk = kx * kx + ky * ky + kz * kz;
-        L[m] = kk == 0.f ? 0.f : -scale * __frcp_rn(kk);
-        sx[m] = (special && x == N / 2) ? 0.f : kx * L[m];
+    }
+#pragma unroll
+    for (int i = 0; i < NL; ++i) {   // only kz differs between a thread's columns
+        const int kzi = kz0 + i;
+        ok[i] = kzi < g.nzh;
+        const float kz = TWO_PI * (float)kzi / (float)g.nz;
+        const bool special = (kzi == 0) || (kzi == g.nz / 2);
+#pragma unroll
+        for (int m = 0; m < 8; ++m) {
+            const int x = u + T * m;
+            const float kx = dkx * (float)(x < N / 2 ? x : x - N);
+            const float kk = fmaf(kx, kx, ky * ky) + kz * kz;
+            L[i][m] = kk == 0.f ? 0.f : -scale * __frcp_rn(kk);
+            sx[i][m] = (special && x == N / 2) ? 0.f : kx * L[i][m];
+        }
     }
     TL tile{l};
     // The y and z multipliers are (ky, kz) * L(kx): constant factors of ONE x-dependent spectrum, so they share one
     // x transform -- two inverse (MODE 0) or forward (MODE 1) transforms instead of three.
     if (MODE == 0) {
-        cf v[8];
+        cf v[NL][8];
 #pragma unroll
-        for (int m = 0; m < 8; ++m) v[m] = ok ? in[o1[m]] : mkc(0.f, 0.f);
+        for (int m = 0; m < 8; ++m) ld_cols<NL>(v, m, &in[o1[m]], ok);
         fft_line<N, -1>(v, lds, W, u, tile);
-        cf w[8];
+        cf w[NL][8];
 #pragma unroll
-        for (int m = 0; m < 8; ++m) w[m] = mkc(sx[m] * v[m].y, -sx[m] * v[m].x);  // (a + i b)(-i s_x)
+        for (int i = 0; i < NL; ++i)
+#pragma unroll
+            for (int m = 0; m < 8; ++m) w[i][m] = mkc(sx[i][m] * v[i][m].y, -sx[i][m] * v[i][m].x);  // (a + i b)(-i s_x)
         fft_line<N, +1>(w, lds, W, u, tile);
-        if (ok) {
+        if (ok[0]) {
 #pragma unroll
-            for (int m = 0; m < 8; ++m) NTSTORE(w[m], &out[o3[m]]);
+            for (int m = 0; m < 8; ++m) st_cols<NL, true>(&out[o3[m]], w, m);
         }
 #pragma unroll
-        for (int m = 0; m < 8; ++m) w[m] = mkc(L[m] * v[m].y, -L[m] * v[m].x);  // (a + i b)(-i L)
+        for (int i = 0; i < NL; ++i)
+#pragma unroll
+            for (int m = 0; m < 8; ++m) w[i][m] = mkc(L[i][m] * v[i][m].y, -L[i][m] * v[i][m].x);  // (a + i b)(-i L)
         fft_line<N, +1>(w, lds, W, u, tile);
-        if (ok) {  // G: the y pass turns it into the y and z components (ycol2_kernel)
+        if (ok[0]) {  // G: the y pass turns it into the y and z components (ycol2_kernel)
             cf *og = out + xl.SC;
 #pragma unroll
-            for (int m = 0; m < 8; ++m) NTSTORE(w[m], &og[o3[m]]);
+            for (int m = 0; m < 8; ++m) st_cols<NL, true>(&og[o3[m]], w, m);
         }
     } else {
-        cf a[8], b[8];
+        cf a[NL][8], b[NL][8];
 #pragma unroll
         for (int m = 0; m < 8; ++m) {  // b = ky FFTy(f_bar_y) + kz FFTy(f_bar_z), formed by the y pass (ycol2_kernel)
-            a[m] = ok ? in[o3[m]] : mkc(0.f, 0.f);
-            b[m] = ok ? in[xl.SC + o3[m]] : mkc(0.f, 0.f);
+            ld_cols<NL>(a, m, &in[o3[m]], ok);
+            ld_cols<NL>(b, m, &in[xl.SC + o3[m]], ok);
         }
         fft_line<N, -1>(a, lds, W, u, tile);
         fft_line<N, -1>(b, lds, W, u, tile);
-        cf acc[8];
+        cf acc[NL][8];
 #pragma unroll
-        for (int m = 0; m < 8; ++m)  // (a + i b)(+i s): conj of the forward multipliers
-            acc[m] = mkc(-sx[m] * a[m].y - L[m] * b[m].y, sx[m] * a[m].x + L[m] * b[m].x);
+        for (int i = 0; i < NL; ++i)
+#pragma unroll
+            for (int m = 0; m < 8; ++m)  // (a + i b)(+i s): conj of the forward multipliers
+                acc[i][m] = mkc(fmaf(-sx[i][m], a[i][m].y, -(L[i][m] * b[i][m].y)), fmaf(sx[i][m], a[i][m].x, L[i][m] * b[i][m].x));
         fft_line<N, +1>(acc, lds, W, u, tile);
-        if (ok) {
+        if (ok[0]) {
 #pragma unroll
-            for (int m = 0; m < 8; ++m) NTSTORE(acc[m], &out[o1[m]]);
+            for (int m = 0; m < 8; ++m) st_cols<NL, true>(&out[o1[m]], acc, m);
         }
     }
 }
@@ -683,24 +762,29 @@ static XLayout xlayout(const mcpm_plan *p) {
     return XLayout{nyl, p->rank * nyl, p->nxl, lg2i(p->nxl), sbx, spec_elems(p), 0, lg2i(cw), cw, (uint32_t)(p->nranks * sbx)};
 }
 
-// kz columns per workgroup of the register-heavy passes (ycol2, xfused; 75-118 VGPRs, so a 1024-thread workgroup is
-// alone on its CU).  Fused x pass: 8 columns (512 threads at N = 512, two independent workgroups per CU, 64-byte row
-// segments) beat 16 (0.51 vs 0.53 ms); 4 columns (32-byte segments) are 2.3x SLOWER: a row segment must stay a whole
-// 64-byte access.  Factor-carrying y pass: with streaming stores 16 columns (128-byte segments) win (stage 0.423 vs 0.440
-// ms).  Knobs: MCPM_XCOL_LINES, MCPM_YCOL_LINES = 8 | 16 (MCPM_COL_LINES sets both).
+// Columns per THREAD (ColShape NL) of the passes that gained from two, and the axis lengths at which they did; measured at
+// 512^3, 256^3 and 128^3 against one column per thread (DESIGN finding 51, profiles/r06_*):
+//   ycol2 (expand and contract) and xfused mode 0: two columns, 16 columns per workgroup, at axis lengths 256 and 512;
+//   ycol: one column (two measured equal: 220 against 222 us at 512^3) -- its pair form is not built;
+//   xfused mode 1: one column, 8 per workgroup (two hold two input spectra per column: 170 VGPRs, one workgroup per CU,
+//   586 against 484 us at 512^3) -- its pair form is not built;
+//   N = 1024: one column (two chains in a 1024-thread workgroup do not fit 128 VGPRs).
+// MCPM_COL_PAIRS=0 puts every pass back on one column per thread (A/B runs).
+constexpr int PAIR_NMAX = 512;
+// below 256 nothing gains: at 128^3 xfused mode 0 runs 9.4 against 9.6 us and the contracting ycol2 15.8 against 14.2 us
+constexpr int PAIR_NMIN_YCOL2 = 256, PAIR_NMIN_XF0 = 256;
+static bool col_pairs(int n, int nmin) {
+    static const bool on = [] { const char *e = getenv("MCPM_COL_PAIRS"); return e ? atoi(e) != 0 : true; }();
+    return on && n >= nmin && n <= PAIR_NMAX;
+}
+
+// kz columns per WORKGROUP of the one-column forms of the register-heavy passes (ycol2, xfused).  Fused x pass: 8 columns
+// (512 threads at N = 512, 64-byte row segments; 16 columns are 1024 threads and spill); 4 columns (32-byte segments) are 2.3x
+// slower.  Factor-carrying y pass: 16.  Knobs: MCPM_XCOL_LINES (also the pair form: 8 | 16), MCPM_YCOL_LINES = 8 | 16.
 static int col_lines(const char *name, int dflt) {
     const char *e = getenv(name);
-    if (!e && dflt) e = getenv("MCPM_COL_LINES");
     const int v = e ? atoi(e) : dflt;
     return (v == 8 || v == 16) ? v : dflt;
-}
-static int col_lines_x() {
-    static const int v = col_lines("MCPM_XCOL_LINES", 8);
-    return v;
-}
-static int col_lines_y() {
-    static const int v = col_lines("MCPM_YCOL_LINES", 16);
-    return v;
 }
 
 static int y_columns(mcpm_plan *p, const cf *in, cf *out, int batch, int sign, bool in_packed, bool out_packed) {
@@ -725,17 +809,23 @@ static int y_columns2(mcpm_plan *p, const cf *in, cf *out, bool expand, bool in_
     const FGeom g = fgeom(p);
     const YLayout li = ylayout(p, in_packed), lo = ylayout(p, out_packed);
     StageTimer st_(p, expand ? ST_C2R : ST_R2C, pass_bytes(p, parts == 3 ? 3 : (parts == 1 ? 1 : 2)));
-#define CALLL(NN, ML)                                                                                  \
+#define CALLL(NN, ML, NL)                                                                              \
     {                                                                                                  \
-        constexpr int LINES = ColShape<NN, ML>::LINES, TH = ColShape<NN, ML>::THREADS;                 \
+        constexpr int LINES = ColShape<NN, ML, NL>::LINES, TH = ColShape<NN, ML, NL>::THREADS;         \
         dim3 grid((unsigned)((g.nzh + LINES - 1) / LINES), (unsigned)p->xwn);                          \
-        if (expand) ycol2_kernel<NN, true, ML><<<grid, TH, 0, p->stream>>>(g, in, out, li, lo, (const cf *)p->tw[1], parts);  \
-        else ycol2_kernel<NN, false, ML><<<grid, TH, 0, p->stream>>>(g, in, out, li, lo, (const cf *)p->tw[1], parts);        \
+        if (expand) ycol2_kernel<NN, true, ML, NL><<<grid, TH, 0, p->stream>>>(g, in, out, li, lo, (const cf *)p->tw[1], parts);  \
+        else ycol2_kernel<NN, false, ML, NL><<<grid, TH, 0, p->stream>>>(g, in, out, li, lo, (const cf *)p->tw[1], parts);        \
     }
-    static const int ysmall = col_lines("MCPM_YCOL_LINES_SMALL", 0);
-    const int ylines_small = ysmall ? ysmall : 16;
+    static const int ylines = col_lines("MCPM_YCOL_LINES", 16);
+    const bool pairs = col_pairs(g.ny, PAIR_NMIN_YCOL2);
 #define CALL(NN)                                                                                       \
-    if ((NN >= 512 ? col_lines_y() : ylines_small) == 8) CALLL(NN, 8) else CALLL(NN, 16)
+    if constexpr (NN <= PAIR_NMAX) {                                                                   \
+        if (pairs) {                                                                                   \
+            CALLL(NN, 16, 2)                                                                           \
+            break;                                                                                     \
+        }                                                                                              \
+    }                                                                                                  \
+    if (ylines == 8) CALLL(NN, 8, 1) else CALLL(NN, 16, 1)
     DISPATCH_N(g.ny, CALL)
 #undef CALL
 #undef CALLL
@@ -761,21 +851,25 @@ static int x_fused(mcpm_plan *p, const cf *in, cf *out, int mode) {
     const float scale = 1.f / ((float)g.nx * (float)g.ny * (float)g.nz);
     // one forward + one inverse x pass of (1 + 3) spectra and the k-space multiply
     StageTimer st_(p, ST_KSPACE, (32.0 * p->nxl * g.ny * g.nzh) + 4.0 * pass_bytes(p, 1));
-#define CALLL(NN, ML)                                                                                         \
+    // the XCD remap serves row segments that are HALF a 128-byte line (col_block): the 8-column one-column form.  A 16-column
+    // workgroup owns whole lines and runs in launch order (tools/xpass_bench.hip: 0.425 ms against 0.433 ms remapped).
+#define CALLL(NN, MODE, ML, NL)                                                                               \
     {                                                                                                         \
-        constexpr int LINES = ColShape<NN, ML>::LINES, TH = ColShape<NN, ML>::THREADS;                        \
+        constexpr int LINES = ColShape<NN, ML, NL>::LINES, TH = ColShape<NN, ML, NL>::THREADS;                \
         dim3 grid((unsigned)((g.nzh + LINES - 1) / LINES), (unsigned)nyl);                                    \
-        xl.remap = xcd_remap() && (grid.x * grid.y) % 8 == 0;                                                 \
-        if (mode == 0) xfused_kernel<NN, 0, ML><<<grid, TH, xf_lds_pad(), p->stream>>>(g, in, out, xl, scale, (const cf *)p->tw[0]); \
-        else xfused_kernel<NN, 1, ML><<<grid, TH, xf_lds_pad(), p->stream>>>(g, in, out, xl, scale, (const cf *)p->tw[0]);           \
+        xl.remap = LINES < 16 && xcd_remap() && (grid.x * grid.y) % 8 == 0;                                   \
+        xfused_kernel<NN, MODE, ML, NL><<<grid, TH, xf_lds_pad(), p->stream>>>(g, in, out, xl, scale, (const cf *)p->tw[0]); \
     }
-    // columns per workgroup: 8 at N >= 512 (above) and below it too -- with 16 the 2 -> 1 (adjoint) form takes 146 VGPRs at
-    // N = 256 (three waves per SIMD: 89 us at 256^3 against 61-67 us with 8) and the 1 -> 2 form 128 (56-60 vs 51 us).
-    // MCPM_XCOL_LINES_SMALL=16: round 2's choice.
-    static const int small_lines = col_lines("MCPM_XCOL_LINES_SMALL", 0);
-    const int lines_small = small_lines ? small_lines : 8;
+    static const int xlines = col_lines("MCPM_XCOL_LINES", 16);
+    const bool pairs = mode == 0 && col_pairs(g.nx, PAIR_NMIN_XF0);
 #define CALL(NN)                                                                                              \
-    if ((NN >= 512 ? col_lines_x() : lines_small) == 8) CALLL(NN, 8) else CALLL(NN, 16)
+    if constexpr (NN <= PAIR_NMAX) {                                                                          \
+        if (pairs) {                                                                                          \
+            if (xlines == 8) CALLL(NN, 0, 8, 2) else CALLL(NN, 0, 16, 2)                                      \
+            break;                                                                                            \
+        }                                                                                                     \
+    }                                                                                                         \
+    if (mode == 0) CALLL(NN, 0, 8, 1) else CALLL(NN, 1, 8, 1)
     DISPATCH_N(g.nx, CALL)
 #undef CALL
 #undef CALLL

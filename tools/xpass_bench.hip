@@ -12,66 +12,101 @@ enum { F_NOSYNC = 1, F_CONSTTW = 2, F_NOFFT = 4, F_NOLOAD = 8, F_NOSTORE = 16, F
 // F_BLOCKED: spectrum stored [y / 16][x][y % 16][kz] instead of [x][y][kz]: the x stride drops from 1.1 MB to 35 KB (an x line
 // then spans 9 two-megabyte pages instead of 285)
 
-template <int N, int ML>
+// NL = kz columns per thread (fftpm.hip, ColShape): 2 = the thread's adjacent columns as one 16-byte access
+template <int N, int ML, int NL = 1>
 struct CS {
     static constexpr int T = N / 8;
-    static constexpr int LINES = (1024 / T) < ML ? (1024 / T) : ML;
-    static constexpr int THREADS = T * LINES;
+    static constexpr int LINES = (1024 * NL / T) < ML ? (1024 * NL / T) : ML;
+    static constexpr int THREADS = T * LINES / NL;
 };
+template <int NL>
+__device__ __forceinline__ void ld_cols(cf (&v)[NL][8], int m, const cf *p, const bool (&ok)[NL]) {
+    if (NL == 1) v[0][m] = ok[0] ? *p : mkc(0.f, 0.f);
+    else {
+        const cf2 z = {0.f, 0.f, 0.f, 0.f};
+        const cf2 t = ok[0] ? *reinterpret_cast<const cf2 *>(p) : z;
+        v[0][m] = t.xy;
+        v[NL - 1][m] = ok[NL - 1] ? t.zw : mkc(0.f, 0.f);
+    }
+}
+template <int NL>
+__device__ __forceinline__ void st_cols(cf *p, const cf (&v)[NL][8], int m) {
+    if (NL == 1) __builtin_nontemporal_store(v[0][m], p);
+    else __builtin_nontemporal_store(__builtin_shufflevector(v[0][m], v[NL - 1][m], 0, 1, 2, 3), reinterpret_cast<cf2 *>(p));
+}
 
 // the library's kernel, single-GPU layout, with switches
-template <int N, int ML, int FL>
-__global__ __launch_bounds__((CS<N, ML>::THREADS)) void xf_kernel(int ny, int nz, int nzh, int nzp, const cf *__restrict__ in,
-                                                                 cf *__restrict__ out, int64_t SC, float scale, const cf *__restrict__ W,
-                                                                 int never) {
-    constexpr int T = CS<N, ML>::T, LINES = CS<N, ML>::LINES;
+template <int N, int ML, int FL, int NL = 1>
+__global__ __launch_bounds__((CS<N, ML, NL>::THREADS)) void xf_kernel(int ny, int nz, int nzh, int nzp, const cf *__restrict__ in,
+                                                                     cf *__restrict__ out, int64_t SC, float scale, const cf *__restrict__ W,
+                                                                     int never, int remap) {
+    constexpr int T = CS<N, ML, NL>::T, LINES = CS<N, ML, NL>::LINES, TC = LINES / NL;
     constexpr int DBG = FL & 3;
     typedef Tile<N, LINES, true> TL;
-    __shared__ cf lds[TL::FLOATS2];
-    const int l = threadIdx.x % LINES, u = threadIdx.x / LINES;
+    __shared__ __attribute__((aligned(16))) cf lds[TL::FLOATS2];
+    const int l = (threadIdx.x % TC) * NL, u = threadIdx.x / TC;
     const unsigned nb = gridDim.x * gridDim.y, b = blockIdx.y * gridDim.x + blockIdx.x;
-    const unsigned vv = (nb % 8 == 0) ? (b & 7u) * (nb >> 3) + (b >> 3) : b;
+    const unsigned vv = (remap && nb % 8 == 0) ? (b & 7u) * (nb >> 3) + (b >> 3) : b;
     const unsigned by = vv / gridDim.x, bx = vv - by * gridDim.x;
-    const int kzi = bx * LINES + l, iy = by;
-    const bool ok = kzi < nzh;
-    const uint32_t off0 = (uint32_t)iy * nzp + kzi, xs = (uint32_t)ny * nzp;
+    const int kz0 = bx * LINES + l, iy = by;
+    const uint32_t off0 = (uint32_t)iy * nzp + kz0, xs = (uint32_t)ny * nzp;
     uint32_t o1[8];
-    float sx[8], L[8];
+    float sx[NL][8], L[NL][8];
+    bool ok[NL];
     const int sy = iy < (ny + 1) / 2 ? iy : iy - ny;
-    const float ky = TWO_PI * (float)sy / (float)ny, kz = TWO_PI * (float)kzi / (float)nz;
-    const bool special = (kzi == 0) || (kzi == nz / 2);
+    const float ky = TWO_PI * (float)sy / (float)ny;
     const float dkx = TWO_PI / (float)N;
 #pragma unroll
     for (int m = 0; m < 8; ++m) {
         const int x = u + T * m;
-        o1[m] = (FL & F_BLOCKED) ? (((uint32_t)(iy >> 4) * N + x) * 16 + (iy & 15)) * (uint32_t)nzp + kzi : (uint32_t)x * xs + off0;
-        const float kx = dkx * (float)(x < N / 2 ? x : x - N);
-        const float kk = kx * kx + ky * ky + kz * kz;
-        L[m] = kk == 0.f ? 0.f : -scale * __frcp_rn(kk);
-        sx[m] = (special && x == N / 2) ? 0.f : kx * L[m];
+        o1[m] = (FL & F_BLOCKED) ? (((uint32_t)(iy >> 4) * N + x) * 16 + (iy & 15)) * (uint32_t)nzp + kz0 : (uint32_t)x * xs + off0;
+    }
+#pragma unroll
+    for (int i = 0; i < NL; ++i) {
+        const int kzi = kz0 + i;
+        ok[i] = kzi < nzh;
+        const float kz = TWO_PI * (float)kzi / (float)nz;
+        const bool special = (kzi == 0) || (kzi == nz / 2);
+#pragma unroll
+        for (int m = 0; m < 8; ++m) {
+            const int x = u + T * m;
+            const float kx = dkx * (float)(x < N / 2 ? x : x - N);
+            const float kk = fmaf(kx, kx, ky * ky) + kz * kz;   // as the library writes it
+            L[i][m] = kk == 0.f ? 0.f : -scale * __frcp_rn(kk);
+            sx[i][m] = (special && x == N / 2) ? 0.f : kx * L[i][m];
+        }
     }
     TL tile{l};
     cf tw[3];
     if (FL & F_PRETW) fft_twiddles<N>(W, u, tw);
-    cf v[8];
+    cf v[NL][8];
 #pragma unroll
-    for (int m = 0; m < 8; ++m) v[m] = (FL & F_NOLOAD) ? mkc((float)(u + m) * scale, (float)l) : (ok ? in[o1[m]] : mkc(0.f, 0.f));
+    for (int m = 0; m < 8; ++m) {
+        if (FL & F_NOLOAD) {
+#pragma unroll
+            for (int i = 0; i < NL; ++i) v[i][m] = mkc((float)(u + m) * scale, (float)(l + i));
+        } else ld_cols<NL>(v, m, &in[o1[m]], ok);
+    }
     if (!(FL & F_NOFFT)) { if (FL & F_PRETW) fft_line_tw<N, -1, TL, DBG>(v, lds, tw, u, tile); else fft_line<N, -1, TL, DBG>(v, lds, W, u, tile); }
-    cf w[8];
+    cf w[NL][8];
 #pragma unroll
-    for (int m = 0; m < 8; ++m) w[m] = mkc(sx[m] * v[m].y, -sx[m] * v[m].x);
+    for (int i = 0; i < NL; ++i)
+#pragma unroll
+        for (int m = 0; m < 8; ++m) w[i][m] = mkc(sx[i][m] * v[i][m].y, -sx[i][m] * v[i][m].x);
     if (!(FL & F_NOFFT)) { if (FL & F_PRETW) fft_line_tw<N, +1, TL, DBG>(w, lds, tw, u, tile); else fft_line<N, +1, TL, DBG>(w, lds, W, u, tile); }
-    if (ok && (!(FL & F_NOSTORE) || w[0].x == (float)never)) {
+    if (ok[0] && (!(FL & F_NOSTORE) || w[0][0].x == (float)never)) {
 #pragma unroll
-        for (int m = 0; m < 8; ++m) __builtin_nontemporal_store(w[m], &out[o1[m]]);
+        for (int m = 0; m < 8; ++m) st_cols<NL>(&out[o1[m]], w, m);
     }
 #pragma unroll
-    for (int m = 0; m < 8; ++m) w[m] = mkc(L[m] * v[m].y, -L[m] * v[m].x);
+    for (int i = 0; i < NL; ++i)
+#pragma unroll
+        for (int m = 0; m < 8; ++m) w[i][m] = mkc(L[i][m] * v[i][m].y, -L[i][m] * v[i][m].x);
     if (!(FL & F_NOFFT)) { if (FL & F_PRETW) fft_line_tw<N, +1, TL, DBG>(w, lds, tw, u, tile); else fft_line<N, +1, TL, DBG>(w, lds, W, u, tile); }
-    if (ok && (!(FL & F_NOSTORE) || w[0].x == (float)never)) {
+    if (ok[0] && (!(FL & F_NOSTORE) || w[0][0].x == (float)never)) {
         cf *og = out + SC;
 #pragma unroll
-        for (int m = 0; m < 8; ++m) __builtin_nontemporal_store(w[m], &og[o1[m]]);
+        for (int m = 0; m < 8; ++m) st_cols<NL>(&og[o1[m]], w, m);
     }
 }
 
@@ -256,12 +291,30 @@ int main() {
     CK(hipMemset(in, 0, ss * sizeof(cf)));
     const float scale = 1.f / ((float)N * ny * nz);
     const double gb = (double)N * ny * nzh * 8 * 3 / 1e9;
-#define RUN(ML, FL, label)                                                                                          \
+#define RUNX(ML, FL, NL, REMAP, label)                                                                              \
     {                                                                                                               \
-        dim3 grid((nzh + CS<N, ML>::LINES - 1) / CS<N, ML>::LINES, ny);                                             \
-        float ms = time_it([&] { xf_kernel<N, ML, FL><<<grid, CS<N, ML>::THREADS>>>(ny, nz, nzh, nzp, in, out, ss, scale, W, -12345); }); \
-        printf("%-58s lines %2d  %.4f ms  (%.2f TB/s of 1.6 GB)\n", label, ML, ms, gb / ms);                         \
+        dim3 grid((nzh + CS<N, ML, NL>::LINES - 1) / CS<N, ML, NL>::LINES, ny);                                     \
+        float ms = time_it([&] { xf_kernel<N, ML, FL, NL><<<grid, CS<N, ML, NL>::THREADS>>>(ny, nz, nzh, nzp, in, out, ss, scale, W, -12345, REMAP); }); \
+        printf("%-58s lines %2d x%d  %.4f ms  (%.2f TB/s of 1.6 GB)\n", label, ML, NL, ms, gb / ms);                 \
     }
+#define RUN(ML, FL, label) RUNX(ML, FL, 1, 1, label)
+#define RUN2(ML, FL, label) RUNX(ML, FL, 2, 1, label)
+    // two kz columns per thread (16-byte accesses) against the one-column form, part by part
+    RUN(8, 0, "library kernel");
+    RUN2(16, 0, "library kernel");
+    RUNX(16, 0, 2, 0, "library kernel, launch order (no XCD remap)");
+    RUN2(8, 0, "library kernel");
+    RUNX(8, 0, 2, 0, "library kernel, launch order (no XCD remap)");
+    RUN2(16, F_NOFFT, "no FFTs (load, multiply, 2 stores)");
+    RUN2(8, F_NOFFT, "no FFTs (load, multiply, 2 stores)");
+    RUN2(16, F_NOLOAD | F_NOSTORE, "FFTs only (no global memory)");
+    RUN2(16, F_NOLOAD | F_NOSTORE | F_NOSYNC, "FFTs only, no barriers");
+    RUN2(16, F_NOSTORE, "no stores");
+    RUN2(16, F_NOLOAD, "no loads");
+    RUN2(8, F_NOLOAD | F_NOSTORE, "FFTs only (no global memory)");
+    RUN2(8, F_NOSTORE, "no stores");
+    RUN2(8, F_NOLOAD, "no loads");
+    if (getenv("XPASS_PAIRS_ONLY")) return 0;
     RUN(8, 0, "library kernel");
     RUN(16, 0, "library kernel");
     RUN(8, F_PRETW, "twiddles preloaded into registers");
