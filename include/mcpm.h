@@ -733,6 +733,23 @@ int mcpm_spectrum_bins_c64(void *stream, int nx, int ny, int nz, const float *sp
                            const double *edges, int n_edges, const double *los, const int *ells, int n_ells, void *work,
                            int64_t work_bytes, double *out);
 
+/* Binned real-space sums (montecosmo/metrics.py:bin_and_aggregate, binned.hip): one pass over flat device arrays of n >= 1 cells.
+   values[n] (float, or double when values_f64) are the binning values, shared by the batch; a cell falls in bin i (0-based) when
+   edges[i] <= value < edges[i+1], compared in double (np.digitize, right=False, bins 1..n_edges-1); values outside the edges and
+   NaN are dropped.  edges[n_edges]: HOST float64, finite and non-decreasing (MCPM_E_ARG otherwise; a repeated edge is an empty
+   bin), 2 <= n_edges <= MCPM_BINNED_MAX_EDGES.  Targets are float [batch][n], rows `stride0` / `stride1` elements apart (0 = the
+   same array for every row): t1 NULL: the target of row b is t0[b][i] (`scale` unused); else it is (t0[b][i] - t1[b][i])^2 * scale,
+   formed in double.  mask (bytes [n], or NULL): cells with mask 0 are skipped.  `out` (device, OVERWRITTEN): float64
+   [2 + batch][n_edges-1]: row 0 = the count, 1 = the sum of values, 2 + b = the sum of the target of batch row b.  Bitwise
+   reproducible; a batch row equals the single call, and unaligned pointers (a view x[1:]) give the same bits as aligned ones.
+   `work` (device, work_bytes >= mcpm_binned_workspace(...)) is the caller's; the call synchronises `stream` once after uploading
+   the edges.  No plan: `stream` is a hipStream_t. */
+#define MCPM_BINNED_MAX_EDGES 4096
+int mcpm_binned_workspace(int64_t n, int n_edges, int batch, int64_t *bytes);
+int mcpm_binned_sums_f32(void *stream, int64_t n, const void *values, int values_f64, const float *t0, int64_t stride0,
+                         const float *t1, int64_t stride1, double scale, const unsigned char *mask, int batch, const double *edges,
+                         int n_edges, void *work, int64_t work_bytes, double *out);
+
 /* ---- catalogue -> register (montecosmo/model.py:1287-1362 register_catalog, bricks.py:882-1103; catalog.hip) -----------------
    Per-object passes over a galaxy catalogue (ra, dec in degrees, z: DEVICE float64 arrays of length n) or a simulation box, and
    the reductions around them.  The plan lends its stream and reduction scratch (and, for the footprint, its mesh shape).  atab

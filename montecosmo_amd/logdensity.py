@@ -49,8 +49,8 @@ from types import SimpleNamespace
 import numpy as np
 import torch
 
-from . import nbody, bricks, _lib
-from .utils import r2chshape, chreshape, chreshape_vjp, rg2cgh, rg2cgh_vjp, cgh2rg
+from . import nbody, bricks, metrics, _lib
+from .utils import r2chshape, chreshape, chreshape_vjp, rg2cgh, rg2cgh_vjp, cgh2rg, mesh2masked, masked2mesh
 
 LOG2PI = math.log(2 * math.pi)
 
@@ -346,6 +346,75 @@ class FieldLevelLogDensity:
 
     def _ngb_elem(self, i):
         return {k: float(v[i]) for k, v in self.ngb_lat.items()}
+
+    # ---- real-space diagnostics of meshes against a truth (model.py:1259-1263, :1381-1405) ------------------------------
+    def mesh2masked(self, mesh):
+        """The observed cells of a final mesh (or a batch of them) as a vector; the mesh itself without a mask."""
+        return mesh2masked(mesh, self.mask)
+
+    def masked2mesh(self, masked):
+        """Inverse of mesh2masked, zeros in the unobserved cells."""
+        return masked2mesh(masked, self.mask)
+
+    @property
+    def rmasked(self):
+        """Distances of the observed cells (of every cell without a mask): float64 on the device, built on first use and kept."""
+        if getattr(self, "_rmasked", None) is None:
+            self._rmesh = torch.from_numpy(self.fwd.radius_mesh(self.final_shape)).to(self.count_obs.device)
+            self._rmasked = self._rmesh.reshape(-1) if self.mask is None else self._rmesh[self.mask]
+        return self._rmasked
+
+    def _radial(self, fn, meshes, cell_length, redges, aggr_fn, from_masked):
+        """fn = metrics.mse_radius or metrics.distr_radial on the model's radii; the last of `meshes` may carry a batch axis.  On a cut sky the
+        edges come from the observed radii, and both routes run the same pass over full meshes with the mask (so they agree to the bit):
+        full meshes as they are, masked vectors scattered into zero-filled meshes first, a bounded number of batch rows at a time."""
+        cell_length = self.fwd.cell_length if cell_length is None else cell_length
+        rmasked = self.rmasked
+        if self.mask is None:      # meshes or flat vectors of every cell
+            as_mesh = tuple(np.shape(meshes[-1])[-3:]) == self.final_shape
+            return fn(*meshes, self._rmesh if as_mesh else rmasked, cell_length, redges=redges, aggr_fn=aggr_fn)
+        if aggr_fn is not None:      # the host path takes the masked vectors
+            if not from_masked:
+                meshes = [self.mesh2masked(torch.as_tensor(m)) for m in meshes]
+            return fn(*meshes, rmasked, cell_length, redges=redges, aggr_fn=aggr_fn)
+        edges = metrics._vedges(rmasked, redges, 1, cell_length)[0]
+        if not from_masked:
+            return fn(*meshes, self._rmesh, cell_length, redges=edges, mask=self.mask)
+        meshes = [torch.as_tensor(m) for m in meshes]
+        for m in meshes:
+            if m.ndim not in (1, 2) or m.shape[-1] != rmasked.numel():
+                raise ValueError(f"from_masked=True takes vectors of the {rmasked.numel()} observed cells (one optional batch axis), got shape {tuple(m.shape)}")
+        if getattr(self, "_mask_index", None) is None:      # masked2mesh with the mask's cell numbers found once, not per call
+            self._mask_index = self.mask.reshape(-1).nonzero().squeeze(1)
+
+        def full(m):
+            out = torch.zeros(tuple(m.shape[:-1]) + (self._rmesh.numel(),), dtype=torch.float32, device=self.mask.device)
+            out.index_copy_(-1, self._mask_index, m.to(device=self.mask.device, dtype=torch.float32))
+            return out.reshape(tuple(m.shape[:-1]) + self.final_shape)
+        lead, last = [full(m) for m in meshes[:-1]], meshes[-1]
+        if last.ndim == 1:
+            return fn(*lead, full(last), self._rmesh, cell_length, redges=edges, mask=self.mask)
+        chunk = int(max(1, metrics.CHUNK_BYTES // (8 * self._rmesh.numel())))
+        outs = []
+        for lo in range(0, last.shape[0], chunk):
+            count, mean, aggr = fn(*lead, full(last[lo:lo + chunk]), self._rmesh, cell_length, redges=edges, mask=self.mask)
+            outs.append(aggr)      # count and mean are the same bits from every chunk
+        return count, mean, np.concatenate(outs)
+
+    def mse_radius(self, mesh0, mesh1, cell_length=None, redges: int | float | list = None, aggr_fn=None, from_masked=True):
+        """Mean squared error between mesh0 and mesh1 (which may be batched) over the observed cells, binned by distance: (rcount, rmean,
+        mse).  from_masked: the inputs are vectors of the observed cells (mesh2masked); else full final meshes, binned in place."""
+        return self._radial(metrics.mse_radius, (mesh0, mesh1), cell_length, redges, aggr_fn, from_masked)
+
+    def distr_radial(self, mesh, cell_length=None, redges: int | float | list = None, aggr_fn=None, from_masked=True):
+        """Radial distribution of a mesh (which may be batched) over the observed cells: (rcount, rmean, mean per shell / cell_length^3)."""
+        return self._radial(metrics.distr_radial, (mesh,), cell_length, redges, aggr_fn, from_masked)
+
+    def mse_value(self, mesh0, mesh1, cell_length=None, vedges: int | float | list = 50, min_count=None, aggr_fn=None):
+        return self.fwd.mse_value(mesh0, mesh1, cell_length=cell_length, vedges=vedges, min_count=min_count, aggr_fn=aggr_fn)
+
+    def mse_wave(self, mesh0, mesh1, kedges: int | float | list = None, include_corners=True):
+        return self.fwd.mse_wave(mesh0, mesh1, kedges=kedges, include_corners=include_corners)
 
     def fiducial(self):
         """Fiducial base values: loc_fid of the latents, else the fixed value (model.py:1214-1223)."""

@@ -9,6 +9,16 @@ the reference's `_waves` / `rfftk` / `rectangular_hat` do; `mcpm_spectrum_bins_c
 in one pass over the spectra (both autos and the cross spectrum of `powtranscoh` together), bitwise reproducibly.  A leading
 batch axis on `mesh1` (and on `mesh0` for `spectrum`) replaces the reference's `nvmap` over chains; batches go to the
 device in chunks of bounded memory.  Outputs are float64 numpy arrays; empty bins are NaN, as 0/0 is in the reference.
+
+The real-space half of the module (montecosmo/metrics.py:214-313, :545-553) bins cells by a per-cell value instead of |k|:
+
+    rcount, rmean, mse = metrics.mse_radius(truth, posterior_meshes, rmesh, cell_length)      # by distance, default shells
+    vcount, vmean, mse = metrics.mse_value(truth, posterior_meshes, cell_length, vedges=50)  # by density, 50 quantile bins
+
+`mcpm_binned_sums_f32` (csrc/binned.hip) makes the count, the sum of the binning values and the sum of the target of every batch row
+in one pass, bitwise reproducibly; the squared error is formed inside the pass.  Every comparison with an edge is made in float64
+(the reference compares float32 jax arrays with edges found from them), targets are read as float32, and a leading batch axis on the
+target (`mesh1`, `mesh`, `targets`) gives `taggr` a leading axis.  `aggr_fn` other than the mean is a slow host path.
 """
 from __future__ import annotations
 
@@ -23,7 +33,8 @@ from .utils import safe_div, ch2rshape
 MAX_EDGES = 4096               # MCPM_SPECTRUM_MAX_EDGES
 CHUNK_BYTES = 1 << 32          # device memory a batch chunk may take (spectra, real staging, workspace)
 
-__all__ = ["spectrum", "transfer", "coherence", "powtranscoh", "MAX_EDGES"]
+__all__ = ["spectrum", "transfer", "coherence", "powtranscoh", "bin_and_aggregate", "mse_radius", "mse_value", "mse_wave", "distr_radial",
+           "MAX_EDGES"]
 
 
 # ------------------------------------------------------------------------------------------------
@@ -230,3 +241,214 @@ def powtranscoh(mesh0, mesh1, box_size, kedges: int | float | list = None, inclu
     """(k, pow1, (pow1 / pow0)^.5, pow01 / (pow0 pow1)^.5) from one pass over both meshes."""
     ks, pow0, pow1, pow01 = _pow3(mesh0, mesh1, box_size, kedges, include_corners)
     return ks, pow1, (pow1 / pow0) ** .5, pow01 / (pow0 * pow1) ** .5
+
+
+# ------------------------------------------------------------------------------------------------
+# real-space bins (montecosmo/metrics.py:214-313, :545-553): host side
+def _check_edges(edges):
+    edges = np.asarray(edges, dtype=np.float64).reshape(-1)
+    if len(edges) > MAX_EDGES:
+        raise ValueError(f"at most {MAX_EDGES} bin edges, got {len(edges)}")
+    if not np.all(np.isfinite(edges)) or not np.all(np.diff(edges) >= 0):
+        raise ValueError("bin edges must be finite and non-decreasing")
+    return edges
+
+
+def _quantiles(values, q):
+    """np.quantile(values.astype(float64), q) (method 'linear'), bit for bit, for a tensor of any size on any device: one sort where
+    the values are, a gather of the two order statistics per level, numpy's interpolation on the host in float64."""
+    q = np.asarray(q, dtype=np.float64).reshape(-1)
+    if not np.all((q >= 0) & (q <= 1)):      # (a NaN level fails too)
+        raise ValueError("quantile levels must be in [0, 1]")
+    s = torch.sort(torch.as_tensor(values).reshape(-1)).values
+    n = s.numel()
+    pos = (n - 1) * q
+    lo = np.floor(pos)
+    t = pos - lo
+    lo = lo.astype(np.int64)
+    idx = torch.from_numpy(np.concatenate([lo, np.minimum(lo + 1, n - 1)])).to(s.device)
+    ab = s[idx].to(torch.float64).cpu().numpy()
+    a, b = ab[:len(q)], ab[len(q):]
+    d = b - a
+    return np.where(t < .5, a + d * t, b - d * (1 - t))
+
+
+def _vedges(values, vedges, min_count=1, cell_length=None):
+    """-> (edges, min_count) of bin_and_aggregate (montecosmo/metrics.py:223-235): a list is used as given, an int is a number of edges,
+    a float a bin width, None the width sqrt(3) cell_length that keeps radial shells connected; the int and float cases put the edges
+    at the centres of equal cells of [vmin, vmax], the range of `values` (a tensor, where it lives), or of [0, 1] when min_count is
+    None.  With min_count None the edges are quantile levels: they become the quantiles of `values`, and min_count becomes 1.
+    Unlike _kedges, repeated edges pass (quantiles of tied data repeat); decreasing or non-finite ones raise ValueError."""
+    if vedges is None:
+        if cell_length is None:
+            raise ValueError("edges None need a cell_length")
+        vedges = 3 ** .5 * float(cell_length)
+    if isinstance(vedges, (bool, np.bool_)):
+        raise ValueError("edges must be a list, an int or a float")
+    if isinstance(vedges, (int, np.integer, float, np.floating)):
+        is_int = isinstance(vedges, (int, np.integer))
+        if is_int and not 1 <= vedges <= MAX_EDGES:      # known before the values are looked at
+            raise ValueError(f"1 .. {MAX_EDGES} bin edges, got {vedges}")
+        if min_count is None:
+            vmin, vmax = 0., 1.
+        else:
+            vmin, vmax = float(values.min()), float(values.max())
+        n = int(vedges) if is_int else max(int((vmax - vmin) / float(vedges)), 1)
+        if n > MAX_EDGES:
+            raise ValueError(f"at most {MAX_EDGES} bin edges, got {n}")
+        dv = (vmax - vmin) / n
+        vedges = np.linspace(vmin, vmax, n, endpoint=False)
+        vedges += dv / 2
+    vedges = np.asarray(vedges, dtype=np.float64).reshape(-1)
+    if min_count is None:
+        if len(vedges) > MAX_EDGES:
+            raise ValueError(f"at most {MAX_EDGES} bin edges, got {len(vedges)}")
+        vedges = _quantiles(values, vedges)
+        min_count = 1
+    return _check_edges(vedges), min_count
+
+
+def _batch_of(target, values, what):
+    """None when `target` has the cells of `values`, B when it carries one more leading axis of length B; ValueError otherwise."""
+    if tuple(target.shape) == tuple(values.shape):
+        return None
+    if target.ndim == values.ndim + 1 and tuple(target.shape[1:]) == tuple(values.shape):
+        return int(target.shape[0])
+    if target.numel() == values.numel():      # the reference flattens both
+        return None
+    if values.ndim == target.ndim + 1 and tuple(values.shape[1:]) == tuple(target.shape):
+        raise ValueError(f"the binning values may not be batched (shape {tuple(values.shape)} against {what} of shape {tuple(target.shape)}): "
+                         "the count filter would make the result ragged")
+    raise ValueError(f"{what} of shape {tuple(target.shape)} does not match binning values of shape {tuple(values.shape)}")
+
+
+def _finish_bins(vcount, vsum, tsum, min_count, batched):
+    keep = vcount >= min_count
+    vcount = vcount[keep]
+    with np.errstate(divide="ignore", invalid="ignore"):
+        vmean = vsum[keep] / vcount
+        taggr = tsum[:, keep] / vcount
+    return vcount, vmean, (taggr if batched else taggr[0])
+
+
+def _binned_host(values, t0, t1, scale, vedges, min_count, aggr_fn, mask, cell_length):
+    """The slow path of an `aggr_fn` other than the mean (a median, say): everything on the host in float64, one bin at a time."""
+    to64 = lambda x: torch.as_tensor(x).detach().cpu().numpy().astype(np.float64).reshape(-1)
+    v, tg = to64(values), to64(t0)
+    if t1 is not None:
+        tg = (tg - to64(t1)) ** 2 * scale
+    if mask is not None:
+        m = torch.as_tensor(mask).cpu().numpy().astype(bool).reshape(-1)
+        v, tg = v[m], tg[m]
+    edges, min_count = _vedges(torch.from_numpy(v), vedges, min_count, cell_length)
+    n_bins = len(edges) + 1
+    dig = np.digitize(v, edges)
+    vcount = np.bincount(dig, minlength=n_bins)[1:-1].astype(np.float64)
+    vsum = np.bincount(dig, weights=v, minlength=n_bins)[1:-1]
+    keep = vcount >= min_count
+    taggr = np.array([aggr_fn(tg[dig == i]) for i in range(1, n_bins - 1)], dtype=np.float64).reshape(n_bins - 2)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        return vcount[keep], vsum[keep] / vcount[keep], taggr[keep]
+
+
+# ------------------------------------------------------------------------------------------------
+# real-space bins: device side
+def _binned(values, t0, t1, scale, vedges, min_count, aggr_fn=None, mask=None, cell_length=None):
+    """(vcount, vmean, taggr): cells binned by `values`; the target is t0 (t1 None) or (t0 - t1)^2 scale.  The batched input, if any,
+    is t1 in the squared-error mode and t0 in the plain mode.  Every argument check comes before the first device call."""
+    v, a0 = torch.as_tensor(values), torch.as_tensor(t0)
+    a1 = None if t1 is None else torch.as_tensor(t1)
+    if a1 is None:
+        batch = _batch_of(a0, v, "targets")
+    else:
+        if a0.numel() != v.numel():
+            _batch_of(a0, v, "mesh0")      # raises with the reason
+            raise ValueError(f"mesh0 of shape {tuple(a0.shape)} may not be batched against binning values of shape {tuple(v.shape)}")
+        batch = _batch_of(a1, a0, "mesh1")
+    n = v.numel()
+    if n < 1:
+        raise ValueError("no cells to bin")
+    if mask is not None:
+        mask = torch.as_tensor(mask)
+        if mask.numel() != n:
+            raise ValueError(f"mask of shape {tuple(mask.shape)} does not match binning values of shape {tuple(v.shape)}")
+    if aggr_fn is not None:
+        if batch is not None:
+            raise ValueError("aggr_fn is applied on the host to one target at a time: pass unbatched targets")
+        return _binned_host(v, a0, a1, scale, vedges, min_count, aggr_fn, mask, cell_length)
+    if not isinstance(vedges, (type(None), int, float, np.integer, np.floating)) and min_count is not None:
+        vedges = _check_edges(vedges)
+    elif isinstance(vedges, (int, np.integer)) and not isinstance(vedges, (bool, np.bool_)) and not 1 <= vedges <= MAX_EDGES:
+        raise ValueError(f"1 .. {MAX_EDGES} bin edges, got {vedges}")
+
+    dev = nbody._device()
+    vd = v.detach().to(device=dev, dtype=v.dtype if v.dtype in (torch.float32, torch.float64) else torch.float64).reshape(-1).contiguous()
+    md = None if mask is None else mask.to(device=dev).reshape(-1).contiguous()
+    if md is not None and md.dtype not in (torch.bool, torch.uint8):
+        md = md != 0
+    edges, min_count = _vedges(vd if md is None else vd[md.bool()], vedges, min_count, cell_length)
+    n_bins = len(edges) - 1
+    B = 1 if batch is None else batch
+    if n_bins < 1:      # fewer than two edges: no bin, as in the reference
+        return np.zeros(0), np.zeros(0), np.zeros((B, 0) if batch is not None else 0)
+
+    f32 = lambda x, rows: x.detach().to(device=dev, dtype=torch.float32).reshape(rows, n).contiguous()
+    bat = a0 if a1 is None else a1      # the input that may carry the batch axis
+    fixed0 = f32(a0, 1) if (a1 is not None or batch is None) else None
+    ws1 = C.c_int64()
+    _lib.call("mcpm_binned_workspace", n, len(edges), 1, C.byref(ws1))
+    chunk = int(max(1, min(B, CHUNK_BYTES // (ws1.value + 4 * n))))
+    stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+    out_t = np.zeros((B, n_bins), dtype=np.float64)
+    for lo in range(0, B, chunk):
+        hi = min(lo + chunk, B)
+        rows = f32(bat[lo:hi] if batch is not None else bat, hi - lo) if (a1 is not None or batch is not None) else None
+        d0, s0 = (fixed0, 0) if fixed0 is not None else (rows, n)
+        d1, s1 = (rows, n if batch is not None else 0) if a1 is not None else (None, 0)
+        ws = C.c_int64()
+        _lib.call("mcpm_binned_workspace", n, len(edges), hi - lo, C.byref(ws))
+        work = torch.empty(ws.value, dtype=torch.uint8, device=dev)
+        res = torch.empty((2 + hi - lo, n_bins), dtype=torch.float64, device=dev)
+        _lib.call("mcpm_binned_sums_f32", stream, n, vd, int(vd.dtype == torch.float64), d0, s0, d1, s1, float(scale), md, hi - lo, edges,
+                  len(edges), work, ws.value, res)
+        res = res.cpu().numpy()
+        vcount, vsum = res[0], res[1]      # the same bits from every chunk
+        out_t[lo:hi] = res[2:]
+    return _finish_bins(vcount, vsum, out_t, min_count, batch is not None)
+
+
+# ------------------------------------------------------------------------------------------------
+# real-space bins: public interface.  `mask` (not in the reference; cells where it is zero are skipped) lets full meshes of a cut sky be
+# binned in place, without the compaction mesh[..., mask] the reference makes first.
+def bin_and_aggregate(targets, values, vedges: int | float | list, min_count=1, aggr_fn=None, mask=None):
+    """Bin the cells by `values` and aggregate `targets` per bin: (vcount, vmean, taggr), bins with vcount < min_count removed.
+    min_count None: `vedges` are quantile levels (an int or a float spaces them over [0, 1]).  aggr_fn None: the mean, on the device;
+    any other aggr_fn (np.median, ...) runs on the host, bin by bin, on the float64 targets -- the slow path, unbatched only."""
+    return _binned(values, targets, None, 1., vedges, min_count, aggr_fn, mask)
+
+
+def mse_radius(mesh0, mesh1, rmesh, cell_length, redges: int | float | list = None, aggr_fn=None, mask=None):
+    """Mean squared error between mesh0 and mesh1 binned by radius, in (Mpc/h)^3: (rcount, rmean, mse).  redges None: shells
+    sqrt(3) cell_length wide, the narrowest that stay connected."""
+    return _binned(rmesh, mesh0, mesh1, float(cell_length) ** 3, redges, 1, aggr_fn, mask, cell_length)
+
+
+def mse_value(mesh0, mesh1, cell_length, vedges: int | float | list, min_count=None, aggr_fn=None):
+    """Mean squared error between mesh0 and mesh1 binned by the value of mesh0, in (Mpc/h)^3: (vcount, vmean, mse)."""
+    return _binned(mesh0, mesh0, mesh1, float(cell_length) ** 3, vedges, min_count, aggr_fn)
+
+
+def mse_wave(mesh0, mesh1, box_size, kedges: int | float | list = None, include_corners=True):
+    """Mean squared error between mesh0 and mesh1 binned by wave number, in (Mpc/h)^3: (kcount, kmean, pow), the spectrum of the difference."""
+    t0, t1 = torch.as_tensor(mesh0), torch.as_tensor(mesh1)
+    if t1.is_cuda and not t0.is_cuda:
+        t0 = t0.to(t1.device)
+    elif t0.is_cuda and not t1.is_cuda:
+        t1 = t1.to(t0.device)
+    return _spectrum(t1 - t0, box_size=box_size, kedges=kedges, include_corners=include_corners)
+
+
+def distr_radial(mesh, rmesh, cell_length, redges: int | float | list = None, aggr_fn=None, mask=None):
+    """Radial distribution of the mesh, in (h/Mpc)^3: (rcount, rmean, mean of the mesh per shell / cell_length^3)."""
+    rcount, rmean, maggr = _binned(rmesh, mesh, None, 1., redges, 1, aggr_fn, mask, cell_length)
+    return rcount, rmean, maggr / float(cell_length) ** 3

@@ -97,6 +97,28 @@ class FieldLevelForward:
         """(k, pow1, (pow1 / pow0)^.5, pow01 / (pow0 pow1)^.5) with the model's box_size; a batched mesh1 gives batched outputs."""
         return metrics.powtranscoh(mesh0, mesh1, box_size=self.box_size, kedges=kedges, include_corners=include_corners)
 
+    def mse_value(self, mesh0, mesh1, cell_length=None, vedges: int | float | list = 50, min_count=None, aggr_fn=None):
+        """metrics.mse_value with the model's cell_length (model.py:1390-1394): by default 50 quantile bins of mesh0."""
+        return metrics.mse_value(mesh0, mesh1, self.cell_length if cell_length is None else cell_length, vedges=vedges, min_count=min_count,
+                                 aggr_fn=aggr_fn)
+
+    def mse_wave(self, mesh0, mesh1, kedges: int | float | list = None, include_corners=True):
+        """metrics.mse_wave with the model's box_size (model.py:1396-1397)."""
+        return metrics.mse_wave(mesh0, mesh1, self.box_size, kedges=kedges, include_corners=include_corners)
+
+    # ---- data (model.py:1249-1257) ----------------------------------------------------------------------------
+    def pos_mesh(self, shape=None):
+        """Physical positions of the cells of a mesh of `shape` (default final_shape): host float64, shape + (3,)."""
+        shape = self.final_shape if shape is None else tuple(int(s) for s in shape)
+        p = bricks.cell2phys_pos(bricks.regular_pos(shape), self.box_center, self.box_rotvec, self.box_size, shape)
+        return np.asarray(p, dtype=np.float64).reshape(shape + (3,))
+
+    def radius_mesh(self, shape=None):
+        """Physical distance of the cells of a mesh of `shape` (default final_shape): `lattice_radius` as a mesh, host float64; |x| on the
+        curved sky, |x . los| on the flat one."""
+        shape = self.final_shape if shape is None else tuple(int(s) for s in shape)
+        return np.asarray(self.lattice_radius(shape), dtype=np.float64).reshape(shape)
+
     # ---- pieces ------------------------------------------------------------------------------------------
     def _kphys(self, shape):
         return [float(s) / float(b) for s, b in zip(shape, self.box_size)]

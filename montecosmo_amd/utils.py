@@ -32,6 +32,35 @@ def scale_shape(shape, scale=1.):
     return tuple(int(2 * np.rint(s * scale / 2)) for s in shape)
 
 
+def mesh2masked(mesh, mask=None):
+    """mesh[..., mask]: the observed cells of a mesh (or of a batch of meshes) as a vector (utils.py:1171-1175); numpy or torch, the
+    mask goes where the mesh is.  mask None: the mesh itself."""
+    if mask is None:
+        return mesh
+    if torch.is_tensor(mesh):
+        return mesh[..., torch.as_tensor(mask, device=mesh.device).bool()]
+    return np.asarray(mesh)[..., _host_mask(mask)]
+
+
+def masked2mesh(masked, mask=None):
+    """Inverse of mesh2masked with zeros in the unobserved cells (utils.py:1178-1183); keeps the dtype of `masked`."""
+    if mask is None:
+        return masked
+    if torch.is_tensor(masked):
+        m = torch.as_tensor(mask, device=masked.device).bool()
+        out = torch.zeros(tuple(masked.shape[:-1]) + tuple(m.shape), dtype=masked.dtype, device=masked.device)
+        out[..., m] = masked
+        return out
+    masked, m = np.asarray(masked), _host_mask(mask)
+    out = np.zeros(masked.shape[:-1] + m.shape, dtype=masked.dtype)
+    out[..., m] = masked
+    return out
+
+
+def _host_mask(mask):
+    return (mask.cpu().numpy() if torch.is_tensor(mask) else np.asarray(mask)).astype(bool)
+
+
 def radecrad2cart(ra, dec, radius):
     """ra, dec (degrees) and radius -> cartesian coordinates (..., 3) (utils.py:1186-1196); host float64."""
     ra, dec = np.deg2rad(np.asarray(ra, dtype=np.float64)), np.deg2rad(np.asarray(dec, dtype=np.float64))
