@@ -391,13 +391,10 @@ def set_radial_count(mesh, rmesh, redges, rcounts):
     return out
 
 
-def log_density(cfg, latents, fixed, sample, count_obs, make_cosmo, aux=None):
-    """log p(sample params, count_obs) of the field-level model for Normal or truncated-Normal latents (model.py:1105-1125 prior in
-    sample space; bricks.py:255-287 affine reparametrisation; model.py:1127-1148 'fourier' / 'real' / 'kaiser'
-    preconditioning; model.py:686-838 evolve; model.py:840-908 'quad_gauss' likelihood with no mask, unit selection, one radial
-    bin and phi = 0).  `latents`: name -> dict(loc, scale, loc_fid, scale_fid); `fixed`: name -> value of the base
-    parameters that are not sampled; `sample`: name_ -> value (scalars) and 'white_mesh_' (real, init_shape).  `aux`: an optional
-    dict that receives the intermediates a test may want ('gxy': evolve's output, 'white': its input, 'count': the mean counts)."""
+def prior_and_white(cfg, latents, fixed, sample, make_cosmo):
+    """The part of `log_density` before evolve: the priors of the scalar latents in sample space, the prior of 'white_mesh_' under the
+    preconditioning of cfg['precond'], and the transport of both to base space.  Returns (lp, base, white): the summed log prior, the base
+    parameters (fixed ones included) and the complex half-spectrum that evolve takes."""
     lp = 0.0
     base = dict(fixed)
     scalar_items = []
@@ -438,13 +435,12 @@ def log_density(cfg, latents, fixed, sample, count_obs, make_cosmo, aux=None):
     scale, transfer = precond_scale_and_transfer(cfg, fiduc, cosmo_fid)
     lp += np.sum(-0.5 * np.log(2 * np.pi) - np.log(scale) - 0.5 * (w / scale) ** 2)     # model.py:666-672
     white = (o.rg2cgh(w) if cfg["precond"] != "real" else o._rfftn(w)) * transfer
-    cosmo = make_cosmo(base)
-    bias = {k: base[k] for k in BIAS_KEYS}
-    gxy, _ = evolve(cfg, cosmo, bias, white)
-    if aux is not None:
-        aux.update(gxy=gxy, white=white, base=base)
-    # likelihood (model.py:852-866, :893-908): selection mesh (paint_shape or scalar 1), mask over the final cells,
-    # radial shells with their own mean densities; count_obs is the full final mesh (only its unmasked cells are used)
+    return lp, base, white
+
+
+def mean_counts(cfg, base, gxy):
+    """The mean counts the likelihood is evaluated on (model.py:852-866): selection mesh (paint_shape or scalar 1), mask over the final
+    cells, radial shells with their own mean densities.  Returns (count mesh, selec: a float without a selection mesh, else a mesh; mask)."""
     final = tuple(cfg["final_shape"])
     down = lambda m: o._irfftn(o.chreshape(o._rfftn(m), o.r2chshape(final)), s=final, axes=(0, 1, 2))
     sel = cfg.get("selec_mesh")
@@ -456,6 +452,25 @@ def log_density(cfg, latents, fixed, sample, count_obs, make_cosmo, aux=None):
     rmesh = radius_mesh(cfg, final)
     cm = set_radial_count(down(gxy if sel is None else gxy * sel), rmesh, redges, rcounts)
     selec = np.mean(rcounts) if sel is None else np.abs(set_radial_count(down(sel), rmesh, redges, rcounts))
+    return cm, selec, mask
+
+
+def log_density(cfg, latents, fixed, sample, count_obs, make_cosmo, aux=None):
+    """log p(sample params, count_obs) of the field-level model for Normal or truncated-Normal latents (model.py:1105-1125 prior in
+    sample space; bricks.py:255-287 affine reparametrisation; model.py:1127-1148 'fourier' / 'real' / 'kaiser'
+    preconditioning; model.py:686-838 evolve; model.py:840-908 'quad_gauss' likelihood with no mask, unit selection, one radial
+    bin and phi = 0).  `latents`: name -> dict(loc, scale, loc_fid, scale_fid); `fixed`: name -> value of the base
+    parameters that are not sampled; `sample`: name_ -> value (scalars) and 'white_mesh_' (real, init_shape).  `aux`: an optional
+    dict that receives the intermediates a test may want ('gxy': evolve's output, 'white': its input, 'count': the mean counts)."""
+    lp, base, white = prior_and_white(cfg, latents, fixed, sample, make_cosmo)
+    cosmo = make_cosmo(base)
+    bias = {k: base[k] for k in BIAS_KEYS}
+    gxy, _ = evolve(cfg, cosmo, bias, white)
+    if aux is not None:
+        aux.update(gxy=gxy, white=white, base=base)
+    # likelihood (model.py:852-866, :893-908); count_obs is the full final mesh (only its unmasked cells are used)
+    final = tuple(cfg["final_shape"])
+    cm, selec, mask = mean_counts(cfg, base, gxy)
     if aux is not None:
         aux.update(count=cm)
     delta = cm / selec - 1

@@ -73,8 +73,15 @@ def sigma8_of(ks, pows, r=8.0):
 
 def lin_power_table(cosmo, n_interp=256):
     """(ks, pows normalised to sigma8 = 1) on logspace(-4, 1, n_interp) h/Mpc (bricks.py:73)."""
+    key = ("power_oracle.lin_power_table", n_interp)      # kept with the cosmology's other tables (a function of Omega_m, Omega_b, h, n_s)
+    ws = getattr(cosmo, "_workspace", None)
+    if ws is not None and key in ws:
+        return ws[key]
     ks = np.logspace(-4, 1, n_interp)
     kf = np.logspace(-5, 2, 4097)
     pf = kf ** cosmo.n_s * eisenstein_hu(cosmo, kf) ** 2
     amp = 1.0 / sigma8_of(kf, pf) ** 2
-    return ks, amp * ks ** cosmo.n_s * eisenstein_hu(cosmo, ks) ** 2
+    out = ks, amp * ks ** cosmo.n_s * eisenstein_hu(cosmo, ks) ** 2
+    if ws is not None:
+        ws[key] = out
+    return out

@@ -82,6 +82,15 @@ def observe_pos_ap(cosmo, pos, vel, box_center, R, box_size, evol_shape, paint_s
     return bo.phys2cell_pos(p, box_center, R, box_size, paint_shape)
 
 
+def paint(cfg, pos_c, weights):
+    """model.py:802-809: the weighted nufft of positions in cells of init_shape, with the Jacobian prod(init_shape / ptcl_shape), on paint_shape."""
+    gxy = o.nufft(pos_c, cfg["init_shape"], tuple(cfg["paint_shape"]), weights=weights, paint_order=cfg["paint_order"],
+                  interlace_order=cfg["interlace_order"], paint_deconv=cfg["paint_deconv"])
+    gxy = gxy * np.divide(cfg["init_shape"], cfg["ptcl_shape"]).prod()
+    gxy = o.chreshape(gxy, o.r2chshape(cfg["paint_shape"]))
+    return o._irfftn(gxy, s=tuple(cfg["paint_shape"]), axes=(0, 1, 2))
+
+
 def evolve_ap(cfg, cosmo, bias, white_mesh, ap_auto_=None, ap=None, cosmo_fid=None):
     """model.py:686-838 with ap_auto set, composed from bias_oracle.evolve's intermediates: its `pos` are the redshift-space
     positions in cells of init_shape (model.py:786, :799), so they go back to physical units, through the Alcock-Paczynski step with the
@@ -96,15 +105,12 @@ def evolve_ap(cfg, cosmo, bias, white_mesh, ap_auto_=None, ap=None, cosmo_fid=No
     p = bo.cell2phys_pos(aux["pos"], ctr, R, box, cfg["init_shape"])
     p = apply_ap(p, los, cosmo, cfg["curved_sky"], ap_auto_, ap, cosmo_fid)
     pos_c = bo.phys2cell_pos(p, ctr, R, box, cfg["init_shape"])
-    gxy = o.nufft(pos_c, cfg["init_shape"], tuple(cfg["paint_shape"]), weights=aux["weights"], paint_order=cfg["paint_order"],
-                  interlace_order=cfg["interlace_order"], paint_deconv=cfg["paint_deconv"])
-    gxy = gxy * np.divide(cfg["init_shape"], cfg["ptcl_shape"]).prod()
-    gxy = o.chreshape(gxy, o.r2chshape(cfg["paint_shape"]))
-    return o._irfftn(gxy, s=tuple(cfg["paint_shape"]), axes=(0, 1, 2))
+    return paint(cfg, pos_c, aux["weights"])
 
 
 def log_density_ap(cfg, latents, fixed, sample, count_obs, make_cosmo, ap_auto_, cosmo_fid=None):
-    """bias_oracle.log_density (no selection, no mask, one radial bin) with the Alcock-Paczynski step inside evolve: the prior and
+    """Single-feature restatement; the composed form is tests/_model_f64.py (whose host test keeps this one as an independent witness).
+    bias_oracle.log_density (no selection, no mask, one radial bin) with the Alcock-Paczynski step inside evolve: the prior and
     white-field terms are its own, and its likelihood term (model.py:852-866, :893-908) is re-evaluated on `evolve_ap`'s mesh.
     alpha_iso / alpha_ap: latents (truncated normal, model.py:189-204) or fixed; a missing one is 1."""
     aux = {}

@@ -142,6 +142,14 @@ def evolve(cfg, cosmo, bias, white_mesh, png=None, png_type=None):
                           paint_order=cfg["paint_order"], lpt_order=cfg["lpt_order"])
         pos, vel = p[-1], v[-1]
     pos_c = bo.observe_pos(cosmo, pos, vel, ctr, R, box, cfg["evol_shape"], cfg["init_shape"], cfg["a_obs"], cfg["curved_sky"], dvel)
+    return painted_bias(cfg, pos_c, phi_pos, bias, png)
+
+
+def painted_bias(cfg, pos_c, phi_pos, bias, png=None):
+    """model.py:815-831: the unweighted and (phi_pos not None) the phi-weighted paint of positions in cells of init_shape, then
+    `eulerian_bias` with the coefficients of `l2e`.  `png`: the products of fNL_bias (None without PNG)."""
+    from oracle import pm_oracle as o
+    box = cfg["box_size"]
     jac = np.divide(cfg["init_shape"], cfg["ptcl_shape"]).prod()
     kshape = o.r2chshape(cfg["paint_shape"])
     spec = lambda wts: o.chreshape(o.nufft(pos_c, cfg["init_shape"], tuple(cfg["paint_shape"]), weights=wts, paint_order=cfg["paint_order"],

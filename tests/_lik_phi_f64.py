@@ -182,7 +182,9 @@ def evol_mesh(cfg, cosmo, white):
 
 
 def log_density(cfg, latents, fixed, sample, count_obs, make_cosmo, lik_type, png_type, temp=1., info=None):
-    """log p(sample, count_obs) with the likelihood `lik_type`, the term s_ep phi and the temperature `temp` of the likelihood: the
+    """Single-feature restatement; the composed form is tests/_model_f64.py.  The patch of `bo.evolve` below puts the PNG-enabled evolve
+    (and no other feature) under the oracle's log density; it stays as the composed oracle's independent witness.
+    log p(sample, count_obs) with the likelihood `lik_type`, the term s_ep phi and the temperature `temp` of the likelihood: the
     oracle's prior + (PNG-enabled, tests/_png_f64.py) evolve + 'quad_gauss' term, minus that term recomputed from the intermediates it
     leaves in `aux` (evaluated at value = loc, see tests/_lik_f64.py::_CountAsObs), plus the family's term on the same mean counts.
     `make_cosmo(base)` must put the PNG parameters of the base point on the cosmology as `png_params`.  `info` (a dict) receives
