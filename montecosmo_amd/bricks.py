@@ -14,7 +14,7 @@ import os
 import numpy as np
 import torch
 
-from . import _lib, nbody, power, utils
+from . import _lib, nbody, power, tables, utils
 
 
 class Cosmology:
@@ -113,7 +113,7 @@ def lagrangian_bias(cosmo, pos, a, box_size, lin_mesh, bias, png=None, png_type=
     phi, pctx = 0., None
     if png_type is not None:
         png = png or {}
-        tab, nt = png_table_dev(cosmo, kpow, dev)
+        tab, nt = _png_table(cosmo, kpow, dev)
         pl = torch.empty((2,) + tuple(shape), dtype=torch.float32, device=dev)      # phi, lap phi
         plan.call("mcpm_png_phi_f32", spec, kphys[0], kphys[1], kphys[2], tab, tab[nt:], nt, pl[0], pl[1])
         if ident:
@@ -212,21 +212,10 @@ def trans_phi2delta_table(cosmo, a=1., kpow=None):
     return ks, trans
 
 
-_PNG_TABLES = {}
-
-
-def png_table_dev(cosmo, kpow, device):
-    """(device float64 tensor [ks, trans], n): the table of `trans_phi2delta_table` at a = 1, built once per cosmology and power
-    source and kept on the device (a handful of entries: a sampler revisits the same cosmology for every call of one gradient)."""
-    key = (float(cosmo.Omega_c), float(cosmo.Omega_b), float(cosmo.h), float(cosmo.n_s), float(cosmo.Omega_k), float(cosmo.w0),
-           float(cosmo.wa), None if kpow is None else id(kpow[0]), str(device))
-    hit = _PNG_TABLES.get(key)
-    if hit is None or (kpow is not None and hit[2] is not kpow[0]):
-        if len(_PNG_TABLES) > 8:
-            _PNG_TABLES.clear()
-        ks, trans = trans_phi2delta_table(cosmo, kpow=kpow)
-        hit = _PNG_TABLES[key] = (torch.from_numpy(np.concatenate([ks, trans])).to(device), len(ks), None if kpow is None else kpow[0])
-    return hit[0], hit[1]
+def _png_table(cosmo, kpow, device):
+    """(device float64 tensor [ks | trans], n): the table of `trans_phi2delta_table` at a = 1, as the PNG kernels take it."""
+    tab = tables.on_device(cosmo, tables.TRANS, device, kpow=kpow)
+    return tab.t, tab.n["ks"]
 
 
 def add_png(cosmo, fNL, lin_mesh, box_size, kpow=None, return_ctx=False, phi=None):
@@ -240,7 +229,7 @@ def add_png(cosmo, fNL, lin_mesh, box_size, kpow=None, return_ctx=False, phi=Non
     shape = nbody.ch2rshape(spec.shape)
     plan, dev = nbody.get_plan(shape), spec.device
     kphys = [float(s) / float(b) for s, b in zip(shape, box_size)]
-    tab, nt = png_table_dev(cosmo, kpow, dev)
+    tab, nt = _png_table(cosmo, kpow, dev)
     phi_t = nbody._f32(phi, shape) if phi is not None else torch.empty(tuple(shape), dtype=torch.float32, device=dev)
     out = torch.empty(tuple(spec.shape), dtype=torch.complex64, device=dev)
     mean = torch.empty(1, dtype=torch.float64, device=dev)
@@ -502,30 +491,26 @@ def observe_pos(cosmo, pos, vel, box_center, box_rot, box_size, evol_shape, pain
     gf = 0.0 if lightcone else float(nbody.a2g(cosmo, a_obs) * nbody.a2f(cosmo, a_obs))
     geom = (C.c_float * 19)(*[float(x) for x in list(R.reshape(-1)) + list(box_size) + list(box_center) + list(paint_shape) + [gf]])
     flags = (1 if curved_sky else 0) | (2 if lightcone else 0)
-    tables, nchi, ngrow = None, 0, 0
-    if lightcone:
-        d, gtab = nbody._dist_cache(cosmo), nbody._growth_cache(cosmo)
-        nchi, ngrow = len(d["chi"]), len(gtab["a"])
-        tables = torch.from_numpy(np.concatenate([d["chi"][::-1], d["a"][::-1], gtab["a"], gtab["g"], gtab["f"]])).to(p.device)
+    lc = tables.on_device(cosmo, tables.LIGHTCONE, p.device) if lightcone else None
+    lctab, nchi, ngrow = (lc.t, lc.n["chi"], lc.n["a"]) if lightcone else (None, 0, 0)
     out = torch.empty((n, 3), dtype=torch.float32, device=p.device)
     apkw = dict(ap_mode=_lib.AP_NONE, alpha_iso=1.0, alpha_ap=1.0, ap_tables=None, nap=0, nfid=0)
     if ap_auto is None:
-        plan.call("mcpm_observe_pos_f32", p, v, dv, n, mode, geom, flags, tables, nchi, ngrow, out)
+        plan.call("mcpm_observe_pos_f32", p, v, dv, n, mode, geom, flags, lctab, nchi, ngrow, out)
     else:
         if ap_auto:
             if cosmo_fid is None:
                 raise ValueError("ap_auto=True needs the fiducial cosmology `cosmo_fid`")
-            d, df = nbody._dist_cache(cosmo), nbody._dist_cache(cosmo_fid)
-            apkw.update(ap_mode=_lib.AP_AUTO, nap=len(d["chi"]), nfid=len(df["a"]),
-                        ap_tables=torch.from_numpy(np.concatenate([d["chi"][::-1], d["a"][::-1], df["a"], df["chi"]])).to(p.device))
+            apt = tables.on_device(cosmo, tables.AP, p.device, fid=cosmo_fid)
+            apkw.update(ap_mode=_lib.AP_AUTO, nap=apt.n["chi"], nfid=apt.n["a_fid"], ap_tables=apt.t)
         else:
             ap = ap or {}
             apkw.update(ap_mode=_lib.AP_PARAM, alpha_iso=float(ap.get("alpha_iso", 1.0)), alpha_ap=float(ap.get("alpha_ap", 1.0)))
-        plan.call("mcpm_observe_pos_ap_f32", p, v, dv, n, mode, geom, flags, tables, nchi, ngrow, apkw["ap_mode"], apkw["alpha_iso"],
+        plan.call("mcpm_observe_pos_ap_f32", p, v, dv, n, mode, geom, flags, lctab, nchi, ngrow, apkw["ap_mode"], apkw["alpha_iso"],
                   apkw["alpha_ap"], apkw["ap_tables"], apkw["nap"], apkw["nfid"], out)
     res = nbody.LatticePos(out, paint_shape, pos.ptcl_shape) if isinstance(pos, nbody.LatticePos) else out
     if return_ctx:
-        return res, ObsCtx(plan=plan, p=p, v=v, dv=dv, n=n, mode=mode, geom=geom, flags=flags, tables=tables, nchi=nchi, ngrow=ngrow, **apkw)
+        return res, ObsCtx(plan=plan, p=p, v=v, dv=dv, n=n, mode=mode, geom=geom, flags=flags, tables=lctab, nchi=nchi, ngrow=ngrow, lc=lc, **apkw)
     return res
 
 
@@ -624,13 +609,9 @@ def kaiser_sky(cosmo, lin_mesh, box_size, box_center, box_rot, b1E, fNL_bp=None,
     los = nbody.safe_div(c, np.linalg.norm(c))
     geom = np.ascontiguousarray(np.concatenate([np.asarray(box_size, dtype=np.float64), c, los]))
     flags = (1 if curved else 0) | (2 if lightcone else 0)
-    tables, nchi, ngrow, g, f = None, 0, 0, 0., 0.
-    if lightcone:
-        d, gtab = nbody._dist_cache(cosmo), nbody._growth_cache(cosmo)
-        nchi, ngrow = len(d["chi"]), len(gtab["a"])
-        tables = torch.from_numpy(np.concatenate([d["chi"][::-1], d["a"][::-1], gtab["a"], gtab["g"], gtab["f"]])).to(dev)
-    else:
-        g, f = float(nbody.a2g(cosmo, a_obs)), float(nbody.a2f(cosmo, a_obs))
+    lc = tables.on_device(cosmo, tables.LIGHTCONE, dev) if lightcone else None
+    lctab, nchi, ngrow = (lc.t, lc.n["chi"], lc.n["a"]) if lightcone else (None, 0, 0)
+    g, f = (0., 0.) if lightcone else (float(nbody.a2g(cosmo, a_obs)), float(nbody.a2f(cosmo, a_obs)))
     nm = 6 if curved else 2
     specs = torch.empty((nm,) + tuple(spec.shape), dtype=torch.complex64, device=dev)
     mu2 = None
@@ -645,17 +626,17 @@ def kaiser_sky(cosmo, lin_mesh, box_size, box_center, box_rot, b1E, fNL_bp=None,
     phi = kphys = tab = nt = None
     if fNL_bp is not None:
         kphys = [float(s) / float(b) for s, b in zip(shape, box_size)]
-        tab, nt = png_table_dev(cosmo, kpow, dev)
+        tab, nt = _png_table(cosmo, kpow, dev)
         plan.call("mcpm_png_div_f32", spec, kphys[0], kphys[1], kphys[2], tab, tab[nt:], nt, 1.0 / plan.M, specs[0])
         phi = torch.empty(tuple(shape), dtype=torch.float32, device=dev)
         plan.call("mcpm_fft_c2r", specs[0], phi, 1)
     del specs
     out = torch.empty(tuple(shape), dtype=torch.float32, device=dev)
-    args = (geom, flags, tables, nchi, ngrow, g, f, float(b1E), 0.0 if fNL_bp is None else float(fNL_bp))
+    args = (geom, flags, lctab, nchi, ngrow, g, f, float(b1E), 0.0 if fNL_bp is None else float(fNL_bp))
     plan.call("mcpm_kaiser_sky_f32", meshes, phi, *args, out)
     if return_ctx:
         return out, _lib.Ctx(plan=plan, spec=spec, shape=tuple(shape), meshes=meshes, phi=phi, args=args, curved=curved, lightcone=lightcone,
-                             mu2=mu2, kphys=kphys, tab=tab, nt=nt)
+                             mu2=mu2, kphys=kphys, tab=tab, nt=nt, lc=lc)
     return out
 
 
@@ -685,11 +666,10 @@ def kaiser_sky_vjp(ctx, out_bar):
         lb, res["trans_bar"] = png_phi_vjp(plan, ctx.spec, ctx.kphys, ctx.tab, ctx.nt, pb)
         lin_bar = lin_bar + lb
     if ctx.lightcone:
-        geom, flags, tables, nchi, ngrow, _, _, b1E, _ = ctx.args
+        geom, flags, lctab, nchi, ngrow, _, _, b1E, _ = ctx.args
         tb = torch.empty(nchi + 2 * ngrow, dtype=torch.float64, device=dev)
-        plan.call("mcpm_kaiser_sky_tables_vjp_f32", ctx.meshes, geom, flags, tables, nchi, ngrow, b1E, ob, tb)
-        t = tb.cpu().numpy()
-        res["tables"] = {"chi": t[:nchi].copy(), "g": t[nchi:nchi + ngrow].copy(), "f": t[nchi + ngrow:].copy()}
+        plan.call("mcpm_kaiser_sky_tables_vjp_f32", ctx.meshes, geom, flags, lctab, nchi, ngrow, b1E, ob, tb)
+        res["tables"] = ctx.lc.bars(tb)
     s = scal.cpu().numpy()
     res.update({"lin_mesh": lin_bar, "b1E": float(s[0]), "fNL_bp": float(s[1]) if ctx.phi is not None else 0.0})
     if not ctx.lightcone:
@@ -700,23 +680,11 @@ def kaiser_sky_vjp(ctx, out_bar):
 # ------------------------------------------------------------------------------------------------
 # Posterior of the initial field under the fiducial linear Kaiser model (bricks.py:234-247), lin2white (bricks.py:159-164) and
 # count2delta (bricks.py:927-937): what `FieldLevelLogDensity.kaiser_post` starts chains from
-_KPOW_TABLES = {}
-
-
-def _kpow_table_dev(cosmo, kpow, device):
-    """(device float64 tensor [ks, pows], n): the linear-power table normalised to sigma8 = 1 as mcpm_power_mult_f32 takes it -- `kpow`, or
-    the Eisenstein & Hu table of this cosmology; uploaded once per source."""
-    key = (None if kpow is None else (id(kpow[0]), id(kpow[1])), float(cosmo.Omega_c), float(cosmo.Omega_b), float(cosmo.h), float(cosmo.n_s),
-           str(device))
-    hit = _KPOW_TABLES.get(key)
-    if hit is None or (kpow is not None and (hit[2] is not kpow[0] or hit[3] is not kpow[1])):
-        if len(_KPOW_TABLES) > 8:
-            _KPOW_TABLES.clear()
-        ks, pows = power.lin_power_table(cosmo) if kpow is None else kpow
-        tab = np.concatenate([np.asarray(ks, dtype=np.float64), np.asarray(pows, dtype=np.float64)])
-        hit = _KPOW_TABLES[key] = (torch.from_numpy(tab).to(device), len(tab) // 2, None if kpow is None else kpow[0],
-                                   None if kpow is None else kpow[1])
-    return hit[0], hit[1]
+def power_mult(plan, spec, kphys, cosmo, kpow, sigma8, out):
+    """out = spec sqrt(sigma8^2 P(|k|)) (mcpm_power_mult_f32), P the table `kpow` (sigma8 = 1) or the Eisenstein & Hu one of `cosmo`."""
+    tab = tables.on_device(cosmo, tables.POWER, spec.device, kpow=kpow)
+    plan.call("mcpm_power_mult_f32", spec, kphys[0], kphys[1], kphys[2], float(sigma8) ** 2, tab.t, tab.v["pows"], tab.n["ks"], out)
+    return out
 
 
 def kaiser_post_white(delta_obs, noise, cosmo, a, box_size, var_noise, b1E, los=(0., 0., 0.), kpow=None, temp=1., scale_field=1.,
@@ -729,7 +697,7 @@ def kaiser_post_white(delta_obs, noise, cosmo, a, box_size, var_noise, b1E, los=
     shape = nbody.ch2rshape(spec.shape)
     plan, dev = nbody.get_plan(shape), spec.device
     kphys = [float(s) / float(b) for s, b in zip(shape, box_size)]
-    tab, nt = _kpow_table_dev(cosmo, kpow, dev)
+    tab = tables.on_device(cosmo, tables.POWER, dev, kpow=kpow)
     white, n_chains = None, 1
     if noise is not None:
         noise = nbody._c64(noise)
@@ -739,7 +707,7 @@ def kaiser_post_white(delta_obs, noise, cosmo, a, box_size, var_noise, b1E, los=
         white = torch.empty_like(noise)
     means = torch.empty_like(spec) if moments else None
     stds = torch.empty(tuple(spec.shape), dtype=torch.float32, device=dev) if moments else None
-    plan.call("mcpm_kaiser_post_c64", spec, noise, n_chains, kphys[0], kphys[1], kphys[2], float(cosmo.sigma8) ** 2, tab, tab[nt:], nt,
+    plan.call("mcpm_kaiser_post_c64", spec, noise, n_chains, kphys[0], kphys[1], kphys[2], float(cosmo.sigma8) ** 2, tab.t, tab.v["pows"], tab.n["ks"],
               *[float(l) for l in los], float(nbody.a2g(cosmo, a)), float(nbody.a2f(cosmo, a)), float(b1E), float(var_noise), float(temp),
               float(scale_field), float(np.prod(kphys)), white, means, stds)
     return white, means, stds
@@ -759,12 +727,8 @@ def lin2white(cosmo, lin_mesh, init_shape, box_size, kpow=None):
     """Linear matter mesh -> white noise mesh (bricks.py:159-164): safe_div(lin_mesh, sqrt(P(|k|))), 0 where P = 0 (k = 0 and the modes
     outside the table).  The divisor is the multiplier of white2lin (mcpm_power_mult_f32 on a mesh of ones), its reciprocal made safe."""
     spec = nbody._c64(lin_mesh, utils.r2chshape(init_shape))
-    plan, dev = nbody.get_plan(init_shape), spec.device
     kphys = [float(s) / float(b) for s, b in zip(init_shape, box_size)]
-    tab, nt = _kpow_table_dev(cosmo, kpow, dev)
-    t = torch.empty_like(spec)
-    plan.call("mcpm_power_mult_f32", torch.ones_like(spec), kphys[0], kphys[1], kphys[2], float(cosmo.sigma8) ** 2, tab, tab[nt:], nt, t)
-    t = t.real
+    t = power_mult(nbody.get_plan(init_shape), torch.ones_like(spec), kphys, cosmo, kpow, cosmo.sigma8, torch.empty_like(spec)).real
     ok = t != 0
     return torch.where(ok, spec / torch.where(ok, t, torch.ones_like(t)), torch.zeros_like(spec))
 
@@ -957,16 +921,6 @@ def _up(x, dtype):
     return torch.from_numpy(np.ascontiguousarray(x, dtype=dtype)).to(nbody._device())
 
 
-def _dist_table_dev(cosmo):
-    """(the distance table [a | chi] on the device, its length), uploaded once per cosmology: kept next to the host table in
-    `cosmo._workspace`, so the chunk loops do not copy it again."""
-    key = "catalog.distance_table_device"
-    if key not in cosmo._workspace:
-        d = nbody._dist_cache(cosmo)
-        cosmo._workspace[key] = (_up(np.concatenate([d["a"], d["chi"]]), np.float64), len(d["a"]))
-    return cosmo._workspace[key]
-
-
 def _cell_geom(box_center, box_rotvec, box_size, mesh_shape):
     """geom18 of include/mcpm.h: box_center, the matrix of box_rotvec (row-major), box_size, mesh_shape."""
     g = np.concatenate([np.asarray(box_center, dtype=np.float64).reshape(3), rot_matrix(box_rotvec).reshape(9),
@@ -987,12 +941,12 @@ def sky_extent(cosmo, radecz, weights=None):
     """(low corner (3,), high corner (3,), weight sum) of radecz2cart(cosmo, radecz), all float64, in one pass on the device
     (mcpm_sky2cart_minmax_f64); no objects: (+inf, -inf, 0)."""
     ra, dec, z = _radecz_dev(radecz)
-    tab, nt = _dist_table_dev(cosmo)
+    tab = tables.on_device(cosmo, tables.DISTANCE, ra.device)
     w = None if weights is None else _up(weights, np.float64)
     if w is not None and w.shape != ra.shape:
         raise ValueError("weights must be as long as RA")
     out = torch.empty(7, dtype=torch.float64, device=ra.device)
-    nbody.get_plan((8, 8, 8)).call("mcpm_sky2cart_minmax_f64", ra, dec, z, ra.numel(), tab, tab[nt:], nt, w, out, out[6:])
+    nbody.get_plan((8, 8, 8)).call("mcpm_sky2cart_minmax_f64", ra, dec, z, ra.numel(), tab.t, tab.v["chi_dist"], tab.n["a_dist"], w, out, out[6:])
     out = out.cpu().numpy()
     return out[:3], out[3:6], float(out[6])
 
@@ -1001,12 +955,12 @@ def sky2cell_pos(cosmo, radecz, box_center, box_rotvec, box_size, mesh_shape, ra
     """phys2cell_pos(radecz2cart(cosmo, radecz), ...) as an (N, 3) float32 device tensor, formed in float64 and rounded once
     (mcpm_sky2cell_f32).  With `ratio` (3,): also that tensor times float32(ratio), the positions at another mesh shape."""
     ra, dec, z = _radecz_dev(radecz)
-    tab, nt = _dist_table_dev(cosmo)
+    tab = tables.on_device(cosmo, tables.DISTANCE, ra.device)
     geom = _cell_geom(box_center, box_rotvec, box_size, mesh_shape)
     out = torch.empty((ra.numel(), 3), dtype=torch.float32, device=ra.device)
     out2 = None if ratio is None else torch.empty_like(out)
     ratio = None if ratio is None else np.ascontiguousarray(ratio, dtype=np.float64).reshape(3)
-    nbody.get_plan(mesh_shape).call("mcpm_sky2cell_f32", ra, dec, z, ra.numel(), tab, tab[nt:], nt, geom, ratio, out, out2)
+    nbody.get_plan(mesh_shape).call("mcpm_sky2cell_f32", ra, dec, z, ra.numel(), tab.t, tab.v["chi_dist"], tab.n["a_dist"], geom, ratio, out, out2)
     return out if ratio is None else (out, out2)
 
 

@@ -49,7 +49,7 @@ from types import SimpleNamespace
 import numpy as np
 import torch
 
-from . import nbody, bricks, metrics, _lib
+from . import nbody, bricks, metrics, tables, _lib
 from .utils import r2chshape, chreshape, chreshape_vjp, rg2cgh, rg2cgh_vjp, cgh2rg, mesh2masked, masked2mesh
 
 LOG2PI = math.log(2 * math.pi)
@@ -454,7 +454,7 @@ class FieldLevelLogDensity:
         kmesh = sum(ki ** 2 for ki in kvec) ** .5
         mu = nbody.safe_div(sum(ki * li for ki, li in zip(kvec, k.los)), kmesh)
         boost = float(nbody.a2g(cosmo_fid, a_fid)) * (k.b1E + float(nbody.a2f(cosmo_fid, a_fid)) * mu ** 2)
-        ks, pows = fwd.kpow(cosmo_fid)
+        ks, pows = tables.host_tables(cosmo_fid, tables.POWER, kpow=fwd.lin_kpow).values()
         pmesh = np.interp(kmesh.reshape(-1), ks, pows * float(fid["sigma8"]) ** 2, left=0., right=0.).reshape(kmesh.shape)
         pmesh *= unit ** 2                                                                # power in cell units
         scale_k = (1 + boost ** 2 / var_fid * pmesh) ** .5

@@ -28,7 +28,7 @@ from __future__ import annotations
 import numpy as np
 import torch
 
-from . import nbody, bricks, metrics
+from . import nbody, bricks, metrics, tables
 from ._lib import Ctx as EvolveCtx
 from .utils import scale_shape, r2chshape, chreshape, chreshape_vjp
 
@@ -71,7 +71,6 @@ class FieldLevelForward:
         # lin_kpow = (ks, pows) normalised to sigma8 = 1, or None: the Eisenstein-Hu power of the CURRENT cosmology
         # (bricks.py:69-79; montecosmo_amd/power.py), re-tabulated whenever Omega_m / Omega_b / h / n_s change
         self.lin_kpow = None if lin_kpow is None else (np.asarray(lin_kpow[0], dtype=np.float64), np.asarray(lin_kpow[1], dtype=np.float64))
-        self._dev_kpow = {}
         self._r0 = self._los_cell = None
 
     def config(self):
@@ -123,28 +122,11 @@ class FieldLevelForward:
     def _kphys(self, shape):
         return [float(s) / float(b) for s, b in zip(shape, self.box_size)]
 
-    def kpow(self, cosmo):
-        """(ks, pows) normalised to sigma8 = 1 for this cosmology: the given table, or Eisenstein-Hu (power.py)."""
-        if self.lin_kpow is not None:
-            return self.lin_kpow
-        from . import power
-        return power.lin_power_table(cosmo)
-
     def _power_mult(self, spec, cosmo, sigma8=None):
         """white2lin (bricks.py:149-154): spec * sqrt(sigma8^2 P(|k|)); real multiplier, self-adjoint.  `sigma8` overrides the
         cosmology's (1.0 gives d init_mesh / d sigma8, which stays finite where a bounded latent has walked to sigma8 = 0)."""
-        key = None if self.lin_kpow is not None else (float(cosmo.Omega_c), float(cosmo.Omega_b), float(cosmo.h), float(cosmo.n_s))
-        tab = self._dev_kpow.get(key)
-        if tab is None:
-            if len(self._dev_kpow) > 8:
-                self._dev_kpow.clear()
-            tab = self._dev_kpow[key] = torch.from_numpy(np.concatenate(self.kpow(cosmo))).to(spec.device)
-        nt = tab.numel() // 2
-        plan = nbody.get_plan(self.init_shape)
-        out = torch.empty_like(spec)
-        kp = self._kphys(self.init_shape)
-        plan.call("mcpm_power_mult_f32", spec, kp[0], kp[1], kp[2], float(cosmo.sigma8 if sigma8 is None else sigma8) ** 2, tab, tab[nt:], nt, out)
-        return out
+        return bricks.power_mult(nbody.get_plan(self.init_shape), spec, self._kphys(self.init_shape), cosmo, self.lin_kpow,
+                                 cosmo.sigma8 if sigma8 is None else sigma8, torch.empty_like(spec))
 
     def los_cell(self):
         """Line of sight (the direction of the box centre) in cell axes (model.py:607-608); host float64, computed once."""
@@ -170,8 +152,8 @@ class FieldLevelForward:
             # the flat-sky product is summed per row here and by `@` in the log density: the two differ in the last bit of a float64,
             # and each consumer keeps the bits it has always had
             self._r0 = nbody._f32(self.lattice_radius(self.evol_shape, self.ptcl_shape, flat_dot=lambda p, los: (p * los).sum(-1)))
-        d = nbody._dist_cache(cosmo)
-        return nbody.interp_dev(self._r0, d["chi"][::-1], d["a"][::-1]).reshape(-1, 1)
+        c = tables.on_device(cosmo, tables.CHI2A, self._r0.device)
+        return nbody.interp_dev(self._r0, c.v["chi"], c.v["a_of_chi"]).reshape(-1, 1)
 
     # ---- Kaiser model: growth, Eulerian linear bias and RSD.  Flat sky at fixed a (bricks.py:170-198): diagonal in k, `_kaiser`;
     # curved sky and / or light cone (bricks.py:200-231): a real-space pass with a line of sight and a growth factor per cell, `_kaiser_sky` ----
@@ -186,7 +168,7 @@ class FieldLevelForward:
 
     def _png_div(self, spec, cosmo, scale):
         """scale * safe_div(spec, t(|k|)) on the evolution mesh, t from `lin_kpow` as the reference's Kaiser model takes it."""
-        tab, nt = bricks.png_table_dev(cosmo, self.lin_kpow, spec.device)
+        tab, nt = bricks._png_table(cosmo, self.lin_kpow, spec.device)
         out, kp = torch.empty_like(spec), self._kphys(self.evol_shape)
         nbody.get_plan(self.evol_shape).call("mcpm_png_div_f32", spec, kp[0], kp[1], kp[2], tab, tab[nt:], nt, float(scale), out)
         return out
@@ -252,7 +234,7 @@ class FieldLevelForward:
         if getattr(ctx, "png", None) is not None:
             # the PNG term is fNL_bp phi in real space, phi = irfftn(evol_k / t): phi_bar = fNL_bp gxy_bar, pulled back to evol_k and the table
             bp_bar = float((kb.conj() * self._png_div(ctx.evol_k, cosmo, 1.0)).real.double().sum())
-            tab, nt = bricks.png_table_dev(cosmo, self.lin_kpow, kb.device)
+            tab, nt = bricks._png_table(cosmo, self.lin_kpow, kb.device)
             lb, trans_bar = bricks.png_phi_vjp(nbody.get_plan(self.evol_shape), ctx.evol_k, self._kphys(self.evol_shape), tab, nt,
                                                gb * float(ctx.png["fNL_bp"]))
             evol_b = evol_b + lb
@@ -463,57 +445,43 @@ class FieldLevelForward:
         (a_obs = None) the look-ups are per particle: `_cosmo_vjp_lightcone`."""
         if self.a_obs is None:
             return self._cosmo_vjp_lightcone(ctx, grads, params, rel_eps)
-        cosmo, a = ctx.cosmo, self.a_obs
         pre = getattr(ctx, "scalar_fd", None) or {}
-
         if self.evolution == 'kaiser':
-            g, bars = None, [float(grads["kaiser"]["g"]), float(grads["kaiser"]["f"])]
+            bars = [float(grads["kaiser"]["g"]), float(grads["kaiser"]["f"])]
         else:
             g = grads["growth"]
             bars = [float(np.asarray(grads["bias_growth"]).sum()), float(grads["gf"])]
-        if self.evolution == 'kaiser':
-            pass
-        elif self.evolution == 'lpt':
+            if self.evolution == 'nbody':
+                bars += [float(g["dg"])] + list(g["alpha"]) + list(g["beta"])
             bars += [float(g["g"]), float(g["g2"]), float(g["dg2dg"])]
-        else:
-            bars += [float(g["dg"])] + list(g["alpha"]) + list(g["beta"]) + [float(g["g"]), float(g["g2"]), float(g["dg2dg"])]
-        bars = np.array(bars)
         chi_bar = grads["ap_chi_bar"].cpu().numpy() if grads.get("ap_chi_bar") is not None else None
-        out = {}
-        for name in params:
-            h, pair = self._cosmo_fd_pair(cosmo, name, rel_eps)
-            # the table Jacobian's two evaluations: made while the device ran the forward pass, or here
+
+        def terms(name, h, pair):
+            # the table Jacobian's two evaluations, (scalars, chi nodes) each: made while the device ran the forward pass, or here
             vals = pre.get((name, rel_eps)) or [self._cosmo_scalars_chi(c) for c in pair]
-            # the Eisenstein-Hu shape moves with the cosmology: init_mesh = white sqrt(P)
-            inits = [self._power_mult(ctx.white, c) for c in pair] if self.lin_kpow is None else []
-            out[name] = float(np.dot(bars, (vals[0][0] - vals[1][0]) / (2 * h))) + self._trans_term(grads, pair, h)
-            if chi_bar is not None:
-                out[name] += float(np.dot(chi_bar, (vals[0][1] - vals[1][1]) / (2 * h)))
-            if inits:
-                out[name] += float((grads["init_bar"].conj() * (inits[0] - inits[1])).real.sum().item()) / (2 * h)
-        cosmo._workspace = {}
+            return [float(np.dot(b, (p - m) / (2 * h))) for b, p, m in zip((np.array(bars), chi_bar), *vals) if b is not None]
+
+        out = self._cosmo_fd(ctx, grads, params, rel_eps, terms)
+        ctx.cosmo._workspace = {}
         return out
 
-    @staticmethod
-    def _cosmo_fd_pair(cosmo, name, rel_eps):
-        """(h, [cosmology at +h, at -h]) of a central difference over one parameter of the cosmology; 'Omega_m' varies Omega_c at fixed
-        Omega_b.  Each copy starts with an empty `_workspace` of its own (a plain copy would share the dict), so whatever reads its tables
-        derives them from the copy's attributes and `cosmo`'s cached tables stay as they are."""
-        import copy
-        attr = "Omega_c" if name == "Omega_m" else name
-        base = float(getattr(cosmo, attr))
-        h = rel_eps * max(abs(base), 1e-2)
-        pair = []
-        for sgn in (+1, -1):
-            c = copy.copy(cosmo)
-            c._workspace = {}
-            setattr(c, attr, base + sgn * h)
-            pair.append(c)
-        return h, pair
+    def _cosmo_fd(self, ctx, grads, params, rel_eps, terms):
+        """{name: dL/dtheta} by one central difference per parameter (tables.fd_pair).  `terms(name, h, pair)` lists the contractions of the
+        growth and distance tables; the transfer-table and Eisenstein-Hu terms are the same at fixed a_obs and on the light cone.  Summed in
+        a fixed order: first table term, transfer, further table terms, Eisenstein-Hu."""
+        out = {}
+        for name in params:
+            h, pair = tables.fd_pair(ctx.cosmo, name, rel_eps)
+            first, *rest = terms(name, h, pair)
+            out[name] = sum(rest, first + self._trans_term(grads, pair, h))
+            if self.lin_kpow is None:      # the Eisenstein-Hu shape moves with the cosmology: init_mesh = white sqrt(P)
+                inits = [self._power_mult(ctx.white, c) for c in pair]
+                out[name] += float((grads["init_bar"].conj() * (inits[0] - inits[1])).real.sum().item()) / (2 * h)
+        return out
 
     def _trans_term(self, grads, pair, h):
         """<trans_bar, d trans / d theta> for the phi -> delta transfer table (png_type set), the table Jacobian by the same host
-        central difference (`pair`, `h` of `_cosmo_fd_pair`) as the growth tables.  (sigma8 cancels in the table, so its derivative has no
+        central difference (`pair`, `h` of `tables.fd_pair`) as the growth tables.  (sigma8 cancels in the table, so its derivative has no
         such term.)"""
         if grads.get("trans_bar") is None:
             return 0.0
@@ -539,48 +507,33 @@ class FieldLevelForward:
         """(`_cosmo_scalars`, chi nodes ascending of the distance table or None): the second entry only with ap_auto=True, where the
         Alcock-Paczynski look-up chi2a(cosmo, r') is the one per-particle table dependence at fixed a_obs."""
         s = self._cosmo_scalars(c)
-        return s, (nbody._dist_cache(c)["chi"][::-1].copy() if (self.ap_auto and self.evolution != 'kaiser') else None)
+        return s, (tables.host_tables(c, tables.CHI2A)["chi"] if (self.ap_auto and self.evolution != 'kaiser') else None)
 
     def _cosmo_scalar_fd(self, cosmo, params, rel_eps=1e-5):
         """{(name, rel_eps): ((scalars, chi nodes) at +h, the same at -h)}: the two evaluations of cosmo_vjp's central difference.  Host work of about
         a millisecond (two growth-table solves per parameter) that `evolve` does right after it has queued the forward pass, while the
         device runs it; left to cosmo_vjp it sits at the very end of a gradient, with the device idle (`cosmo_fd_params`)."""
         # (the copies carry their own tables: `cosmo`'s cached ones stay for the rest of evolve)
-        return {(name, rel_eps): tuple(self._cosmo_scalars_chi(c) for c in self._cosmo_fd_pair(cosmo, name, rel_eps)[1]) for name in params}
+        return {(name, rel_eps): tuple(self._cosmo_scalars_chi(c) for c in tables.fd_pair(cosmo, name, rel_eps)[1]) for name in params}
 
     # ---- light cone: the cosmology enters through per-particle table look-ups -----------------------------------------
-    _LC_TABLES = ("chi", "g", "g2", "f", "f2")
-
-    def _lightcone_tables(self, cosmo):
-        """The five cosmology-dependent tables the light-cone look-ups read (host float64): chi ascending (the nodes of
-        chi2a, nbody.py:862-884; its values, the scale-factor grid, do not move) and g, g2 (raw), f, f2 on the growth grid."""
-        d, gt = nbody._dist_cache(cosmo), nbody._growth_cache(cosmo)
-        return {"chi": d["chi"][::-1].copy(), "g": gt["g"], "g2": gt["g2"], "f": gt["f"], "f2": gt["f2"]}
-
     def lightcone_table_bars(self, ctx, grads):
         """Cotangents of those tables (dict of float64 arrays): the Lagrangian look-ups a_q = chi2a(r0_q) -> a2g (bias weights,
         model.py:756, and lpt), a2g2, a2dg2dg (lpt, nbody.py:652-666) contracted with the per-particle cotangents of
         `evolve_vjp` (mcpm_lightcone_tables_vjp_f32), plus the observation-side a2g a2f at the evolved positions
         (model.py:781-784; mcpm_observe_pos_tables_vjp_f32) and, with ap_auto=True, the chi2a(cosmo, r') of ap_auto in the same chi bar
         (mcpm_observe_pos_ap_tables_vjp_f32)."""
-        cosmo = ctx.cosmo
-        d, gt = nbody._dist_cache(cosmo), nbody._growth_cache(cosmo)
-        nchi, ng = len(d["chi"]), len(gt["a"])
         dev = ctx.evol_k.device
-        tabs = torch.from_numpy(np.concatenate([d["chi"][::-1], d["a"][::-1], gt["a"], gt["g"], gt["g2"], gt["f"], gt["f2"]])).to(dev)
-        plan = nbody.get_plan(self.evol_shape, self.ptcl_shape)
-        n = plan.N
-        g = grads["growth"]
+        tab = tables.on_device(ctx.cosmo, tables.LIGHTCONE_VJP, dev)
+        nchi, ng = tab.n["chi"], tab.n["a"]
+        plan, g = nbody.get_plan(self.evol_shape, self.ptcl_shape), grads["growth"]
         gB = (nbody._f32(grads["bias_growth"]).reshape(-1) + nbody._f32(g["g"]).reshape(-1)).contiguous()
         g2B, dB = nbody._f32(g["g2"]).reshape(-1).contiguous(), nbody._f32(g["dg2dg"]).reshape(-1).contiguous()
         tbL = torch.empty(nchi + 4 * ng, dtype=torch.float64, device=dev)
-        plan.call("mcpm_lightcone_tables_vjp_f32", self._r0, n, tabs, nchi, ng, gB, g2B, dB, tbL)
-        o = ctx.octx
-        tbO = bricks.observe_pos_tables_vjp(o, grads["obs_bar"])      # with ap_auto=True the Alcock-Paczynski look-up arrives in its chi bar
-        L, O = tbL.cpu().numpy(), tbO.cpu().numpy()
-        out = {"chi": L[:nchi] + O[:nchi], "g": L[nchi:nchi + ng] + O[nchi:nchi + ng], "g2": L[nchi + ng:nchi + 2 * ng],
-               "f": L[nchi + 2 * ng:nchi + 3 * ng] + O[nchi + ng:], "f2": L[nchi + 3 * ng:]}
-        return out
+        plan.call("mcpm_lightcone_tables_vjp_f32", self._r0, plan.N, tab.t, nchi, ng, gB, g2B, dB, tbL)
+        # with ap_auto=True the Alcock-Paczynski look-up arrives in the chi bar of the observation side
+        L, O = tab.bars(tbL), ctx.octx.lc.bars(bricks.observe_pos_tables_vjp(ctx.octx, grads["obs_bar"]))
+        return {k: L[k] + O[k] if k in O else L[k] for k in L}
 
     def _cosmo_vjp_lightcone(self, ctx, grads, params, rel_eps):
         """cosmo_vjp on the light cone (a_obs = None, the reference's default configuration, model.py:45, :62): dL/dtheta =
@@ -588,16 +541,11 @@ class FieldLevelForward:
         float64 RK4 tables (256-point distance table, 128-point growth tables), plus the Eisenstein-Hu term as at fixed a_obs."""
         if self.evolution == 'nbody':
             raise NotImplementedError("light cone is built for evolution='lpt' and 'kaiser' (model.py:770 asserts the same for 'nbody')")
-        cosmo = ctx.cosmo
         # 'kaiser': the per-cell look-ups a = chi2a(r), a2g(a), a2f(a) of bricks.kaiser_sky, already contracted by evolve_vjp (chi, g, f)
         bars = grads["kaiser"] if self.evolution == 'kaiser' else self.lightcone_table_bars(ctx, grads)
-        out = {}
-        for name in params:
-            h, pair = self._cosmo_fd_pair(cosmo, name, rel_eps)
-            tabs = [self._lightcone_tables(c) for c in pair]
-            inits = [self._power_mult(ctx.white, c) for c in pair] if self.lin_kpow is None else []
-            out[name] = float(sum(np.dot(bars[k], (tabs[0][k] - tabs[1][k]) / (2 * h)) for k in self._LC_TABLES if k in bars))
-            out[name] += self._trans_term(grads, pair, h)
-            if inits:
-                out[name] += float((grads["init_bar"].conj() * (inits[0] - inits[1])).real.sum().item()) / (2 * h)
-        return out
+
+        def terms(name, h, pair):
+            p, m = [tables.host_tables(c, tables.LIGHTCONE_VJP) for c in pair]
+            return [float(sum(np.dot(bars[k], (p[k] - m[k]) / (2 * h)) for k in tables.LIGHTCONE_VJP if k in bars))]
+
+        return self._cosmo_fd(ctx, grads, params, rel_eps, terms)

@@ -18,7 +18,7 @@ from itertools import product
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, tables
 from ._lib import lib, Ctx, POS_ABSOLUTE, POS_LATTICE
 from .utils import safe_div, ch2rshape, r2chshape, scale_shape, chreshape, chreshape_vjp  # noqa: F401 (re-exported like the reference)
 
@@ -613,27 +613,21 @@ def pm_forces2(pos, mesh, read_order: int = 2, grad_fd=np.inf, lap_fd=np.inf):
 
 
 def interp_dev(x, xp, fp, scale=1.0):
-    """np.interp(x, xp, fp) * scale for a float32 device tensor x (mcpm_interp_f32); xp, fp host float64 tables."""
+    """np.interp(x, xp, fp) * scale for a float32 device tensor x (mcpm_interp_f32); xp, fp: host float64 tables, or views of a tables.Table."""
     x = _f32(x).reshape(-1)
-    tab = torch.from_numpy(np.concatenate([np.asarray(xp, dtype=np.float64), np.asarray(fp, dtype=np.float64)])).to(x.device)
+    if not torch.is_tensor(xp):
+        xp, fp = tables.upload(xp, x.device), tables.upload(fp, x.device)
     out = torch.empty_like(x)
-    nt = len(xp)
-    get_plan((8, 8, 8)).call("mcpm_interp_f32", x, x.numel(), tab, tab[nt:], nt, float(scale), out)
+    get_plan((8, 8, 8)).call("mcpm_interp_f32", x, x.numel(), xp, fp, xp.numel(), float(scale), out)
     return out
 
 
 def growth_dev(cosmo, a, which):
     """Growth quantity `which` in {'g', 'g2', 'dg2dg', 'f'} at per-particle scale factors `a` given as a device tensor
     (same tables and linear interpolation as the host functions a2g, a2g2, a2dg2dg, a2f)."""
-    c = _growth_cache(cosmo)
-    if which == "g":
-        return interp_dev(a, c["a"], c["g"])
-    if which == "g2":
-        return interp_dev(a, c["a"], c["g2"], -3 / 7)
-    if which == "f":
-        return interp_dev(a, c["a"], c["f"])
-    if which == "f2":
-        return interp_dev(a, c["a"], c["f2"])
+    c = tables.on_device(cosmo, tables.GROWTH, a.device)
+    if which in ("g", "g2", "f", "f2"):
+        return interp_dev(a, c.v["a"], c.v[which], -3 / 7 if which == "g2" else 1.0)
     if which == "dg2dg":      # a2dg2dg = safe_div(g2 f2, g f) of the four separately interpolated values (nbody.py:775-777)
         num = growth_dev(cosmo, a, "g2") * growth_dev(cosmo, a, "f2")
         den = growth_dev(cosmo, a, "g") * growth_dev(cosmo, a, "f")
@@ -1099,18 +1093,10 @@ def cosmo_vjp(ctx, scalar_bars, params=("Omega_c",), rel_eps=1e-5):
     + g_bar dg(a0)/dtheta + g2_bar dg2(a0)/dtheta + dg2dg_bar d(dg2dg)(a0)/dtheta, with the Jacobian of the
     (128-point RK4) tables taken by central finite differences (nbody.py:679-808, :907-931 are host scalars).
     `params` are attribute names of the cosmology object (e.g. 'Omega_c', 'Omega_b', 'w0')."""
-    import copy
     out = {}
     for name in params:
-        base = float(getattr(ctx.cosmo, name))
-        h = rel_eps * max(abs(base), 1e-2)
-        vals = []
-        for sgn in (+1, -1):
-            c = copy.copy(ctx.cosmo)
-            c._workspace = {}
-            setattr(c, name, base + sgn * h)
-            vals.append(_step_scalars(c, ctx.a0, ctx.a1, ctx.n_steps, ctx.integrator))
-        (dgp, ap, bp, lp), (dgm, am, bm, lm) = vals
+        h, pair = tables.fd_pair(ctx.cosmo, name, rel_eps)
+        (dgp, ap, bp, lp), (dgm, am, bm, lm) = [_step_scalars(c, ctx.a0, ctx.a1, ctx.n_steps, ctx.integrator) for c in pair]
         d = lambda p_, m_: (np.asarray(p_) - np.asarray(m_)) / (2 * h)
         out[name] = float(np.dot(scalar_bars["alpha"], d(ap, am)) + np.dot(scalar_bars["beta"], d(bp, bm))
                           + scalar_bars["dg"] * d(dgp, dgm)

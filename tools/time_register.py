@@ -39,7 +39,7 @@ def main():
     ap.add_argument("--n", type=int, default=1 << 24)
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
-    from montecosmo_amd import bricks, nbody, register
+    from montecosmo_amd import bricks, nbody, register, tables
     n = a.n
     rng = np.random.default_rng(0)
     rnd = {'RA': rng.uniform(100, 140, n), 'DEC': np.rad2deg(np.arcsin(rng.uniform(np.sin(np.deg2rad(10)), np.sin(np.deg2rad(40)), n))),
@@ -54,7 +54,8 @@ def main():
     box = np.multiply(shape, cell)
     dev = nbody._device()
     ra, dec, z, w = (torch.from_numpy(rnd[k]).to(dev) for k in ('RA', 'DEC', 'Z', 'WEIGHT'))
-    tab, nt = bricks._dist_table_dev(cosmo)
+    dist = tables.on_device(cosmo, tables.DISTANCE, dev)
+    tab, nt = dist.t, dist.n["a_dist"]
     geom = bricks._cell_geom(center, np.zeros(3), box, shape)
     plan = nbody.get_plan(shape)
     out7 = torch.empty(7, dtype=torch.float64, device=dev)
