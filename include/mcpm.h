@@ -806,6 +806,31 @@ int mcpm_mclmc_kick_drift_f32(mcpm_plan *plan, float *u, float *q, const float *
      product and sum rounded on its own (q^2 is exact in float64). */
 int mcpm_mclmc_moments_f64(mcpm_plan *plan, const float *q, int64_t d, double gamma, double w, double *xavg, double *x2avg);
 
+/* ---- chain diagnostics (numpyro.diagnostics as montecosmo/metrics.py:562-579 uses it; chains.hip) -----------------------------
+   Draws x[c, t, d] of n_chain chains, float32 on the DEVICE: element (c, p, t, d) is
+       x[offset0 + c stride_chain + p stride_part + t stride_draw + d],      0 <= d < n_dim contiguous, strides in elements (>= 0),
+   all index arithmetic 64-bit.  A segment is a pair (c, p), numbered c n_part + p, of n_draw draws: whole chains are n_part = 1, the two
+   halves of split R-hat n_part = 2 with stride_part = (N - h) stride_draw and n_draw = h, the equal blocks of a thinning n_part blocks.
+   No plan: `stream` is a hipStream_t.  One lane forms a dimension's result alone, in float64 and in an order fixed by (segments, n_draw,
+   bias): every output is bitwise the same call after call, and does not depend on n_dim, on the dimension's position, on the alignment
+   of x or on the other dimensions.  A NULL pointer, n_dim / n_chain / n_part / n_draw < 1, a negative offset or stride, or more than
+   65535 segments return MCPM_E_ARG and launch nothing.
+
+   moments: mean[seg][d] = the float64 mean over the draws and m2[seg][d] = sum (x - mean)^2, in two sweeps as numpy.var makes them. */
+int mcpm_chain_moments_f32(void *stream, const float *x, int64_t offset0, int64_t n_dim, int n_chain, int64_t stride_chain, int n_part,
+                           int64_t stride_part, int64_t n_draw, int64_t stride_draw, double *mean, double *m2);
+/* tau: the integrated autocorrelation time of every dimension, each segment taken as one chain of N = n_draw draws (they share N), from
+     the mean and m2 of `moments` on the same layout.  With S segments, v_s = m2_s / (N - 1), W = mean_s v_s, V = W (N - 1) / N
+     + var_s(mean_s, ddof 1) (S = 1: W = V), gamma(k) = mean_s sum_{t < N - k} y_s[t] y_s[t + k] / N (bias = 0: / (N - k)),
+     rho_k = 1 - (W - gamma(k)) / V, rho_0 = 1, pairs P_j = rho_2j + rho_2j+1 for j < N_even / 2 (N_even = N - N % 2):
+         tau[d] = -1 + 2 (P_0 + sum_{j >= 1} cummin_j max(P_j, 0)),      ess = S N / tau.
+     n_lags[d] (int32) = 2 (j_stop + 1), j_stop the first j >= 1 with P_j <= 0, or N_even when there is none.  The lags are summed 16 per
+     sweep over the draws and a wave stops when each of its dimensions has met its j_stop: never later than N_even / 2 pairs, NaN data
+     included (tau = NaN, n_lags = N_even).  A constant dimension gives NaN (0 / 0).  n_draw < 2: MCPM_E_ARG. */
+int mcpm_chain_tau_f32(void *stream, const float *x, int64_t offset0, int64_t n_dim, int n_chain, int64_t stride_chain, int n_part,
+                       int64_t stride_part, int64_t n_draw, int64_t stride_draw, const double *mean, const double *m2, int bias,
+                       double *tau, unsigned *n_lags);
+
 /* RK4 on atab = logspace(log10_amin, 0, steps); writes seven host arrays of length `steps`. */
 int mcpm_growth_table(double Omega_m, double Omega_de, double Omega_k, double w0, double wa,
                       double log10_amin, int steps, double *a, double *g, double *f, double *h, double *g2,

@@ -203,6 +203,10 @@ SIGNATURES = {
     "mcpm_masked_sum_f64": (C.c_int, [_plan, _f32p, _u8p, C.c_int64, _d64p]),
     "mcpm_mclmc_kick_drift_f32": (C.c_int, [_plan, _f32p, _f32p, _f32p, _f32p, C.c_int64, C.c_double, C.c_double, _d64p]),
     "mcpm_mclmc_moments_f64": (C.c_int, [_plan, _f32p, C.c_int64, C.c_double, C.c_double, _d64p, _d64p]),
+    "mcpm_chain_moments_f32": (C.c_int, [C.c_void_p, _f32p, C.c_int64, C.c_int64, C.c_int, C.c_int64, C.c_int, C.c_int64, C.c_int64, C.c_int64,
+                                         _d64p, _d64p]),
+    "mcpm_chain_tau_f32": (C.c_int, [C.c_void_p, _f32p, C.c_int64, C.c_int64, C.c_int, C.c_int64, C.c_int, C.c_int64, C.c_int64, C.c_int64,
+                                     _d64p, _d64p, C.c_int, _d64p, _u32p]),
     "mcpm_growth_table": (C.c_int, [C.c_double] * 6 + [C.c_int] + [_f64p] * 7),
     "mcpm_distance_table": (C.c_int, [C.c_double] * 6 + [C.c_int] + [_f64p] * 2),
 }

@@ -28,13 +28,14 @@ import numpy as np
 import torch
 
 from . import nbody, _lib
+from .chains import multi_ess, multi_gr, harmean, geomean      # the chain metrics of montecosmo/metrics.py:562-579 (chains.py)
 from .utils import safe_div, ch2rshape
 
 MAX_EDGES = 4096               # MCPM_SPECTRUM_MAX_EDGES
 CHUNK_BYTES = 1 << 32          # device memory a batch chunk may take (spectra, real staging, workspace)
 
 __all__ = ["spectrum", "transfer", "coherence", "powtranscoh", "bin_and_aggregate", "mse_radius", "mse_value", "mse_wave", "distr_radial",
-           "MAX_EDGES"]
+           "multi_ess", "multi_gr", "harmean", "geomean", "MAX_EDGES"]
 
 
 # ------------------------------------------------------------------------------------------------

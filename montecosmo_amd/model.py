@@ -96,6 +96,18 @@ class FieldLevelForward:
         """(k, pow1, (pow1 / pow0)^.5, pow01 / (pow0 pow1)^.5) with the model's box_size; a batched mesh1 gives batched outputs."""
         return metrics.powtranscoh(mesh0, mesh1, box_size=self.box_size, kedges=kedges, include_corners=include_corners)
 
+    def powtranscoh_chains(self, chains, mesh0, names: str | list = (), kedges: int | float | list = None):
+        """A copy of `chains` (chains.Chains) with, for every entry `name` of meshes (C, N, *mesh), the tuple `kptc_<name>` =
+        powtranscoh(mesh0, mesh) per draw, each of shape (C, N, bins) (model.py:1429-1442): the chain and draw axes go through the
+        batch axis of metrics.powtranscoh together."""
+        out = chains.copy()
+        for name in np.atleast_1d(names):
+            x = torch.as_tensor(chains[str(name)])
+            c, n = x.shape[:2]
+            res = self.powtranscoh(mesh0, x.reshape((c * n,) + tuple(x.shape[2:])), kedges=kedges)
+            out[f"kptc_{name}"] = tuple(r.reshape((c, n) + r.shape[1:]) for r in res)
+        return out
+
     def mse_value(self, mesh0, mesh1, cell_length=None, vedges: int | float | list = 50, min_count=None, aggr_fn=None):
         """metrics.mse_value with the model's cell_length (model.py:1390-1394): by default 50 quantile bins of mesh0."""
         return metrics.mse_value(mesh0, mesh1, self.cell_length if cell_length is None else cell_length, vedges=vedges, min_count=min_count,

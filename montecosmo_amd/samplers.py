@@ -357,6 +357,15 @@ class FlatLogDensity:
             if self.scalars else np.zeros(0)
         return torch.cat([torch.tensor(vals, dtype=torch.float32, device=w.device), w])
 
+    def layout(self):
+        """name -> (start, stop, shape) of every latent in the flat vector (what `unpack` slices): chains.Chains.from_flat takes it."""
+        out, k = {}, 0
+        for n, sz in zip(self.scalars, self.sizes):
+            out[n] = (k, k + sz, (sz,) if n == "ngbars_" else ())
+            k += sz
+        out["white_mesh_"] = (k, k + int(math.prod(self.shape)), self.shape)
+        return out
+
     def unpack(self, q):
         vals = q[:self.ns].tolist()
         out, k = {}, 0
