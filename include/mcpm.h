@@ -831,6 +831,39 @@ int mcpm_chain_tau_f32(void *stream, const float *x, int64_t offset0, int64_t n_
                        int64_t stride_part, int64_t n_draw, int64_t stride_draw, const double *mean, const double *m2, int bias,
                        double *tau, unsigned *n_lags);
 
+/* ---- MAP optimisation and Laplace approximation (montecosmo/samplers.py:671-696, montecosmo/lapprox.py; lapprox.hip) ---------------
+   Shape-free passes over flat DEVICE vectors of length d, as the integrator above: the plan lends its stream and reduction scratch, the
+   pointers need not be 16-byte aligned (aligned ones take 16-byte accesses, with bitwise the same results), every value is formed in
+   float64 and rounded once, every output is bitwise the same call after call, and there is no floating-point atomic.
+
+   The Rademacher probe r of (seed, probe) is never stored; each pass regenerates it.  With all arithmetic modulo 2^64 and
+       splitmix64(x):  x += 0x9E3779B97F4A7C15;  x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9;  x = (x ^ (x >> 27)) * 0x94D049BB133111EB;
+                       return x ^ (x >> 31),
+       key = splitmix64(seed ^ splitmix64(probe)),
+       r_i = +1 if the top bit of splitmix64(i ^ key) is 0, else -1,      for start <= i < stop;  r_i = 0 elsewhere.
+
+   adam_step: one epoch of Adam (jax.example_libraries.optimizers.adam) for the gradient g of the LOG density, g_U = -g:
+         m' = (1 - b1) g_U + b1 m,   v' = (1 - b2) g_U^2 + b2 v,   q' = q - lr (m' c1) / (sqrt(v' c2) + eps),
+     with the caller's lr = lr0 / sqrt(1 + i), c1 = 1 / (1 - b1^(i+1)), c2 = 1 / (1 - b2^(i+1)) at epoch i = 0, 1, ...  q' is formed from the
+     float64 m' and v'; q, m, v (float32) are updated in place, every product and sum rounded on its own.  d < 1 or a NULL pointer:
+     MCPM_E_ARG. */
+int mcpm_adam_step_f32(mcpm_plan *plan, float *q, float *m, float *v, const float *g, int64_t d, double lr, double b1, double b2,
+                       double eps, double c1, double c2);
+/* probe_shift: q_plus = q + eps r and q_minus = q - eps r (either may be NULL); outside start .. stop they are copies of q.
+     Not 0 <= start <= stop <= d: MCPM_E_ARG. */
+int mcpm_probe_shift_f32(mcpm_plan *plan, const float *q, int64_t d, int64_t start, int64_t stop, uint64_t seed, uint64_t probe,
+                         double eps, float *q_plus, float *q_minus);
+/* hutchinson_accum: diag[i] += coef r_i (g_plus[i] - g_minus[i]) in float64 for start <= i < stop (the difference, the product and the
+     sum each rounded on their own); the other entries of diag (DEVICE double[d]) are not touched.  With coef = -1 / (2 eps n_probes) and the
+     LOG density's gradients at q_plus and q_minus, n_probes calls leave the Hutchinson estimate of the diagonal of the Hessian of
+     U = -log p. */
+int mcpm_hutchinson_accum_f64(mcpm_plan *plan, const float *g_plus, const float *g_minus, int64_t d, int64_t start, int64_t stop,
+                              uint64_t seed, uint64_t probe, double coef, double *diag);
+/* schur: out[i m + j] = sum_k B[i ldb + k] B[j ldb + k] / (D[k] + eps_diag), 0 <= k < n, in float64 (B float32 with row stride
+     ldb >= n, D and out DEVICE double): the m x m matrix B (D + eps_diag)^-1 B^T of the Schur complement.  Fixed-order sums, computed for
+     i <= j and mirrored: out is exactly symmetric.  m < 1 or m > 16: MCPM_E_ARG. */
+int mcpm_schur_f64(mcpm_plan *plan, const float *B, int m, int64_t n, int64_t ldb, const double *D, double eps_diag, double *out);
+
 /* RK4 on atab = logspace(log10_amin, 0, steps); writes seven host arrays of length `steps`. */
 int mcpm_growth_table(double Omega_m, double Omega_de, double Omega_k, double w0, double wa,
                       double log10_amin, int steps, double *a, double *g, double *f, double *h, double *g2,

@@ -892,3 +892,66 @@ def chain_sampler(kind="mclmc", **warmup_kw):
             state = dict(state, q=state["q"].to(q0.device), u=state["u"].to(q0.device))
         return run(logdensity_and_grad, state, config, n_samples, backend=backend, **kw)
     return sampler
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# MAP optimisation (montecosmo/samplers.py:671-696: `optimize`, Adam from jax.example_libraries.optimizers with the learning
+# rate lr0 / sqrt(1 + i)).  jax is not installed where this was written: the update below is restated from knowledge of that
+# library (adam(step_size, b1=0.9, b2=0.999, eps=1e-8): m and v start at zero, both are bias-corrected, eps is added to the
+# root), as is done for numpyro and jax_cosmo elsewhere in the package.
+def _adam_torch(q, m, v, g, lr, b1, b2, eps, c1, c2):
+    """One Adam epoch in place through torch ops: the formulas of csrc/lapprox.hip in float64, rounded once to the dtype of q."""
+    gu = -g.double()
+    md = (1.0 - b1) * gu + b1 * m.double()
+    vd = (1.0 - b2) * (gu * gu) + b2 * v.double()
+    q.copy_(q.double() - (lr * (md * c1)) / (torch.sqrt(vd * c2) + eps))
+    m.copy_(md)
+    v.copy_(vd)
+
+
+def optimize(logdensity_and_grad, start, lr0=0.1, n_epochs=100, b1=0.9, b2=0.999, eps=1e-8, backend="auto", callback=None):
+    """Climbs the log density from `start` by Adam, the reference's `optimize(potential, start, lr0, n_epochs)` on the flat
+    contract `logdensity_and_grad(q) -> (lp, g)`.  With U = -log p, g_U = -g and epoch i = 0, 1, ...:
+
+        m = (1 - b1) g_U + b1 m,   v = (1 - b2) g_U^2 + b2 v,
+        q -= lr0 / sqrt(1 + i) * [m / (1 - b1^(i+1))] / (sqrt(v / (1 - b2^(i+1))) + eps)
+
+    which is jax.example_libraries.optimizers.adam under the schedule lr0 / sqrt(1 + i), restated from knowledge of that
+    library (jax is not a dependency).  Returns (q, pots): pots[i] is the potential at the point epoch i STARTS from, as in the
+    reference, and q the state after the last update.  A non-finite log density (FlatLogDensity returns -inf outside the support)
+    stops the loop: the last point whose potential was finite is returned, with pots up to there.  A NaN raises.
+
+    backend 'hip' runs one fused pass per epoch (mcpm_adam_step_f32) on a flat contiguous float32 device vector, 'torch' the same
+    formulas through torch ops on any dtype and device, 'auto' takes 'hip' where it applies.  Nothing is random: two runs from one
+    start are bitwise equal.  callback(i, {'potential', 'lr'}) is called once per epoch."""
+    if backend == "auto":
+        backend = "hip" if hip_backend_applies(start) else "torch"
+    if backend not in ("hip", "torch"):
+        raise ValueError(f"backend must be 'auto', 'hip' or 'torch', not {backend!r}")
+    q = start.clone()
+    if backend == "hip":
+        from . import nbody
+        if not hip_backend_applies(q):
+            raise ValueError("backend='hip' serves flat contiguous float32 device tensors")
+        plan = nbody.get_plan((8, 8, 8))      # shape-free pass: the plan lends its stream
+    m, v, last = torch.zeros_like(q), torch.zeros_like(q), q.clone()
+    pots = []
+    for i in range(int(n_epochs)):
+        lp, g = logdensity_and_grad(q)
+        lp = float(lp)
+        if math.isnan(lp):
+            raise FloatingPointError(f"log density is NaN at epoch {i}")
+        if not math.isfinite(lp):      # the last update left the support
+            return last, pots
+        pots.append(-lp)
+        last.copy_(q)
+        lr = lr0 / math.sqrt(1.0 + i)
+        c1, c2 = 1.0 / (1.0 - b1 ** (i + 1)), 1.0 / (1.0 - b2 ** (i + 1))
+        if backend == "hip":
+            plan.call("mcpm_adam_step_f32", q, m, v, g if g.is_contiguous() else g.contiguous(), q.numel(), lr, float(b1), float(b2),
+                      float(eps), c1, c2)
+        else:
+            _adam_torch(q, m, v, g, lr, b1, b2, eps, c1, c2)
+        if callback is not None:
+            callback(i, {"potential": -lp, "lr": lr})
+    return q, pots

@@ -27,6 +27,8 @@ ap.add_argument("--n-chains", type=int, default=4)
 ap.add_argument("--field-warmup", type=int, default=256, help="transitions of the field-only warm-up")
 ap.add_argument("--warmup", type=int, default=512, help="transitions of the full warm-up")
 ap.add_argument("--tune-mass", action="store_true", help="estimate a diagonal inverse mass in the full warm-up")
+ap.add_argument("--inverse-mass", default=None, metavar="FILE", help="start the full warm-up from the diagonal inverse mass of this .npz "
+                "(array 'inverse_mass' over the whole flat vector: tools/run_map_laplace.py writes one)")
 ap.add_argument("--n-runs", type=int, default=2)
 ap.add_argument("--n-samples", type=int, default=16, help="kept states per run")
 ap.add_argument("--thinning", type=int, default=64)
@@ -94,9 +96,12 @@ else:
     # phase 2: full warm-up from the warmed field and the fiducial scalars
     t0 = time.perf_counter()
     states, configs = [], []
+    config0 = None
+    if a.inverse_mass:
+        config0 = {"inverse_mass": torch.from_numpy(np.load(a.inverse_mass)["inverse_mass"]).float().cuda()}
     for c in range(a.n_chains):
         q1 = joint.pack(dict(ld.sample_params(scalars), white_mesh_=fields[c]))
-        st, cf = warmup(joint, q1, a.warmup, diagonal_preconditioning=a.tune_mass, seed=a.seed + 100 * c + 1, backend=a.backend)
+        st, cf = warmup(joint, q1, a.warmup, config=config0, diagonal_preconditioning=a.tune_mass, seed=a.seed + 100 * c + 1, backend=a.backend)
         states.append(st)
         configs.append(cf)
         print(f"chain {c} full warm-up: step size {cf['step_size']:.4f} L {cf['L']:.2f} [{time.perf_counter() - t0:.0f} s]", flush=True)
