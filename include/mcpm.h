@@ -831,6 +831,29 @@ int mcpm_chain_tau_f32(void *stream, const float *x, int64_t offset0, int64_t n_
                        int64_t stride_part, int64_t n_draw, int64_t stride_draw, const double *mean, const double *m2, int bias,
                        double *tau, unsigned *n_lags);
 
+/* ---- order statistics of chains (montecosmo/bdec.py: quantile, qbci, sci_noweights; bdec.hip) --------------------------------------
+   The draws as above, without parts: element (c, t, d) is x[offset0 + c stride_chain + t stride_draw + d], float32 on the DEVICE, and the
+   M = n_chain n_draw draws of a dimension are pooled, m = c n_draw + t.  Each dimension is sorted on chip (LDS) by the IEEE total order of
+   its values (-inf < .. < -0 < +0 < .. < +inf < NaN, every NaN alike and last), x_(0) <= .. <= x_(M-1), and one call leaves
+     out[r n_dim + d] = x_(ranks[r]), 0 <= r < n_rank: exact copies of input values (a NaN as the canonical quiet NaN).  `ranks` is a HOST
+       array of n_rank <= MCPM_BDEC_MAX_RANKS ints;
+     if sci != NULL: the smallest window of L = sci_len: with i the first index in 0 .. M - L - 1 that minimises
+       (double) x_(i+L) - (double) x_(i) (a NaN length, both ends the same infinity, counts as +inf), sci[d] = x_(i), sci[n_dim + d] = x_(i+L),
+       sci_idx[d] = i (int32); a dimension that holds a NaN gives NaN, NaN and -1;
+     if truth != NULL (n_dim floats): below[d] and equal[d] (int32) = the number of draws with x < truth[d] and with x == truth[d], as IEEE
+       compares them (-0 == +0; a NaN is neither);
+     if sorted != NULL: sorted[m n_dim + d] = x_(m), 0 <= m < M.
+   No atomics: every output is bitwise the same call after call and does not depend on n_dim, on the dimension's position, on its
+   neighbours or on the alignment of x.  A NULL x / ranks / out, n_dim / n_chain / n_draw < 1, n_rank outside 1 .. MCPM_BDEC_MAX_RANKS, a rank
+   outside [0, M), sci without sci_idx or with L outside [0, M - 1], truth without below and equal, a negative offset or stride: MCPM_E_ARG.
+   M > MCPM_BDEC_MAX_M (a row no longer fits the LDS tile): MCPM_E_UNSUPPORTED; the caller sorts such chains another way (bdec.py).
+   Either way nothing is launched. */
+#define MCPM_BDEC_MAX_M 32768
+#define MCPM_BDEC_MAX_RANKS 64
+int mcpm_bdec_sort_f32(void *stream, const float *x, int64_t offset0, int64_t n_dim, int n_chain, int64_t stride_chain, int64_t n_draw,
+                       int64_t stride_draw, const int *ranks, int n_rank, float *out, int64_t sci_len, float *sci, int *sci_idx,
+                       const float *truth, int *below, int *equal, float *sorted);
+
 /* ---- MAP optimisation and Laplace approximation (montecosmo/samplers.py:671-696, montecosmo/lapprox.py; lapprox.hip) ---------------
    Shape-free passes over flat DEVICE vectors of length d, as the integrator above: the plan lends its stream and reduction scratch, the
    pointers need not be 16-byte aligned (aligned ones take 16-byte accesses, with bitwise the same results), every value is formed in

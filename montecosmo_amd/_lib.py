@@ -207,6 +207,8 @@ SIGNATURES = {
                                          _d64p, _d64p]),
     "mcpm_chain_tau_f32": (C.c_int, [C.c_void_p, _f32p, C.c_int64, C.c_int64, C.c_int, C.c_int64, C.c_int, C.c_int64, C.c_int64, C.c_int64,
                                      _d64p, _d64p, C.c_int, _d64p, _u32p]),
+    "mcpm_bdec_sort_f32": (C.c_int, [C.c_void_p, _f32p, C.c_int64, C.c_int64, C.c_int, C.c_int64, C.c_int64, C.c_int64, C.POINTER(C.c_int), C.c_int,
+                                     _f32p, C.c_int64, _f32p, _u32p, _f32p, _u32p, _u32p, _f32p]),
     "mcpm_adam_step_f32": (C.c_int, [_plan, _f32p, _f32p, _f32p, _f32p, C.c_int64] + [C.c_double] * 6),
     "mcpm_probe_shift_f32": (C.c_int, [_plan, _f32p, C.c_int64, C.c_int64, C.c_int64, C.c_uint64, C.c_uint64, C.c_double, _f32p, _f32p]),
     "mcpm_hutchinson_accum_f64": (C.c_int, [_plan, _f32p, _f32p, C.c_int64, C.c_int64, C.c_int64, C.c_uint64, C.c_uint64, C.c_double, _d64p]),

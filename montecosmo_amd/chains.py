@@ -33,7 +33,7 @@ import torch
 from . import _lib, nbody
 
 __all__ = ["effective_sample_size", "autocorr_time", "gelman_rubin", "split_gelman_rubin", "chain_moments", "segment_moments",
-           "multi_ess", "multi_gr", "harmean", "geomean", "Chains"]
+           "multi_ess", "multi_gr", "quantile", "credint", "harmean", "geomean", "Chains"]
 
 HOST_CHUNK_BYTES = 1 << 28      # float64 working set of one host chunk
 
@@ -348,6 +348,18 @@ def multi_gr(x, axis=None, backend="auto"):
     return _reduce(r, dims, axis, lambda t, ax: torch.sqrt((t * t).mean(dim=ax)), lambda a, ax: np.sqrt(np.mean(a ** 2, axis=ax)))
 
 
+def quantile(x, p, backend="auto"):
+    """bdec.quantile of the pooled chains and draws of x (C, N, *dims): float64 (*p.shape, *dims)."""
+    from . import bdec      # (imports this module for its chunks)
+    return bdec.quantile(_check(x, 1), p, axis=(0, 1), backend=backend)
+
+
+def credint(x, p=.95, type="small", backend="auto"):
+    """bdec.credint of the pooled chains and draws of x (C, N, *dims): float64 (*p.shape, *dims, 2); the smallest interval takes a scalar p."""
+    from . import bdec
+    return bdec.credint(_check(x, 1), p, axis=(0, 1), type=type, backend=backend)
+
+
 # ------------------------------------------------------------------------------------------------
 N_EVALS = "n_evals"
 
@@ -501,6 +513,26 @@ class Chains(dict):
 
     def eval_per_ess(self, axis=None):
         return self.multi_ess(axis=axis)._times(lambda n, x: n / x)
+
+    def quantile(self, p):
+        """Quantiles of the pooled chains and draws of every entry: (*p.shape, *dims) (bdec.quantile)."""
+        return self.metric(lambda x: quantile(x, p, backend=self.backend), axis=(0, 1))
+
+    def credint(self, p=.95, type="small"):
+        """Credible intervals of the pooled chains and draws of every entry: (*p.shape, *dims, 2) (bdec.credint)."""
+        return self.metric(lambda x: credint(x, p, type=type, backend=self.backend), axis=(0, 1))
+
+    def coverage(self, truth, p=.95, type="small"):
+        """Per entry of `truth` (a dict of arrays of shape dims) the fraction of its dimensions with low <= truth <= high, the p-credible
+        interval of `type` taken over the pooled chains and draws."""
+        out = {}
+        for k, t in truth.items():
+            ci = credint(self[k], p, type=type, backend=self.backend)
+            t = _host64(t)
+            if t.shape != ci.shape[:-1]:
+                raise ValueError(f"truth of {k!r} must have shape {ci.shape[:-1]}, got {t.shape}")
+            out[k] = float(np.mean((ci[..., 0] <= t) & (t <= ci[..., 1])))
+        return out
 
     def thin(self, thinning=None, moment=None):
         """The draws in n_split = max(rint(N / thinning), 1) blocks (as numpy.array_split makes them) -> one value per block along axis 1:
