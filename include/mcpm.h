@@ -454,6 +454,28 @@ int mcpm_nbody_bf_vjp_f32(mcpm_plan *plan, const float *init_mesh, int n_steps, 
                           const double *beta, double dg, const double *lpt_scalars, int lpt_order,
                           int paint_order, const float *ckpt, const float *pos_bar, const float *vel_bar,
                           float *init_mesh_bar, double *scalar_bars);
+/* N-body state on the light cone (no reference counterpart: montecosmo/model.py:770 asserts a scalar a): every particle takes the Euler
+   solution of a mcpm_nbody_bf_f32 run at its own growth time g_p[p] = a2g(a_p), by linear interpolation between the step states, as
+   diffrax's dense output does for whole snapshots.  With K = n_steps, g0 = a2g(a0), dg the run's step:
+     s = (g_p - g0) / dg,  i = clamp(floor(s), 0, K - 1),  theta = clamp(s - i, 0, 1),
+     disp = (1 - theta) x_i + theta x_{i+1},  vel = (1 - theta) v_i + theta v_{i+1}
+   with the step states as displacements from the lattice: (x_i, v_i) = (x'_i - v_i dg / 2, v_i) from arrays 2 i and 2 i + 1 of `ckpt`
+   (the pitch in force: mcpm_plan_particle_pitch) for i < K, and (pos_out, vel_out) of that run for i = K.  Particles earlier than
+   the start take the LPT start state, later than the end the final state; theta = 0 and theta = 1 return a state bit for bit.  s is
+   formed in double and the index clamped before any address is: no g_p reads out of range, a NaN g_p takes interval 0 and gives
+   NaN.  ckpt, pos_out, vel_out: what mcpm_nbody_bf_f32 wrote; g_p: N floats; disp, vel: (N, 3) outputs. */
+int mcpm_nbody_lightcone_f32(mcpm_plan *plan, const float *ckpt, int n_steps, double dg, double g0, const float *pos_out,
+                             const float *vel_out, const float *g_p, float *disp, float *vel);
+/* Its reverse sweep: mcpm_nbody_bf_vjp_f32 with pos_bar, vel_bar the cotangents of (disp, vel), injected state by state with the
+   weights of the selection (state K first, state i after step i's adjoint, state 0 before the initial half drift and the LPT
+   adjoint; the steps stay chained).  g_bar_p (N floats) receives the cotangent of g_p, (pos_bar . (x_{i+1} - x_i) +
+   vel_bar . (v_{i+1} - v_i)) / dg, 0 where theta was clamped.  scalar_bars keeps the layout of mcpm_nbody_bf_vjp_f32; the
+   dependence of theta on g0 and dg, and of x_j = x'_j - v_j dg / 2 on dg, is added into g_bar (g0 IS a2g(a0)) and dg_bar.  All sums
+   in a fixed order, no floating-point atomics.  With every particle later than the end it is mcpm_nbody_bf_vjp_f32 bit for bit. */
+int mcpm_nbody_bf_lc_vjp_f32(mcpm_plan *plan, const float *init_mesh, int n_steps, const double *alpha, const double *beta, double dg,
+                             double g0, const double *lpt_scalars, int lpt_order, int paint_order, const float *ckpt,
+                             const float *pos_out, const float *vel_out, const float *g_p, const float *pos_bar,
+                             const float *vel_bar, float *init_mesh_bar, float *g_bar_p, double *scalar_bars);
 
 /* ---- likelihoods besides 'quad_gauss' (montecosmo/model.py:872-886, :911-932), value and gradient in one pass ---------------- */
 #define MCPM_LIK_SHASH 0

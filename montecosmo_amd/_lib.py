@@ -176,6 +176,9 @@ SIGNATURES = {
     "mcpm_plan_set_particle_pitch": (C.c_int, [_plan, C.c_int64]),
     "mcpm_plan_particle_pitch": (C.c_int, [_plan, C.POINTER(C.c_int64)]),
     "mcpm_nbody_bf_vjp_f32": (C.c_int, [_plan, _f32p, C.c_int, _f64p, _f64p, C.c_double, _f64p, C.c_int, C.c_int, _f32p, _f32p, _f32p, _f32p, _f64p]),
+    "mcpm_nbody_lightcone_f32": (C.c_int, [_plan, _f32p, C.c_int, C.c_double, C.c_double, _f32p, _f32p, _f32p, _f32p, _f32p]),
+    "mcpm_nbody_bf_lc_vjp_f32": (C.c_int, [_plan, _f32p, C.c_int, _f64p, _f64p, C.c_double, C.c_double, _f64p, C.c_int, C.c_int, _f32p, _f32p,
+                                           _f32p, _f32p, _f32p, _f32p, _f32p, _f32p, _f64p]),
     "mcpm_slab_rccl_unique_id": (C.c_int, [C.c_void_p]),
     "mcpm_slab_comm_init_local": (C.c_int, [_plan]),
     "mcpm_slab_comm_init_rccl": (C.c_int, [_plan, C.c_void_p]),

@@ -933,4 +933,69 @@ int mcpm_nbody_bf_vjp_f32(mcpm_plan *p, const float *init_mesh, int n_steps, con
     return MCPM_OK;
 }
 
+// The sweep above with the loss cotangents (Xb, Vb) of the LIGHT-CONE state (lightcone.hip) injected state by state: state K opens the
+// sweep, state i follows step i's adjoint and precedes step i - 1's, state 0 precedes the initial half drift and the LPT adjoint.
+// The steps stay chained.  After a hinted step vel_bar holds u = v_bar + tau' x_bar (tau' = dg as a float, what the kernel used), which is
+// linear in the two cotangents: the injection adds w Xb to pos_bar and w (Vb + (tau' - dg/2) Xb) to u, exactly what adding w Xb to x_bar
+// and w (Vb - dg/2 Xb) to v_bar would have made of it, so the carry stays the sum the next step expects and no hint is left pending
+// across the modification (the step's launcher consumed it).  What the injection does invalidate is the maximum of |beta' u| that the
+// step's kernel left for the fixed-point paint of u: the paint takes it again from the array (fx_src).  Where no particle has a weight
+// for a state nothing is written, and the sweep is the plain one bit for bit.
+int mcpm_nbody_bf_lc_vjp_f32(mcpm_plan *p, const float *init_mesh, int n_steps, const double *alpha, const double *beta, double dg, double g0,
+                             const double *lpt_scalars, int lpt_order, int paint_order, const float *ckpt, const float *pos_out,
+                             const float *vel_out, const float *g_p, const float *pos_bar, const float *vel_bar, float *init_mesh_bar,
+                             float *g_bar_p, double *scalar_bars) {
+    if (!p) return MCPM_E_ARG;
+    MCPM_REQUIRE(p, init_mesh && alpha && beta && lpt_scalars && ckpt && pos_out && vel_out && g_p && pos_bar && vel_bar && init_mesh_bar && g_bar_p,
+                 MCPM_E_ARG, "mcpm_nbody_bf_lc_vjp_f32: null argument");
+    MCPM_REQUIRE(p, n_steps >= 1 && 2 * n_steps + MCPM_RED_SWEEP_TAIL <= MCPM_NREDUCE - MCPM_RED_SWEEP, MCPM_E_ARG, "mcpm_nbody_bf_lc_vjp_f32: bad n_steps");
+    MCPM_REQUIRE(p, paint_order >= 1 && paint_order <= 4, MCPM_E_ORDER, "mcpm_nbody_bf_lc_vjp_f32: paint_order must be 1..4");
+    MCPM_REQUIRE(p, lpt_order == 1 || lpt_order == 2, MCPM_E_ORDER, "mcpm_nbody_bf_lc_vjp_f32: lpt_order must be 1 or 2");
+    MCPM_REQUIRE(p, dg != 0. && dg == dg && g0 == g0, MCPM_E_ARG, "mcpm_nbody_bf_lc_vjp_f32: dg must be non-zero, dg and g0 numbers");
+    const int64_t N = p->Np, M = p->M;
+    MCPM_TRY(ensure_pscratch(p));
+    float *xb = ps_arr(p, 0), *vb = ps_arr(p, 1);
+    const int64_t pitch = mcpm_pitch(p);
+    auto state_x = [&](int i) { return ckpt + (int64_t)(2 * i) * pitch; };
+    auto state_v = [&](int i) { return ckpt + (int64_t)(2 * i + 1) * pitch; };
+    auto force_m = [&](int i) { return ckpt + (int64_t)n_steps * 2 * mcpm_pitch_max(p) + (int64_t)i * 3 * M; };
+    double *alpha_bar = p->reduce + MCPM_RED_SWEEP, *beta_bar = alpha_bar + n_steps, *lpt_bar = beta_bar + n_steps, *dg_bar = lpt_bar + 3;
+    const size_t nbars = 2 * (size_t)n_steps + MCPM_RED_SWEEP_TAIL;
+    MCPM_HIP(p, hipMemsetAsync(alpha_bar, 0, sizeof(double) * nbars, p->stream));
+    p->fb_valid = 0;
+    p->hint_set = 0;
+    MCPM_TRY(carry_undo(p));      // a carry left pending by the caller lives in ITS arrays: turned back before this sweep owns the plan's
+    // cotangent of g_p, and the theta terms of g0 (into g: g0 IS a2g(a0)) and of dg, with dg's share of x_j = x'_j - v_j dg/2
+    MCPM_TRY(mcpm_lc_gbar(p, ckpt, n_steps, dg, g0, pos_out, vel_out, g_p, pos_bar, vel_bar, g_bar_p, lpt_bar, dg_bar));
+    MCPM_TRY(mcpm_lc_inject(p, n_steps, n_steps, dg, g0, g_p, pos_bar, vel_bar, 0.f, 1, xb, vb));
+    for (int i = n_steps - 1; i >= 0; --i) {
+        if (i > 0) MCPM_TRY(mcpm_plan_hint_next_adjoint(p, beta[i - 1], dg));
+        const bool first = i == n_steps - 1;
+        MCPM_TRY(mcpm_bullfrog_step_vjp_from_f32(p, state_x(i), state_v(i), force_m(i), alpha[i], beta[i], first ? dg / 2 : dg, paint_order,
+                                                 xb, vb, xb, vb, alpha_bar + i, beta_bar + i, first ? 0.5 : 1.0, dg_bar));
+        const bool carried = p->carry_valid && p->carry_vb == vb;
+        const double tau_c = carried ? (double)p->carry_tau : 0.;
+        MCPM_TRY(mcpm_lc_inject(p, i, n_steps, dg, g0, g_p, pos_bar, vel_bar, (float)(tau_c - dg / 2), 0, xb, vb));
+        if (p->fx_src == vb) p->fx_src = nullptr;
+    }
+    {
+        unsigned nbk = (unsigned)((3 * N + 255) / 256);
+        DetSum s;
+        MCPM_TRY(mcpm_det_begin(p, 1, nbk, &s));
+        dot_partial_kernel<<<nbk, 256, 0, p->stream>>>(xb, state_v(0), 3 * N, s.P);
+        MCPM_LAUNCH_CHECK(p, "dot_partial_kernel");
+        MCPM_TRY(mcpm_det_fold(p, s, 1, 0.5, det_outs_ptrs(DET_ACCUMULATE, dg_bar)));
+    }
+    MCPM_TRY(axpby(p, vb, xb, 3 * N, 1.f, (float)(dg / 2), vb));
+    MCPM_TRY(lpt_vjp_device(p, init_mesh, lpt_order, lpt_scalars, xb, vb, init_mesh_bar, lpt_bar, MCPM_FD_INF, MCPM_FD_INF,
+                            ckpt + ckpt_lpt_offset(p, n_steps)));
+    if (scalar_bars) {
+        MCPM_HIP(p, hipMemcpyAsync(scalar_bars, alpha_bar, sizeof(double) * nbars, hipMemcpyDeviceToHost, p->stream));
+        MCPM_HIP(p, hipStreamSynchronize(p->stream));
+        scalar_bars[2 * n_steps + 1] = -scalar_bars[2 * n_steps + 1];
+        scalar_bars[2 * n_steps + 2] = -scalar_bars[2 * n_steps + 2];
+    }
+    return MCPM_OK;
+}
+
 }  // extern "C"

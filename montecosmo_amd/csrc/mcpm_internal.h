@@ -257,6 +257,15 @@ bool mcpm_paint3_tiled(mcpm_plan *p, const float *pos, const float *weights3, fl
 int mcpm_paint3_scaled(mcpm_plan *p, const float *pos, int64_t n, int mode, const float *weights3, float wscale, int order, float *meshes3,
                        int accumulate);
 
+// light-cone selection of the N-body state (lightcone.hip), the two passes its reverse sweep (composite.hip) is built from.
+// mcpm_lc_gbar: g_bar_p (N floats) from the loss cotangents (Xb, Vb); *g_bar -= sum g_bar_p and *dg_bar -= sum g_bar_p (g_p - g0) / dg
+// + sum_{j < K} w_j Xb . v_j / 2 (DEVICE doubles, deterministic grid sums).  mcpm_lc_inject: state j's share of (Xb, Vb) into the running
+// cotangents, pos_bar += w Xb, vel_bar += w (Vb + cu Xb); init: pos_bar = w Xb, vel_bar = w Vb instead (state K).
+int mcpm_lc_gbar(mcpm_plan *p, const float *ckpt, int n_steps, double dg, double g0, const float *pos_out, const float *vel_out,
+                 const float *g_p, const float *Xb, const float *Vb, float *g_bar_p, double *g_bar, double *dg_bar);
+int mcpm_lc_inject(mcpm_plan *p, int j, int n_steps, double dg, double g0, const float *g_p, const float *Xb, const float *Vb, float cu,
+                   int init, float *xb, float *vb);
+
 // adjoint of the NGP lattice read on a lattice != mesh: order-independent fixed-point sums (particles.hip)
 int mcpm_lattice_scatter_fx(mcpm_plan *p, const float *xb, const float *vb, float a, float b, float *meshes3);
 

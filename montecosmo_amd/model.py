@@ -1,7 +1,7 @@
 """`FieldLevelModel.evolve` (montecosmo/model.py:686-838) on the HIP path, with its hand-written reverse sweep.
 
 Built branches: bias_type 'lagrangian' or 'eulerian' (model.py:68, :753-754, :797-831; `FieldLevelForward(bias_type=)`), evolution 'lpt'
-(scalar a_obs or light cone), 'nbody' (scalar a_obs, as the reference asserts) or 'kaiser' (any sky, scalar a_obs or light cone: bricks.py:170-231), png_type None, 'fNL' or 'bias' (local primordial
+(scalar a_obs or light cone), 'nbody' (scalar a_obs as the reference asserts, or the light cone: every particle at the time of its Lagrangian lattice point) or 'kaiser' (any sky, scalar a_obs or light cone: bricks.py:170-231), png_type None, 'fNL' or 'bias' (local primordial
 non-Gaussianity: `evolve(..., png={'fNL': ..., ...})`, model.py:688, :751-758), ap_auto None, True or False (Alcock-Paczynski:
 model.py:64, :787-794; `evolve(..., ap={'alpha_iso': ..., 'alpha_ap': ...})` for False), kernel_type 'rectangular', linear power from a table (`lin_kpow`,
 bricks.py:75-77) or, with lin_kpow = None, from the Eisenstein-Hu fit of the current cosmology (bricks.py:72-74; power.py).
@@ -66,12 +66,10 @@ class FieldLevelForward:
         self.evolution, self.nbody_a_start, self.nbody_n_steps = evolution, float(nbody_a_start), int(nbody_n_steps)
         self.lpt_order, self.paint_order, self.paint_deconv = int(lpt_order), int(paint_order), bool(paint_deconv)
         self.interlace_order, self.a_obs, self.curved_sky = int(interlace_order), a_obs, bool(curved_sky)
-        if evolution == 'nbody' and a_obs is None:
-            raise NotImplementedError("N-body light-cone not implemented (model.py:770)")
         # lin_kpow = (ks, pows) normalised to sigma8 = 1, or None: the Eisenstein-Hu power of the CURRENT cosmology
         # (bricks.py:69-79; montecosmo_amd/power.py), re-tabulated whenever Omega_m / Omega_b / h / n_s change
         self.lin_kpow = None if lin_kpow is None else (np.asarray(lin_kpow[0], dtype=np.float64), np.asarray(lin_kpow[1], dtype=np.float64))
-        self._r0 = self._los_cell = None
+        self._r0 = self._r_min = self._los_cell = None
 
     def config(self):
         """The model attributes as a dict (what the parity tests hand to their float64 checker)."""
@@ -163,9 +161,18 @@ class FieldLevelForward:
         if self._r0 is None:
             # the flat-sky product is summed per row here and by `@` in the log density: the two differ in the last bit of a float64,
             # and each consumer keeps the bits it has always had
-            self._r0 = nbody._f32(self.lattice_radius(self.evol_shape, self.ptcl_shape, flat_dot=lambda p, los: (p * los).sum(-1)))
+            r0 = self.lattice_radius(self.evol_shape, self.ptcl_shape, flat_dot=lambda p, los: (p * los).sum(-1))
+            self._r_min = float(r0.min())      # host float64: the nearest lattice point ends the N-body run on the light cone (`_a_end`)
+            self._r0 = nbody._f32(r0)
         c = tables.on_device(cosmo, tables.CHI2A, self._r0.device)
         return nbody.interp_dev(self._r0, c.v["chi"], c.v["a_of_chi"]).reshape(-1, 1)
+
+    def _a_end(self, cosmo):
+        """End of the N-body run on the light cone: the scale factor of the nearest lattice point, chi2a(cosmo, r_min) -- host float64 from
+        the cached lattice radii (no device synchronisation).  It moves with the cosmology: cosmo_vjp's central differences recompute it."""
+        if self._r_min is None:
+            self._scale_factors(cosmo)
+        return float(nbody.chi2a(cosmo, self._r_min))
 
     # ---- Kaiser model: growth, Eulerian linear bias and RSD.  Flat sky at fixed a (bricks.py:170-198): diagonal in k, `_kaiser`;
     # curved sky and / or light cone (bricks.py:200-231): a real-space pass with a line of sight and a growth factor per cell, `_kaiser_sky` ----
@@ -300,9 +307,12 @@ class FieldLevelForward:
             (dpos, vel), lctx = nbody.lpt(cosmo, lin_k, pos0, a, lpt_order=self.lpt_order, read_order=1, return_ctx=True)
             pos, nctx = pos0 + dpos, lctx      # (the LPT context rides in the N-body context's slot)
         else:
+            # light cone: every particle at the scale factor of its Lagrangian lattice point (as 'lpt' does, model.py:739-741), the run ending
+            # at the nearest one's
+            lckw = {} if self.a_obs is not None else {"a_end": self._a_end(cosmo)}
             (pos, vel), nctx = nbody.nbody_bf(cosmo, lin_k, pos0, a0=self.nbody_a_start, a1=a, n_steps=self.nbody_n_steps,
                                               paint_order=self.paint_order, lpt_order=self.lpt_order, return_ctx=True,
-                                              lattice_out=True)
+                                              lattice_out=True, **lckw)
             vel = vel.reshape(-1, 3)
         # the growth-table Jacobian of cosmo_vjp: a millisecond of host work, done HERE -- the device has the whole evolution queued
         fd = self._cosmo_scalar_fd(cosmo, self.cosmo_fd_params) if (return_ctx and self.a_obs is not None and getattr(self, "cosmo_fd_params", None)) else None
@@ -539,8 +549,12 @@ class FieldLevelForward:
         tab = tables.on_device(ctx.cosmo, tables.LIGHTCONE_VJP, dev)
         nchi, ng = tab.n["chi"], tab.n["a"]
         plan, g = nbody.get_plan(self.evol_shape, self.ptcl_shape), grads["growth"]
-        gB = (nbody._f32(grads["bias_growth"]).reshape(-1) + nbody._f32(g["g"]).reshape(-1)).contiguous()
-        g2B, dB = nbody._f32(g["g2"]).reshape(-1).contiguous(), nbody._f32(g["dg2dg"]).reshape(-1).contiguous()
+        if self.evolution == 'nbody':      # the per-particle look-up of the N-body light cone is a2g alone ('g_lc'); its g / g2 / dg2dg are host scalars
+            gB = (nbody._f32(grads["bias_growth"]).reshape(-1) + nbody._f32(g["g_lc"]).reshape(-1)).contiguous()
+            g2B, dB = torch.zeros_like(gB), torch.zeros_like(gB)
+        else:
+            gB = (nbody._f32(grads["bias_growth"]).reshape(-1) + nbody._f32(g["g"]).reshape(-1)).contiguous()
+            g2B, dB = nbody._f32(g["g2"]).reshape(-1).contiguous(), nbody._f32(g["dg2dg"]).reshape(-1).contiguous()
         tbL = torch.empty(nchi + 4 * ng, dtype=torch.float64, device=dev)
         plan.call("mcpm_lightcone_tables_vjp_f32", self._r0, plan.N, tab.t, nchi, ng, gB, g2B, dB, tbL)
         # with ap_auto=True the Alcock-Paczynski look-up arrives in the chi bar of the observation side
@@ -550,14 +564,28 @@ class FieldLevelForward:
     def _cosmo_vjp_lightcone(self, ctx, grads, params, rel_eps):
         """cosmo_vjp on the light cone (a_obs = None, the reference's default configuration, model.py:45, :62): dL/dtheta =
         sum over the five tables (three for 'kaiser') of <table_bar, d table / d theta>, the table Jacobian by central differences of the host
-        float64 RK4 tables (256-point distance table, 128-point growth tables), plus the Eisenstein-Hu term as at fixed a_obs."""
-        if self.evolution == 'nbody':
-            raise NotImplementedError("light cone is built for evolution='lpt' and 'kaiser' (model.py:770 asserts the same for 'nbody')")
+        float64 RK4 tables (256-point distance table, 128-point growth tables), plus the Eisenstein-Hu term as at fixed a_obs.
+        'nbody' adds the host scalars of the run, as at fixed a_obs: central differences of `_step_scalars(c, a_start, a_end(c), K)` contracted
+        with alpha / beta / dg / g / g2 / dg2dg, the end of the run a_end(c) = chi2a(c, r_min) recomputed for each perturbed cosmology; its
+        per-particle look-up is a2g(a_p) alone (cotangent bias_growth + g_lc, in `lightcone_table_bars`)."""
         # 'kaiser': the per-cell look-ups a = chi2a(r), a2g(a), a2f(a) of bricks.kaiser_sky, already contracted by evolve_vjp (chi, g, f)
         bars = grads["kaiser"] if self.evolution == 'kaiser' else self.lightcone_table_bars(ctx, grads)
 
+        sbar = None
+        if self.evolution == 'nbody':
+            g = grads["growth"]
+            sbar = np.array([float(g["dg"])] + list(g["alpha"]) + list(g["beta"]) + [float(g["g"]), float(g["g2"]), float(g["dg2dg"])])
+
+        def run_scalars(c):
+            c._workspace = {}
+            dg, al, be, ls = nbody._step_scalars(c, self.nbody_a_start, self._a_end(c), self.nbody_n_steps, "bullfrog")
+            return np.array([dg] + list(al) + list(be) + list(ls))
+
         def terms(name, h, pair):
             p, m = [tables.host_tables(c, tables.LIGHTCONE_VJP) for c in pair]
-            return [float(sum(np.dot(bars[k], (p[k] - m[k]) / (2 * h)) for k in tables.LIGHTCONE_VJP if k in bars))]
+            out = [float(sum(np.dot(bars[k], (p[k] - m[k]) / (2 * h)) for k in tables.LIGHTCONE_VJP if k in bars))]
+            if sbar is not None:
+                out.append(float(np.dot(sbar, (run_scalars(pair[0]) - run_scalars(pair[1])) / (2 * h))))
+            return out
 
         return self._cosmo_fd(ctx, grads, params, rel_eps, terms)

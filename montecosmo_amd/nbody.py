@@ -898,7 +898,7 @@ def save_y(t, y, args=None):
 
 def nbody_bf(cosmo, init_mesh, pos, a0=0., a1=1., n_steps=5, paint_order: int = 2, lpt_order: int = 2,
              paint_deconv=False, grad_fd=np.inf, lap_fd=np.inf, snapshots=None, fn=save_y,
-             integrator="bullfrog", return_ctx=False, lattice_out=False):    # signature and defaults of nbody.py:967-969 (+ three keyword extras)
+             integrator="bullfrog", return_ctx=False, lattice_out=False, a_end=None):    # signature and defaults of nbody.py:967-969 (+ four keyword extras)
     """N-body simulation with the BullFrog solver (nbody.py:967-1002).
 
     `pos` must be the regular lattice (`bricks.regular_pos(mesh_shape, ptcl_shape)`, as at model.py:738) given
@@ -906,8 +906,25 @@ def nbody_bf(cosmo, init_mesh, pos, a0=0., a1=1., n_steps=5, paint_order: int = 
     diffrax's SaveAt(t1=True); with `lattice_out=True`, pos is a LatticePos (no leading axis).
     `integrator='fastpm'` selects the alpha_fpm coefficient (nbody.py:921-931).
     `return_ctx=True` also returns the context for `nbody_bf_vjp` (checkpoints are then kept).
+
+    Light cone: `a1` of shape (N,) or (N,1) (array or device tensor), one scale factor per particle as `lpt` takes its `a`.  The run goes
+    from a0 to `a_end` (default float(max(a1)); a device tensor is read back for it, so the model passes its own host value) and particle p
+    takes the Euler solution at its own growth time g_p = a2g(a1[p]): with K = n_steps, g0 = a2g(a0), dg = (a2g(a_end) - g0) / K and the step
+    states (x_i, v_i), i = 0 .. K (the checkpoints' x'_i - v_i dg/2 and v_i; state K is the end of the run),
+        s = (g_p - g0) / dg,  i = clamp(floor(s), 0, K - 1),  theta = clamp(s - i, 0, 1),  state_p = (1 - theta) state_i[p] + theta state_{i+1}[p]
+    -- diffrax's dense output (linear between step states, what `snapshots` returns) per particle (mcpm_nbody_lightcone_f32).  Particles
+    earlier than a0 take the LPT start state, later than a_end the final state: documented behaviour, not an error.  Same return shapes as
+    with a scalar a1; checkpoints are always kept.  `snapshots`, deconvolved paints and finite-difference kernels raise ValueError here.
     """
     n_steps = int(n_steps)
+    lc = (a1.numel() > 1) if isinstance(a1, torch.Tensor) else (np.ndim(a1) > 0 and np.size(a1) > 1)
+    a_lc = a1 if lc else None
+    if lc:
+        if a_end is None:
+            a_end = float(a1.max()) if isinstance(a1, torch.Tensor) else float(np.max(a1))
+        a1 = float(a_end)
+    elif a_end is not None:
+        raise ValueError("a_end goes with a per-particle a1 (the light cone); a scalar a1 is the end of the run itself")
     spec = _c64(init_mesh)
     mesh_shape = ch2rshape(spec.shape)
     if isinstance(pos, LatticePos):
@@ -922,6 +939,24 @@ def nbody_bf(cosmo, init_mesh, pos, a0=0., a1=1., n_steps=5, paint_order: int = 
     dg, alphas, betas, lpt_s = _step_scalars(cosmo, a0, a1, n_steps, integrator)
     N = plan.N
     want_snaps = not (snapshots is None or (isinstance(snapshots, int) and snapshots <= 1))
+    g_p = None
+    if lc:
+        if want_snaps:
+            raise ValueError("nbody_bf: snapshots are whole-box times; with a per-particle a1 every particle already has its own time")
+        if paint_deconv or grad_fd != np.inf or lap_fd != np.inf:
+            raise ValueError("nbody_bf: the light cone (per-particle a1) is built for the fused loop only: "
+                             "paint_deconv=False, grad_fd=lap_fd=inf")
+        if dg == 0.0 or not np.isfinite(dg):
+            raise ValueError("nbody_bf: the light cone needs a run of non-zero length (a0 != a_end)")
+        if isinstance(a_lc, torch.Tensor) and a_lc.is_cuda:
+            if a_lc.numel() != N:
+                raise ValueError(f"a1 must be a scalar or have one entry per particle ({N}), got {a_lc.numel()}")
+            g_p = growth_dev(cosmo, a_lc, "g")
+        else:
+            a_host = np.asarray(a_lc.cpu() if isinstance(a_lc, torch.Tensor) else a_lc, dtype=np.float64).reshape(-1)
+            if a_host.size != N:
+                raise ValueError(f"a1 must be a scalar or have one entry per particle ({N}), got {a_host.size}")
+            g_p = _f32(a2g(cosmo, a_host))
     if paint_deconv or grad_fd != np.inf or lap_fd != np.inf:
         # The options the model never selects on this branch (model.py:771-773; nbody.py:590-593 deconvolved paint, :125-163
         # finite-difference kernels): one pm_forces call per step (paint -> R2C -> FD / deconvolved k-space kernel -> 3 C2R ->
@@ -956,7 +991,7 @@ def nbody_bf(cosmo, init_mesh, pos, a0=0., a1=1., n_steps=5, paint_order: int = 
     x = torch.empty((N, 3), dtype=torch.float32, device=spec.device)
     v = torch.empty((N, 3), dtype=torch.float32, device=spec.device)
     ckpt = None
-    if return_ctx or want_snaps:
+    if return_ctx or want_snaps or lc:
         nck = plan.call("mcpm_nbody_ckpt_floats", n_steps, lpt_order)
         ckpt = torch.empty((nck,), dtype=torch.float32, device=spec.device)
         if not getattr(plan, "_pitch_probed", False):
@@ -972,6 +1007,10 @@ def nbody_bf(cosmo, init_mesh, pos, a0=0., a1=1., n_steps=5, paint_order: int = 
     plan.call("mcpm_plan_particle_pitch", C.byref(pitch))
     pitch = int(pitch.value)
     plan.call("mcpm_nbody_bf_f32", spec, n_steps, alphas, betas, float(dg), lpt_s, int(lpt_order), int(paint_order), x, v, ckpt)
+    xK, vK = x, v
+    if lc:      # every particle at its own time: one streaming pass over the checkpoints just written
+        x, v = torch.empty_like(xK), torch.empty_like(vK)
+        plan.call("mcpm_nbody_lightcone_f32", ckpt, n_steps, float(dg), float(lpt_s[0]), xK, vK, g_p, x, v)
     lp = LatticePos(x, mesh_shape, ptcl_shape)
     if want_snaps:
         if lattice_out:
@@ -983,7 +1022,8 @@ def nbody_bf(cosmo, init_mesh, pos, a0=0., a1=1., n_steps=5, paint_order: int = 
         out = _apply_fn(fn, out, lattice_out)
     if return_ctx:
         return out, NbodyCtx(plan=plan, init_mesh=spec, n_steps=n_steps, dg=dg, alphas=alphas, betas=betas, lpt_s=lpt_s, lpt_order=int(lpt_order),
-                             paint_order=int(paint_order), ckpt=ckpt, cosmo=cosmo, a0=a0, a1=a1, integrator=integrator, pitch=pitch)
+                             paint_order=int(paint_order), ckpt=ckpt, cosmo=cosmo, a0=a0, a1=a1, integrator=integrator, pitch=pitch,
+                             g_p=g_p, final=(xK, vK) if lc else None)
     return out
 
 
@@ -1069,7 +1109,10 @@ def nbody_bf_vjp(ctx, pos_bar, vel_bar):
     """Reverse sweep of nbody_bf.  `pos_bar`, `vel_bar`: cotangents of the final (pos, vel), shape (N,3) or
     (1,N,3).  Returns (init_mesh_bar, scalar_bars): init_mesh_bar is a complex64 half-spectrum in the
     real-pair convention dL = Re(sum(conj(bar) * d init_mesh)) (the conjugate of jax.grad's); scalar_bars is a
-    dict of float64 cotangents of the host scalars (alpha_i, beta_i per step, and the LPT growth scalars)."""
+    dict of float64 cotangents of the host scalars (alpha_i, beta_i per step, and the LPT growth scalars).
+    Light cone (a context of `nbody_bf` with a per-particle a1): the cotangents are those of the light-cone state; scalar_bars also has
+    'g_lc', a float32 device tensor (N,) with the cotangent of a2g(a1[p]) (zero for the particles clamped to the start or the end), and
+    'g' / 'dg' include the dependence of the interpolation weights on a2g(a0) and on the step (mcpm_nbody_bf_lc_vjp_f32)."""
     plan, n = ctx.plan, ctx.n_steps
     xb = _f32(pos_bar).reshape(-1, 3)
     vb = _f32(vel_bar).reshape(-1, 3)
@@ -1080,10 +1123,18 @@ def nbody_bf_vjp(ctx, pos_bar, vel_bar):
     out = torch.empty(tuple(ctx.init_mesh.shape), dtype=torch.complex64, device=xb.device)
     sb = np.zeros(2 * n + 4)
     plan.call("mcpm_plan_set_particle_pitch", 0 if ctx.pitch == 3 * plan.N else ctx.pitch)      # the layout this checkpoint was written in
-    plan.call("mcpm_nbody_bf_vjp_f32", ctx.init_mesh, n, ctx.alphas, ctx.betas, float(ctx.dg), ctx.lpt_s, ctx.lpt_order, ctx.paint_order,
-              ctx.ckpt, xb, vb, out, sb)
+    g_lc = None
+    if getattr(ctx, "g_p", None) is not None:
+        g_lc = torch.empty((plan.N,), dtype=torch.float32, device=xb.device)
+        plan.call("mcpm_nbody_bf_lc_vjp_f32", ctx.init_mesh, n, ctx.alphas, ctx.betas, float(ctx.dg), float(ctx.lpt_s[0]), ctx.lpt_s, ctx.lpt_order,
+                  ctx.paint_order, ctx.ckpt, ctx.final[0], ctx.final[1], ctx.g_p, xb, vb, out, g_lc, sb)
+    else:
+        plan.call("mcpm_nbody_bf_vjp_f32", ctx.init_mesh, n, ctx.alphas, ctx.betas, float(ctx.dg), ctx.lpt_s, ctx.lpt_order, ctx.paint_order,
+                  ctx.ckpt, xb, vb, out, sb)
     bars = {"alpha": sb[:n].copy(), "beta": sb[n:2 * n].copy(), "g": sb[2 * n], "g2": sb[2 * n + 1], "dg2dg": sb[2 * n + 2],
             "dg": sb[2 * n + 3]}
+    if g_lc is not None:
+        bars["g_lc"] = g_lc
     return out, bars
 
 
@@ -1092,7 +1143,9 @@ def cosmo_vjp(ctx, scalar_bars, params=("Omega_c",), rel_eps=1e-5):
     parameters: dL/dtheta = sum_i alpha_bar_i dalpha_i/dtheta + beta_bar_i dbeta_i/dtheta + dg_bar ddg/dtheta
     + g_bar dg(a0)/dtheta + g2_bar dg2(a0)/dtheta + dg2dg_bar d(dg2dg)(a0)/dtheta, with the Jacobian of the
     (128-point RK4) tables taken by central finite differences (nbody.py:679-808, :907-931 are host scalars).
-    `params` are attribute names of the cosmology object (e.g. 'Omega_c', 'Omega_b', 'w0')."""
+    `params` are attribute names of the cosmology object (e.g. 'Omega_c', 'Omega_b', 'w0').
+    Light-cone context: the scalars are those of the run to the `a_end` the context records (ctx.a1), held fixed; the per-particle
+    cotangent 'g_lc' is left to the caller, as `lpt_vjp` leaves its per-particle cotangents to the model."""
     out = {}
     for name in params:
         h, pair = tables.fd_pair(ctx.cosmo, name, rel_eps)
