@@ -772,6 +772,28 @@ int mcpm_binned_sums_f32(void *stream, int64_t n, const void *values, int values
                          const float *t1, int64_t stride1, double scale, const unsigned char *mask, int batch, const double *edges,
                          int n_edges, void *work, int64_t work_bytes, double *out);
 
+/* Binned bispectrum, the FFT (Scoccimarro) estimator (montecosmo_amd/metrics.py:bispectrum, bispectrum.hip): with F_b the inverse
+   transform of the half-spectrum whose modes outside k bin b are zero, S_ijl = sum over cells of F_i F_j F_l.  Two passes around the
+   caller's batched mcpm_fft_c2r of batch * n_bins spectra.  No plan: `stream` is a hipStream_t.
+
+   split: spec = complex64 [batch][nx][ny][nz/2+1] (nz even; rows `stride` complex elements apart, 0 = the same spectrum for every
+     row), or NULL = the unit spectrum (deconv is then ignored).  Host float64 inputs as for mcpm_spectrum_bins_c64: ktab, deconv (or
+     NULL), edges[n_edges] finite and strictly increasing (MCPM_E_ARG otherwise), 2 <= n_edges <= MCPM_BISPECTRUM_MAX_BINS + 1.  A mode
+     goes to the bin mcpm_spectrum_bins_c64 puts it in.  out (device, every element WRITTEN): complex64 [batch][n_edges-1][nx][ny]
+     [nz/2+1], the mode times its deconvolution factor in its bin's spectrum and zero in the others.  The call synchronises `stream`.
+   sums: fields = float [batch][n_bins][n_cells]; tri = DEVICE int [n_tri][3] of bin indices in 0 .. n_bins-1 (indices outside are
+     clamped), 1 <= n_tri <= MCPM_BISPECTRUM_MAX_TRIANGLES.  out (device, OVERWRITTEN): float64 [batch][n_tri], out[b][t] = sum over
+     cells of (F_i F_j) F_l of row b formed and added in float64.  Bitwise reproducible; a batch row equals the single call (the
+     decomposition follows from n_cells, n_bins and n_tri only).  `work` (device, work_bytes >= mcpm_bispectrum_workspace(...)) is
+     the caller's. */
+#define MCPM_BISPECTRUM_MAX_BINS 32
+#define MCPM_BISPECTRUM_MAX_TRIANGLES 8192
+int mcpm_bispectrum_workspace(int nx, int ny, int nz, int n_bins, int n_tri, int batch, int64_t *bytes);
+int mcpm_bispectrum_split_c64(void *stream, int nx, int ny, int nz, const float *spec, int64_t stride, int batch, const double *ktab,
+                              const double *deconv, const double *edges, int n_edges, float *out);
+int mcpm_bispectrum_sums_f32(void *stream, const float *fields, int64_t n_cells, int n_bins, int batch, const int *tri, int n_tri,
+                             void *work, int64_t work_bytes, double *out);
+
 /* ---- catalogue -> register (montecosmo/model.py:1287-1362 register_catalog, bricks.py:882-1103; catalog.hip) -----------------
    Per-object passes over a galaxy catalogue (ra, dec in degrees, z: DEVICE float64 arrays of length n) or a simulation box, and
    the reductions around them.  The plan lends its stream and reduction scratch (and, for the footprint, its mesh shape).  atab

@@ -199,6 +199,10 @@ SIGNATURES = {
     "mcpm_binned_workspace": (C.c_int, [C.c_int64, C.c_int, C.c_int, C.POINTER(C.c_int64)]),
     "mcpm_binned_sums_f32": (C.c_int, [C.c_void_p, C.c_int64, _realp, C.c_int, _f32p, C.c_int64, _f32p, C.c_int64, C.c_double, _u8p, C.c_int,
                                        _f64p, C.c_int, _u8p, C.c_int64, _d64p]),
+    "mcpm_bispectrum_workspace": (C.c_int, [C.c_int] * 6 + [C.POINTER(C.c_int64)]),
+    "mcpm_bispectrum_split_c64": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, _f32p, C.c_int64, C.c_int, _f64p, _f64p, _f64p, C.c_int,
+                                            _f32p]),
+    "mcpm_bispectrum_sums_f32": (C.c_int, [C.c_void_p, _f32p, C.c_int64, C.c_int, C.c_int, _u32p, C.c_int, _u8p, C.c_int64, _d64p]),
     "mcpm_sky2cart_minmax_f64": (C.c_int, [_plan, _d64p, _d64p, _d64p, C.c_int64, _d64p, _d64p, C.c_int, _d64p, _d64p, _d64p]),
     "mcpm_sky2cell_f32": (C.c_int, [_plan, _d64p, _d64p, _d64p, C.c_int64, _d64p, _d64p, C.c_int, _f64p, _f64p, _f32p, _f32p]),
     "mcpm_box2cell_f32": (C.c_int, [_plan, _realp, _realp, C.c_int, C.c_int64, _f64p, _f64p, C.c_double, _f32p]),

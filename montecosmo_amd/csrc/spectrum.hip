@@ -13,12 +13,12 @@
 //
 // Bin assignment is np.digitize(|k|, edges) (right=False) restated exactly: |k|^2 = (kx^2 + ky^2) + kz^2 and mu = ((kx lx + ky ly) +
 // kz lz) / |k| with contraction OFF (hipcc would fuse them into v_fmac_f64 and move modes that sit on an edge), a correctly rounded
-// sqrt and division.  The bin comes from a lookup table over a uniform grid of [e_0, e_last) (a lower bound of the count of edges
-// <= |k|) and a short forward walk over the edges.
+// sqrt and division.  The bin itself comes from kbin_dev.h (shared with bispectrum.hip).
 #include <algorithm>
 #include <cmath>
 
 #include "mcpm_internal.h"
+#include "kbin_dev.h"
 #include "reduce_dev.h"
 
 namespace {
@@ -33,10 +33,8 @@ struct SpecArgs {
     const double *kx, *ky, *kz;         // per-axis |k| tables (caller's units)
     const double *dc0, *dc1;            // per-axis deconvolution factors [nx | ny | nzh] per input, or NULL
     const double *dz0, *dz1;            // their kz parts (dc + nx + ny)
-    const double *edges;                // [n_edges]
-    const int *lut;                     // [nlut]: count of edges <= e_0 + c * lut_w
-    double lut_inv, lut_w;
-    int nlut, n_edges, n_bins;
+    KBinTable kb;                       // edges [n_edges] and their lookup table
+    int n_bins;
     double los[3];
     unsigned long long ells;            // 4 bits per multipole, in request order
     int n_ells, lmax, two;
@@ -80,17 +78,6 @@ __device__ __forceinline__ double legendre(double mu, int l) {
         p1 = p2;
     }
     return p1;
-}
-
-__device__ __forceinline__ int digitize(const SpecArgs &a, double k) {
-    // count of edges <= k (np.digitize, right=False); 0 and n_edges are dropped by the caller
-    if (!(k >= a.edges[0])) return 0;
-    if (k >= a.edges[a.n_edges - 1]) return a.n_edges;
-    int c = (int)((k - a.edges[0]) * a.lut_inv) - 1;     // one cell below: e_0 + c * w <= k despite the rounding of c
-    c = min(max(c, 0), a.nlut - 1);
-    int b = a.lut[c];
-    while (b < a.n_edges && a.edges[b] <= k) ++b;
-    return b;
 }
 
 template <bool TWO>
@@ -158,7 +145,7 @@ __global__ __launch_bounds__(64 * SPEC_WAVES) void spectrum_bins_kernel(SpecArgs
             }
             const double k = __dsqrt_rn(k2);
             const double mu = k == 0. ? 0. : __ddiv_rn(mu_num, k);
-            int key = in ? digitize(a, k) - 1 : -1;                 // bin index, or -1: dropped
+            int key = in ? digitize(a.kb, k) - 1 : -1;                 // bin index, or -1: dropped
             if (key >= a.n_bins) key = -1;
             const int tk = key >= t0 && key < t0 + nbt ? key - t0 : -1;   // bin within this tile
             // segments: lanes with equal tk are contiguous (|k| non-decreasing along the row)
@@ -231,20 +218,6 @@ __global__ __launch_bounds__(256) void spectrum_fold2_kernel(const double *__res
     out[(size_t)b * nout + o] = t;
 }
 
-// count of edges <= e_0 + c * w, by bisection
-__global__ __launch_bounds__(256) void spectrum_lut_kernel(const double *__restrict__ edges, int n_edges, double w, int nlut, int *lut) {
-    const int c = blockIdx.x * 256 + threadIdx.x;
-    if (c >= nlut) return;
-    const double x = edges[0] + c * w;
-    int lo = 0, hi = n_edges;      // answer in [lo, hi]
-    while (lo < hi) {
-        const int m = (lo + hi) >> 1;
-        if (edges[m] <= x) lo = m + 1;
-        else hi = m;
-    }
-    lut[c] = lo;
-}
-
 struct SpecLayout {
     int n_acc, n_bins, bt, tiles, nlut, rows, rows_per_wave;
     unsigned nblk;
@@ -264,7 +237,7 @@ int spec_layout(int nx, int ny, int nz, int n_edges, int n_ells, int two, int ba
     L->n_bins = n_edges - 1;
     L->bt = std::min(L->n_bins, SPEC_LDS_DOUBLES / (SPEC_WAVES * L->n_acc));
     L->tiles = (L->n_bins + L->bt - 1) / L->bt;
-    L->nlut = std::min(4 * n_edges, 16384);
+    L->nlut = kbin_nlut(n_edges);
     L->rows = nx * ny;
     const int64_t nout = (int64_t)L->n_acc * L->n_bins;
     // workgroups: enough to fill the chip, fewer when the partials would pass 32 MB per spectrum
@@ -337,12 +310,12 @@ int mcpm_spectrum_bins_c64(void *stream, int nx, int ny, int nz, const float *sp
     a.dc1 = deconv1 && two ? tab + 2 * nk : nullptr;
     a.dz0 = a.dc0 ? a.dc0 + nx + ny : nullptr;
     a.dz1 = a.dc1 ? a.dc1 + nx + ny : nullptr;
-    a.edges = tab + 3 * nk;
-    a.lut = (const int *)(ws + L.off_lut);
-    a.nlut = L.nlut;
-    a.lut_w = (edges[n_edges - 1] - edges[0]) / L.nlut;
-    a.lut_inv = 1. / a.lut_w;
-    a.n_edges = n_edges;
+    a.kb.edges = tab + 3 * nk;
+    a.kb.lut = (const int *)(ws + L.off_lut);
+    a.kb.nlut = L.nlut;
+    a.kb.lut_w = (edges[n_edges - 1] - edges[0]) / L.nlut;
+    a.kb.lut_inv = 1. / a.kb.lut_w;
+    a.kb.n_edges = n_edges;
     a.n_bins = L.n_bins;
     for (int i = 0; i < 3; ++i) a.los[i] = los[i];
     for (int j = 0; j < n_ells; ++j) a.ells |= (unsigned long long)ells[j] << (4 * j);
@@ -360,8 +333,8 @@ int mcpm_spectrum_bins_c64(void *stream, int nx, int ny, int nz, const float *sp
     a.nblk = L.nblk;
     a.P = (double *)(ws + L.off_P);
 
-    spectrum_lut_kernel<<<(L.nlut + 255) / 256, 256, 0, s>>>(a.edges, n_edges, a.lut_w, L.nlut, (int *)(ws + L.off_lut));
-    MCPM_LAUNCH_CHECK(nullptr, "spectrum_lut_kernel");
+    kbin_lut_kernel<<<(L.nlut + 255) / 256, 256, 0, s>>>(a.kb.edges, n_edges, a.kb.lut_w, L.nlut, (int *)(ws + L.off_lut));
+    MCPM_LAUNCH_CHECK(nullptr, "kbin_lut_kernel");
     const dim3 grid(L.nblk, batch, L.tiles);
     const size_t lds = (size_t)SPEC_WAVES * L.n_acc * L.bt * 8;
     if (two)

@@ -10,6 +10,12 @@ in one pass over the spectra (both autos and the cross spectrum of `powtranscoh`
 batch axis on `mesh1` (and on `mesh0` for `spectrum`) replaces the reference's `nvmap` over chains; batches go to the
 device in chunks of bounded memory.  Outputs are float64 numpy arrays; empty bins are NaN, as 0/0 is in the reference.
 
+    tri, kmean, ntri, bk = metrics.bispectrum(mesh, box_size=box)      # every closed triangle of the default bins
+
+is the first statistic beyond the power spectrum (the reference lists 'bispec' as still to do): the FFT estimator, one shell field per
+k bin (`mcpm_bispectrum_split_c64`, the batched `mcpm_fft_c2r`) and one sum over cells per triangle of bins (`mcpm_bispectrum_sums_f32`,
+csrc/bispectrum.hip), bitwise reproducibly, with the same bins and the same batch axis as `spectrum`.
+
 The real-space half of the module (montecosmo/metrics.py:214-313, :545-553) bins cells by a per-cell value instead of |k|:
 
     rcount, rmean, mse = metrics.mse_radius(truth, posterior_meshes, rmesh, cell_length)      # by distance, default shells
@@ -33,9 +39,11 @@ from .utils import safe_div, ch2rshape
 
 MAX_EDGES = 4096               # MCPM_SPECTRUM_MAX_EDGES
 CHUNK_BYTES = 1 << 32          # device memory a batch chunk may take (spectra, real staging, workspace)
+MAX_BISPEC_BINS = 32           # MCPM_BISPECTRUM_MAX_BINS
+MAX_TRIANGLES = 8192           # MCPM_BISPECTRUM_MAX_TRIANGLES
 
-__all__ = ["spectrum", "transfer", "coherence", "powtranscoh", "bin_and_aggregate", "mse_radius", "mse_value", "mse_wave", "distr_radial",
-           "multi_ess", "multi_gr", "harmean", "geomean", "MAX_EDGES"]
+__all__ = ["spectrum", "transfer", "coherence", "powtranscoh", "bispectrum", "bin_and_aggregate", "mse_radius", "mse_value", "mse_wave",
+           "distr_radial", "multi_ess", "multi_gr", "harmean", "geomean", "MAX_EDGES", "MAX_BISPEC_BINS", "MAX_TRIANGLES"]
 
 
 # ------------------------------------------------------------------------------------------------
@@ -242,6 +250,172 @@ def powtranscoh(mesh0, mesh1, box_size, kedges: int | float | list = None, inclu
     """(k, pow1, (pow1 / pow0)^.5, pow01 / (pow0 pow1)^.5) from one pass over both meshes."""
     ks, pow0, pow1, pow01 = _pow3(mesh0, mesh1, box_size, kedges, include_corners)
     return ks, pow1, (pow1 / pow0) ** .5, pow01 / (pow0 * pow1) ** .5
+
+
+# ------------------------------------------------------------------------------------------------
+# binned bispectrum (not in the reference: montecosmo/model.py:60 lists 'bispec' as the observable still to do)
+def _bispec_edges(mesh_shape, box_size, kedges=None):
+    """Bin edges of `bispectrum`: None, an int, a float or a list, read as `_kedges` reads them, except that the int / float / None
+    cases stop at kmax = (2/3) pi min(mesh_shape / box_size), below which no aliased triangle closes, and that None spaces the edges
+    by three fundamentals, 3 * 2 pi / min(box_size)."""
+    mesh_shape = np.asarray(mesh_shape)
+    box_size = np.asarray(box_size, dtype=np.float64)
+    if isinstance(kedges, (bool, np.bool_)):
+        raise ValueError("edges must be None, an int, a float or a list")
+    if isinstance(kedges, (type(None), int, float, np.integer, np.floating)):
+        kmin = 0.
+        kmax = 2. / 3. * np.pi * (mesh_shape / box_size).min()
+        if kedges is None:
+            n_kedges = max(int((kmax - kmin) / (3 * 2 * np.pi / box_size.min())), 1)
+        elif isinstance(kedges, (int, np.integer)):
+            n_kedges = int(kedges)
+        else:
+            n_kedges = max(int((kmax - kmin) / float(kedges)), 1)
+        if not 2 <= n_kedges <= MAX_BISPEC_BINS + 1:
+            raise ValueError(f"1 .. {MAX_BISPEC_BINS} bins (2 .. {MAX_BISPEC_BINS + 1} edges), got {n_kedges} edges: pass kedges")
+        dk = (kmax - kmin) / n_kedges
+        kedges = np.linspace(kmin, kmax, n_kedges, endpoint=False)
+        kedges += dk / 2
+    kedges = np.asarray(kedges, dtype=np.float64).reshape(-1)
+    if not 2 <= len(kedges) <= MAX_BISPEC_BINS + 1:
+        raise ValueError(f"1 .. {MAX_BISPEC_BINS} bins (2 .. {MAX_BISPEC_BINS + 1} edges), got {len(kedges)} edges")
+    if not np.all(np.isfinite(kedges)) or not np.all(np.diff(kedges) > 0):
+        raise ValueError("bin edges must be finite and strictly increasing")
+    return kedges
+
+
+def _bispec_triangles(edges, triangles=None):
+    """(T, 3) int64 bin triples in the caller's row order.  None: every i <= j <= l with edges[l] < edges[i+1] + edges[j+1], the bins
+    between which a closed triangle k1 + k2 + k3 = 0 can exist."""
+    n_bins = len(edges) - 1
+    if triangles is None:
+        tri = np.array([(i, j, l) for i in range(n_bins) for j in range(i, n_bins) for l in range(j, n_bins)
+                        if edges[l] < edges[i + 1] + edges[j + 1]], dtype=np.int64).reshape(-1, 3)
+    else:
+        tri = np.asarray(triangles)
+        if tri.ndim != 2 or tri.shape[1] != 3 or not np.issubdtype(tri.dtype, np.integer):
+            raise ValueError(f"triangles must be an integer array of shape (T, 3), got {tri.dtype} {tri.shape}")
+        tri = tri.astype(np.int64)
+    if not 1 <= len(tri) <= MAX_TRIANGLES:
+        raise ValueError(f"1 .. {MAX_TRIANGLES} triangles, got {len(tri)}")
+    if tri.min() < 0 or tri.max() >= n_bins:
+        raise ValueError(f"triangle bin indices must be in 0 .. {n_bins - 1}")
+    return tri
+
+
+def _bispec_spec(t, real, shape, dev):
+    """_to_spec, one row per transform, so that a row's spectrum has the bits of its single call whatever the batch; a real view that does
+    not start on a 16-byte boundary is copied first (the transforms load vectors)."""
+    if not real:
+        return _to_spec(t, real, shape, dev)
+    t = t.to(device=dev, dtype=torch.float32).contiguous()
+    if t.data_ptr() % 16:
+        t = t.clone()
+    out = torch.empty((t.shape[0],) + tuple(nbody.r2chshape(shape)), dtype=torch.complex64, device=dev)
+    plan = nbody.get_plan(shape)
+    for r in range(t.shape[0]):
+        plan.call("mcpm_fft_r2c", t[r], out[r], 1)
+    return out
+
+
+def _shell_spectra(rows, real, shape, dev, ktab, dc, edges):
+    """complex64 [b, n_bins, nx, ny, nz/2+1]: the (deconvolved) half-spectrum of every row of `rows` (None: the unit spectrum, one row)
+    split by k bin, zero outside the bin."""
+    nx, ny, nz = shape
+    n_bins, mh = len(edges) - 1, nx * ny * (nz // 2 + 1)
+    spec = None if rows is None else _bispec_spec(rows, real, shape, dev)
+    b = 1 if spec is None else int(spec.shape[0])
+    stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+    shells = torch.empty((b, n_bins, nx, ny, nz // 2 + 1), dtype=torch.complex64, device=dev)
+    _lib.call("mcpm_bispectrum_split_c64", stream, nx, ny, nz, spec, mh if spec is not None else 0, b, ktab, dc, edges, len(edges), shells)
+    return shells
+
+
+def _shell_fields(rows, real, shape, dev, ktab, dc, edges):
+    """float32 [b, n_bins, nx, ny, nz]: F_bin(x) of every row of `rows` (None: I_bin(x), of the unit spectrum, one row): the shell
+    split and, per row, one unnormalised C2R of its n_bins spectra (the same transform whatever the batch: a row keeps its bits)."""
+    shells = _shell_spectra(rows, real, shape, dev, ktab, dc, edges)
+    fields = torch.empty(tuple(shells.shape[:2]) + tuple(shape), dtype=torch.float32, device=dev)
+    plan = nbody.get_plan(shape)
+    for r in range(shells.shape[0]):
+        plan.call("mcpm_fft_c2r", shells[r], fields[r], int(shells.shape[1]))
+    return fields
+
+
+def _triple_sums(t, real, shape, ktab, dc, edges, tri_sorted):
+    """float64 [B, T]: sum over cells of F_i F_j F_l for every row of t (None: of I_i I_j I_l, one row), in chunks of bounded memory."""
+    dev = nbody._device()
+    nx, ny, nz = shape
+    n_bins, n_tri, m, mh = len(edges) - 1, len(tri_sorted), nx * ny * nz, nx * ny * (nz // 2 + 1)
+    batch = 1 if t is None else int(t.shape[0])
+    ws1 = C.c_int64()
+    _lib.call("mcpm_bispectrum_workspace", nx, ny, nz, n_bins, n_tri, 1, C.byref(ws1))
+    per_row = ws1.value + (n_bins + 1) * (8 * mh + 4 * m)
+    chunk = int(max(1, min(batch, CHUNK_BYTES // per_row)))
+    tri_dev = torch.from_numpy(np.ascontiguousarray(tri_sorted, dtype=np.int32)).to(dev)
+    stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+    out = np.zeros((batch, n_tri), dtype=np.float64)
+    for lo in range(0, batch, chunk):
+        hi = min(lo + chunk, batch)
+        fields = _shell_fields(None if t is None else t[lo:hi], real, shape, dev, ktab, dc, edges)
+        ws = C.c_int64()
+        _lib.call("mcpm_bispectrum_workspace", nx, ny, nz, n_bins, n_tri, hi - lo, C.byref(ws))
+        work = torch.empty(ws.value, dtype=torch.uint8, device=dev)
+        res = torch.empty((hi - lo, n_tri), dtype=torch.float64, device=dev)
+        _lib.call("mcpm_bispectrum_sums_f32", stream, fields, m, n_bins, hi - lo, tri_dev, n_tri, work, ws.value, res)
+        out[lo:hi] = res.cpu().numpy()
+    return out
+
+
+_NTRI_CACHE = {}      # (mesh_shape, box_size, edges, sorted triangles) -> ntri; the few most recent geometries
+_NTRI_CACHE_SIZE = 8
+
+
+def bispectrum(mesh, box_size=None, kedges: int | float | list = None, triangles=None, deconv: int = 0, reduced=False):
+    """Binned bispectrum of a mesh, the FFT (Scoccimarro) estimator: (tri, kmean, ntri, bk), with qk appended when `reduced`.
+
+    With d = rfftn(mesh) (unnormalised, divided by the paint window of order `deconv`), bins kedges[b] <= |k| < kedges[b+1] as in
+    `spectrum`, F_b(x) = sum_{k in bin b} d(k) e^{ikx} and I_b the same with d = 1, a triangle of bins (i, j, l) has
+    S = sum_x F_i F_j F_l, ntri = sum_x I_i I_j I_l / M and bk = (V^2 / M^3) (S / M) / ntri (M cells, V = prod box_size).  ntri counts the
+    ordered mode triples k1 + k2 + k3 = 0 with k1 in i, k2 in j, k3 in l, where the sum closes MODULO THE MESH: the default edges stop
+    at 2/3 of the Nyquist wavenumber, below which no aliased triple closes; edges given by the caller may go further, and triangles that
+    reach past 2/3 Nyquist then count aliased triples as well.  ntri is measured through the same float32 transforms as S, so it is an
+    integer to about 1e-6 of sum_x |I_i I_j I_l| / M only; a triangle whose bins hold no mode has ntri = 0 exactly and bk = NaN.
+
+    mesh: a real mesh or a complex64 half-spectrum (Hermitian, as rfftn of a real mesh is), numpy or torch, with an optional leading
+    batch axis, which `bk` and `qk` then carry.  kedges: see `_bispec_edges`; at most MAX_BISPEC_BINS bins.  triangles: None (every
+    i <= j <= l that can close) or an integer array (T, 3) of bin indices in any order, repeats allowed, T <= MAX_TRIANGLES; outputs
+    follow its row order, and the order inside a row does not change a bit of the result.  tri (T, 3), kmean (n_bins,), ntri (T,),
+    bk ([B,] T), qk = bk / (P_i P_j + P_j P_l + P_l P_i) with P the binned power of the same mesh: float64 numpy arrays."""
+    t, real, batched, shape = _prepare(mesh)
+    box_size = np.asarray(shape, dtype=np.float64) if box_size is None else np.asarray(box_size, dtype=np.float64)
+    edges = _bispec_edges(shape, box_size, kedges)
+    tri = _bispec_triangles(edges, triangles)
+    if not isinstance(deconv, (int, np.integer)) or deconv < 0:
+        raise ValueError(f"deconv must be a non-negative int, got {deconv!r}")
+    tri_sorted = np.sort(tri, axis=1)
+    ktab = _ktable(shape, box_size)
+    dc = _deconv_table(shape, int(deconv))
+    m, vol = float(np.prod(shape)), float(box_size.prod())
+
+    key = (shape, box_size.tobytes(), edges.tobytes(), tri_sorted.tobytes())
+    ntri = _NTRI_CACHE.get(key)
+    if ntri is None:
+        ntri = _triple_sums(None, False, shape, ktab, None, edges, tri_sorted)[0] / m
+        while len(_NTRI_CACHE) >= _NTRI_CACHE_SIZE:
+            _NTRI_CACHE.pop(next(iter(_NTRI_CACHE)))
+        _NTRI_CACHE[key] = ntri
+    sums = _triple_sums(t, real, shape, ktab, dc, edges, tri_sorted)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        bk = (vol ** 2 / m ** 3) * (sums / m) / ntri
+    _, kmean, pk = _spectrum(t if reduced else t[:1], box_size=box_size, kedges=edges, deconv=int(deconv))
+    out = (tri, kmean[0], ntri.copy(), bk if batched else bk[0])
+    if reduced:
+        pi, pj, pl = (pk[:, tri[:, a]] for a in range(3))
+        with np.errstate(divide="ignore", invalid="ignore"):
+            qk = bk / (pi * pj + pj * pl + pl * pi)
+        out += (qk if batched else qk[0],)
+    return out
 
 
 # ------------------------------------------------------------------------------------------------

@@ -106,6 +106,22 @@ class FieldLevelForward:
             out[f"kptc_{name}"] = tuple(r.reshape((c, n) + r.shape[1:]) for r in res)
         return out
 
+    def bispectrum(self, mesh, kedges: int | float | list = None, triangles=None, deconv: int = 0, reduced=False):
+        """metrics.bispectrum with the model's box_size: (tri, kmean, ntri, bk[, qk]); a batched mesh gives batched bk and qk."""
+        return metrics.bispectrum(mesh, box_size=self.box_size, kedges=kedges, triangles=triangles, deconv=deconv, reduced=reduced)
+
+    def bispectrum_chains(self, chains, names: str | list = (), kedges: int | float | list = None, triangles=None, reduced=False):
+        """A copy of `chains` (chains.Chains) with, for every entry `name` of meshes (C, N, *mesh), the tuple `kb_<name>` =
+        (tri, kmean, ntri, bk[, qk]) of bispectrum(mesh) per draw, bk and qk of shape (C, N, T): the chain and draw axes go through the
+        batch axis of metrics.bispectrum together, as in powtranscoh_chains."""
+        out = chains.copy()
+        for name in np.atleast_1d(names):
+            x = torch.as_tensor(chains[str(name)])
+            c, n = x.shape[:2]
+            res = self.bispectrum(x.reshape((c * n,) + tuple(x.shape[2:])), kedges=kedges, triangles=triangles, reduced=reduced)
+            out[f"kb_{name}"] = res[:3] + tuple(r.reshape((c, n) + r.shape[1:]) for r in res[3:])
+        return out
+
     def mse_value(self, mesh0, mesh1, cell_length=None, vedges: int | float | list = 50, min_count=None, aggr_fn=None):
         """metrics.mse_value with the model's cell_length (model.py:1390-1394): by default 50 quantile bins of mesh0."""
         return metrics.mse_value(mesh0, mesh1, self.cell_length if cell_length is None else cell_length, vedges=vedges, min_count=min_count,
