@@ -16,8 +16,9 @@
 // thin bins are served together, step s letting the s-th lane of each add its own terms to the histogram: the lanes of a step hold
 // distinct bins, so their read-modify-writes do not meet, and a bin receives its terms in lane order.  Which way a bin goes depends on
 // the round's cells alone.  Rounds follow in program order, so every histogram cell is a fixed-order sum whichever load path ran.  The
-// four waves' histograms are added in a fixed tree, the workgroup writes its partials P[g][blk][acc][bin], and two fold kernels add
-// the workgroups in a fixed order (as spectrum.hip does).
+// four waves' histograms are added in a fixed tree, the workgroup writes its partials P[g][blk][acc][bin] (reduce_dev.h: hist4_partials),
+// and mcpm_fold_partials (reduce.hip) adds the workgroups in a fixed order, as for spectrum.hip, and scatters a group's accumulators to
+// out[2 + batch][n_bins] (fold_binned).
 //
 // The ranges depend on n and on the number of edges only.  A workgroup takes up to BIN_ROWS batch rows through the rounds together
 // (they share the bins, the ballots, the count and the sum of values); a row's own sums see the same terms in the same order whether
@@ -37,7 +38,6 @@ namespace {
 constexpr int BIN_WAVES = 4;            // waves per workgroup, one LDS histogram each
 constexpr int BIN_ROWS = 4;             // batch rows a workgroup takes together (1 when the batch has one or two rows)
 constexpr int BIN_HIST_DOUBLES = 4096;  // 32 KB of histograms per workgroup: BIN_WAVES * n_acc * bins-per-tile <= this; the edges take up to 32 KB more
-constexpr int BIN_FOLD_R = 32;          // first-level chunks of the workgroup fold
 constexpr int BIN_STEP = 256;           // cells a wave takes per step (4 per lane)
 constexpr int BIN_TREE_MIN = 16;        // lanes of a round in one bin from which the bin is tree-summed (at most 4 such bins in a round)
 
@@ -193,41 +193,7 @@ __global__ __launch_bounds__(64 * BIN_WAVES) void binned_sums_kernel(BinArgs a) 
         }
     }
     __syncthreads();
-    double *Pb = a.P + ((size_t)g * a.nblk + blk) * (size_t)a.n_acc * a.n_bins;
-    for (int i = threadIdx.x; i < a.n_acc * nbt; i += blockDim.x) {
-        const int acc = i / nbt, j = i - acc * nbt;
-        const int o = acc * a.bt + j;
-        Pb[(size_t)acc * a.n_bins + tile0 + j] = (hist[o] + hist[hsz + o]) + (hist[2 * hsz + o] + hist[3 * hsz + o]);
-    }
-}
-
-// First level of the workgroup fold: Q[g][r][o] = sum over workgroups [r C, (r + 1) C) of P[g][blk][o], in order.
-__global__ __launch_bounds__(256) void binned_fold_kernel(const double *__restrict__ P, unsigned nblk, int nout, double *__restrict__ Q) {
-    const int o = blockIdx.x * 256 + threadIdx.x, r = blockIdx.y, g = blockIdx.z;
-    if (o >= nout) return;
-    const unsigned C = (nblk + BIN_FOLD_R - 1) / BIN_FOLD_R, lo = r * C, hi = min(lo + C, nblk);
-    const double *Pg = P + (size_t)g * nblk * nout + o;
-    double t = 0.;
-    for (unsigned i = lo; i < hi; ++i) t += Pg[(size_t)i * nout];
-    Q[((size_t)g * BIN_FOLD_R + r) * nout + o] = t;
-}
-
-// Second level, and the scatter of a group's accumulators to out[2 + batch][n_bins]: count and sum of values from group 0 (every group holds
-// the same bits), target row g rb + r from accumulator 2 + r.
-__global__ __launch_bounds__(256) void binned_fold2_kernel(const double *__restrict__ Q, int nout, int n_bins, int rb, int batch,
-                                                           double *__restrict__ out) {
-    const int o = blockIdx.x * 256 + threadIdx.x, g = blockIdx.y;
-    if (o >= nout) return;
-    const double *Qg = Q + (size_t)g * BIN_FOLD_R * nout + o;
-    double t = 0.;
-    for (int r = 0; r < BIN_FOLD_R; ++r) t += Qg[(size_t)r * nout];
-    const int acc = o / n_bins, j = o - acc * n_bins;
-    if (acc < 2) {
-        if (g == 0) out[(size_t)acc * n_bins + j] = t;
-    } else {
-        const int row = g * rb + acc - 2;
-        if (row < batch) out[(size_t)(2 + row) * n_bins + j] = t;
-    }
+    hist4_partials(hist, hsz, a.n_acc, a.bt, tile0, nbt, a.P, g, a.nblk, blk, a.n_bins);
 }
 
 struct BinLayout {
@@ -237,35 +203,28 @@ struct BinLayout {
     size_t off_edges, off_P, off_Q, bytes;
 };
 
-size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
-
 int bin_layout(int64_t n, int n_edges, int batch, BinLayout *L) {
     if (n < 1) return mcpm_fail(nullptr, MCPM_E_SHAPE, "mcpm_binned: need n >= 1 cells");
     if (n_edges < 2 || n_edges > MCPM_BINNED_MAX_EDGES) return mcpm_fail(nullptr, MCPM_E_ARG, "mcpm_binned: need 2 .. MCPM_BINNED_MAX_EDGES edges");
-    if (batch < 1 || batch > 65535) return mcpm_fail(nullptr, MCPM_E_ARG, "mcpm_binned: batch out of range");
+    MCPM_TRY(mcpm_check_batch("mcpm_binned", batch));
     L->rb = batch >= 3 ? BIN_ROWS : 1;
     L->groups = (batch + L->rb - 1) / L->rb;
     L->n_acc = 2 + L->rb;
     L->n_bins = n_edges - 1;
-    L->bt = std::min(L->n_bins, BIN_HIST_DOUBLES / (BIN_WAVES * L->n_acc));
-    L->tiles = (L->n_bins + L->bt - 1) / L->bt;
-    // workgroups and cell ranges from n and n_edges alone (never the batch): enough to fill the chip, fewer when a row's partials would pass 32 MB
-    int64_t nblk = std::min<int64_t>(2048, std::max<int64_t>(64, ((int64_t)1 << 22) / (3 * (int64_t)L->n_bins)));
+    mcpm_hist_tiles(L->n_bins, BIN_HIST_DOUBLES, BIN_WAVES, L->n_acc, &L->bt, &L->tiles);
+    // workgroups and cell ranges from n and n_edges alone (never the batch): fewer when a row's partials would pass 32 MB
     const int64_t per = (int64_t)BIN_WAVES * BIN_STEP;
-    nblk = std::min<int64_t>(nblk, (n + per - 1) / per);
+    const int64_t nblk = mcpm_fold_nblk((int64_t)1 << 22, 3 * (int64_t)L->n_bins, (n + per - 1) / per);
     int64_t cpw = (n + nblk * BIN_WAVES - 1) / (nblk * BIN_WAVES);
     cpw = (cpw + BIN_STEP - 1) / BIN_STEP * BIN_STEP;
     L->cells_per_wave = cpw;
     L->nblk = (unsigned)((n + cpw * BIN_WAVES - 1) / (cpw * BIN_WAVES));
-    const size_t nout = (size_t)L->n_acc * L->n_bins;
-    L->off_edges = 0;
-    L->off_P = align256((size_t)n_edges * 8);
-    L->off_Q = L->off_P + align256((size_t)L->groups * L->nblk * nout * 8);
-    L->bytes = L->off_Q + align256((size_t)L->groups * BIN_FOLD_R * nout * 8);
+    Carve c;
+    L->off_edges = c.take((size_t)n_edges * 8);
+    mcpm_fold_carve(c, L->groups, L->nblk, (size_t)L->n_acc * L->n_bins, &L->off_P, &L->off_Q);
+    L->bytes = c.bytes;
     return MCPM_OK;
 }
-
-inline bool aligned_to(const void *p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }      // (NULL counts as aligned)
 
 template <typename VT, int RB>
 void launch_bins(const BinArgs &a, const BinLayout &L, bool vec, hipStream_t s) {
@@ -297,9 +256,7 @@ int mcpm_binned_sums_f32(void *stream, int64_t n, const void *values, int values
     if (!values || !t0 || !edges || !work || !out) return mcpm_fail(nullptr, MCPM_E_ARG, "mcpm_binned_sums_f32: null pointer");
     if (work_bytes < (int64_t)L.bytes) return mcpm_fail(nullptr, MCPM_E_ARG, "mcpm_binned_sums_f32: workspace too small");
     if (stride0 < 0 || stride1 < 0) return mcpm_fail(nullptr, MCPM_E_ARG, "mcpm_binned_sums_f32: negative stride");
-    for (int i = 0; i < n_edges; ++i)
-        if (!std::isfinite(edges[i]) || (i > 0 && !(edges[i] >= edges[i - 1])))
-            return mcpm_fail(nullptr, MCPM_E_ARG, "mcpm_binned_sums_f32: edges must be finite and non-decreasing");
+    MCPM_TRY(mcpm_check_edges("mcpm_binned_sums_f32", edges, n_edges, false));
     hipStream_t s = (hipStream_t)stream;
     char *ws = (char *)work;
     double *dev_edges = (double *)(ws + L.off_edges);
@@ -325,7 +282,7 @@ int mcpm_binned_sums_f32(void *stream, int64_t n, const void *values, int values
     a.nblk = L.nblk;
     a.P = (double *)(ws + L.off_P);
     // 16-byte loads when every pointer (and every batch row) allows; the order of the sums is the same on either path
-    const bool vec = aligned_to(values, 16) && aligned_to(t0, 16) && aligned_to(t1, 16) && aligned_to(mask, 4) && stride0 % 4 == 0 && a.st1 % 4 == 0;
+    const bool vec = mcpm_aligned(values) && mcpm_aligned(t0) && mcpm_aligned(t1) && mcpm_aligned(mask, 4) && stride0 % 4 == 0 && a.st1 % 4 == 0;
     if (values_f64) {
         if (L.rb == 1) launch_bins<double, 1>(a, L, vec, s);
         else launch_bins<double, BIN_ROWS>(a, L, vec, s);
@@ -334,13 +291,7 @@ int mcpm_binned_sums_f32(void *stream, int64_t n, const void *values, int values
         else launch_bins<float, BIN_ROWS>(a, L, vec, s);
     }
     MCPM_LAUNCH_CHECK(nullptr, "binned_sums_kernel");
-    const int nout = L.n_acc * L.n_bins;
-    double *Q = (double *)(ws + L.off_Q);
-    binned_fold_kernel<<<dim3((nout + 255) / 256, BIN_FOLD_R, L.groups), 256, 0, s>>>(a.P, L.nblk, nout, Q);
-    MCPM_LAUNCH_CHECK(nullptr, "binned_fold_kernel");
-    binned_fold2_kernel<<<dim3((nout + 255) / 256, L.groups), 256, 0, s>>>(Q, nout, L.n_bins, L.rb, batch, out);
-    MCPM_LAUNCH_CHECK(nullptr, "binned_fold2_kernel");
-    return MCPM_OK;
+    return mcpm_fold_partials(s, a.P, L.groups, L.nblk, L.n_acc * L.n_bins, (double *)(ws + L.off_Q), fold_binned(out, L.n_bins, L.rb, batch));
 }
 
 }  // extern "C"

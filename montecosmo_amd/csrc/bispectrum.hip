@@ -15,8 +15,8 @@
 // which stays in a register over the workgroup's contiguous range of chunks: no cross-lane reduction, no atomics, a fixed order.  A
 // workgroup holds up to BISP_RT * 256 triangles (blockIdx.y walks further tiles of the list).  With 128 triangles or fewer the lanes
 // split into 256 / tp groups (tp = T rounded up to a power of two, at least 2), group g takes the cells g, g + G, ... of every chunk,
-// and the groups are added in order at the end.  Every workgroup writes one partial per triangle; two fold kernels add the workgroups
-// up in a fixed order.  The decomposition follows from n_cells, n_bins and n_tri only, so a batch row is bitwise the single call.
+// and the groups are added in order at the end.  Every workgroup writes one partial per triangle; mcpm_fold_partials (reduce.hip) adds the
+// workgroups up in a fixed order.  The decomposition follows from n_cells, n_bins and n_tri only, so a batch row is bitwise the single call.
 #include <algorithm>
 #include <cmath>
 
@@ -30,7 +30,6 @@ constexpr int BISP_CHUNK = 128;             // cells per staged chunk (a power o
 constexpr int BISP_PITCH = BISP_CHUNK + 1;  // doubles between the rows of the staged chunk (odd); 33 KB at 32 bins, four workgroups per CU
 constexpr int BISP_RT = 4;                  // triangles per lane
 constexpr int BISP_TILE = BISP_THREADS * BISP_RT;
-constexpr int BISP_FOLD_R = 32;             // first-level chunks of the workgroup fold
 
 struct SplitArgs {
     const float2 *spec;      // [B][nx][ny][nzh], or NULL: the unit spectrum
@@ -148,26 +147,6 @@ __global__ __launch_bounds__(BISP_THREADS) void bispectrum_sums_kernel(SumsArgs 
     }
 }
 
-// First level of the workgroup fold: Q[b][r][o] = sum over workgroups [r C, (r + 1) C) of P[b][blk][o], in order.
-__global__ __launch_bounds__(256) void bispectrum_fold_kernel(const double *__restrict__ P, unsigned nblk, int nout, double *__restrict__ Q) {
-    const int o = blockIdx.x * 256 + threadIdx.x, r = blockIdx.y, b = blockIdx.z;
-    if (o >= nout) return;
-    const unsigned C = (nblk + BISP_FOLD_R - 1) / BISP_FOLD_R, lo = r * C, hi = min(lo + C, nblk);
-    const double *Pb = P + (size_t)b * nblk * nout + o;
-    double t = 0.;
-    for (unsigned i = lo; i < hi; ++i) t += Pb[(size_t)i * nout];
-    Q[((size_t)b * BISP_FOLD_R + r) * nout + o] = t;
-}
-
-__global__ __launch_bounds__(256) void bispectrum_fold2_kernel(const double *__restrict__ Q, int nout, double *__restrict__ out) {
-    const int o = blockIdx.x * 256 + threadIdx.x, b = blockIdx.y;
-    if (o >= nout) return;
-    const double *Qb = Q + (size_t)b * BISP_FOLD_R * nout + o;
-    double t = 0.;
-    for (int r = 0; r < BISP_FOLD_R; ++r) t += Qb[(size_t)r * nout];
-    out[(size_t)b * nout + o] = t;
-}
-
 struct BispLayout {
     int tp_log2, tiles;
     long long n_chunks, chunks_per_blk;
@@ -175,15 +154,13 @@ struct BispLayout {
     size_t off_P, off_Q, bytes;
 };
 
-size_t bisp_align256(size_t v) { return (v + 255) & ~(size_t)255; }
-
 // The decomposition of the sums pass: a function of n_cells, n_bins and n_tri only.
 int bisp_layout(int64_t n_cells, int n_bins, int n_tri, int batch, BispLayout *L) {
     if (n_cells < 1) return mcpm_fail(nullptr, MCPM_E_ARG, "mcpm_bispectrum: no cells");
     if (n_bins < 1 || n_bins > MCPM_BISPECTRUM_MAX_BINS) return mcpm_fail(nullptr, MCPM_E_ARG, "mcpm_bispectrum: 1 .. MCPM_BISPECTRUM_MAX_BINS bins");
     if (n_tri < 1 || n_tri > MCPM_BISPECTRUM_MAX_TRIANGLES)
         return mcpm_fail(nullptr, MCPM_E_ARG, "mcpm_bispectrum: 1 .. MCPM_BISPECTRUM_MAX_TRIANGLES triangles");
-    if (batch < 1 || batch > 65535) return mcpm_fail(nullptr, MCPM_E_ARG, "mcpm_bispectrum: batch out of range");
+    MCPM_TRY(mcpm_check_batch("mcpm_bispectrum", batch));
     L->tp_log2 = 8;
     if (n_tri <= BISP_THREADS / 2) {
         L->tp_log2 = 0;
@@ -192,14 +169,13 @@ int bisp_layout(int64_t n_cells, int n_bins, int n_tri, int batch, BispLayout *L
     }
     L->tiles = (n_tri + BISP_TILE - 1) / BISP_TILE;
     L->n_chunks = (n_cells + BISP_CHUNK - 1) / BISP_CHUNK;
-    // workgroups per tile: enough to fill the chip, fewer when the partials would pass 16 MB per batch row
-    int64_t nblk = std::min<int64_t>(2048, std::max<int64_t>(64, ((int64_t)1 << 21) / n_tri));
-    nblk = std::min<int64_t>(nblk, L->n_chunks);
+    // workgroups per tile: fewer when the partials would pass 16 MB per batch row
+    const int64_t nblk = mcpm_fold_nblk((int64_t)1 << 21, n_tri, L->n_chunks);
     L->chunks_per_blk = (L->n_chunks + nblk - 1) / nblk;
     L->nblk = (unsigned)((L->n_chunks + L->chunks_per_blk - 1) / L->chunks_per_blk);
-    L->off_P = 0;
-    L->off_Q = bisp_align256((size_t)batch * L->nblk * n_tri * 8);
-    L->bytes = L->off_Q + bisp_align256((size_t)batch * BISP_FOLD_R * n_tri * 8);
+    Carve c;
+    mcpm_fold_carve(c, batch, L->nblk, (size_t)n_tri, &L->off_P, &L->off_Q);
+    L->bytes = c.bytes;
     return MCPM_OK;
 }
 
@@ -226,22 +202,20 @@ int mcpm_bispectrum_split_c64(void *stream, int nx, int ny, int nz, const float 
     MCPM_TRY(bisp_shape(nx, ny, nz));
     if (n_edges < 2 || n_edges > MCPM_BISPECTRUM_MAX_BINS + 1)
         return mcpm_fail(nullptr, MCPM_E_ARG, "mcpm_bispectrum_split_c64: need 2 .. MCPM_BISPECTRUM_MAX_BINS + 1 edges");
-    if (batch < 1 || batch > 65535) return mcpm_fail(nullptr, MCPM_E_ARG, "mcpm_bispectrum_split_c64: batch out of range");
+    MCPM_TRY(mcpm_check_batch("mcpm_bispectrum_split_c64", batch));
     if (!ktab || !edges || !out) return mcpm_fail(nullptr, MCPM_E_ARG, "mcpm_bispectrum_split_c64: null pointer");
     if (stride < 0) return mcpm_fail(nullptr, MCPM_E_ARG, "mcpm_bispectrum_split_c64: negative stride");
-    for (int i = 0; i < n_edges; ++i)
-        if (!std::isfinite(edges[i]) || (i > 0 && !(edges[i] > edges[i - 1])))
-            return mcpm_fail(nullptr, MCPM_E_ARG, "mcpm_bispectrum_split_c64: edges must be finite and strictly increasing");
+    MCPM_TRY(mcpm_check_edges("mcpm_bispectrum_split_c64", edges, n_edges, true));
     hipStream_t s = (hipStream_t)stream;
-    const int nzh = nz / 2 + 1, nk = nx + ny + nzh, nlut = kbin_nlut(n_edges);
+    const int nzh = nz / 2 + 1, nk = nx + ny + nzh;
     // tables: k [nk], deconv [nk], edges [n_edges], then the lookup table; the call owns them and waits for the pass before it frees them
     std::vector<double> host((size_t)2 * nk + n_edges, 1.);
     std::copy(ktab, ktab + nk, host.begin());
     if (deconv) std::copy(deconv, deconv + nk, host.begin() + nk);
     std::copy(edges, edges + n_edges, host.begin() + 2 * nk);
-    const size_t off_lut = bisp_align256(host.size() * 8);
+    const size_t off_lut = align256(host.size() * 8);
     char *dev = nullptr;
-    MCPM_HIP(nullptr, hipMalloc((void **)&dev, off_lut + (size_t)nlut * 4));
+    MCPM_HIP(nullptr, hipMalloc((void **)&dev, off_lut + (size_t)kbin_nlut(n_edges) * 4));
     double *tab = (double *)dev;
     int rc = MCPM_OK;
     hipError_t e = hipMemcpyAsync(tab, host.data(), host.size() * 8, hipMemcpyHostToDevice, s);
@@ -254,19 +228,13 @@ int mcpm_bispectrum_split_c64(void *stream, int nx, int ny, int nz, const float 
         a.kz = tab + nx + ny;
         a.dc = deconv && spec ? tab + nk : nullptr;
         a.dz = a.dc ? a.dc + nx + ny : nullptr;
-        a.kb.edges = tab + 2 * nk;
-        a.kb.lut = (const int *)(dev + off_lut);
-        a.kb.nlut = nlut;
-        a.kb.lut_w = (edges[n_edges - 1] - edges[0]) / nlut;
-        a.kb.lut_inv = 1. / a.kb.lut_w;
-        a.kb.n_edges = n_edges;
         a.n_bins = n_edges - 1;
         a.nx = nx;
         a.ny = ny;
         a.nzh = nzh;
         a.mh = (long long)nx * ny * nzh;
         a.out = (float2 *)out;
-        kbin_lut_kernel<<<(nlut + 255) / 256, 256, 0, s>>>(a.kb.edges, n_edges, a.kb.lut_w, nlut, (int *)(dev + off_lut));
+        a.kb = kbin_table(edges, n_edges, tab + 2 * nk, (int *)(dev + off_lut), s);
         bispectrum_split_kernel<<<dim3((unsigned)((a.mh + 255) / 256), batch), 256, 0, s>>>(a);
         e = hipGetLastError();
         if (e == hipSuccess) e = hipStreamSynchronize(s);      // `host` and the tables die on return
@@ -298,12 +266,7 @@ int mcpm_bispectrum_sums_f32(void *stream, const float *fields, int64_t n_cells,
     const size_t lds = (size_t)n_bins * BISP_PITCH * 8;
     bispectrum_sums_kernel<<<dim3(L.nblk, L.tiles, batch), BISP_THREADS, lds, s>>>(a);
     MCPM_LAUNCH_CHECK(nullptr, "bispectrum_sums_kernel");
-    double *Q = (double *)(ws + L.off_Q);
-    bispectrum_fold_kernel<<<dim3((n_tri + 255) / 256, BISP_FOLD_R, batch), 256, 0, s>>>(a.P, L.nblk, n_tri, Q);
-    MCPM_LAUNCH_CHECK(nullptr, "bispectrum_fold_kernel");
-    bispectrum_fold2_kernel<<<dim3((n_tri + 255) / 256, batch), 256, 0, s>>>(Q, n_tri, out);
-    MCPM_LAUNCH_CHECK(nullptr, "bispectrum_fold2_kernel");
-    return MCPM_OK;
+    return mcpm_fold_partials(s, a.P, batch, L.nblk, n_tri, (double *)(ws + L.off_Q), fold_dense(out));
 }
 
 }  // extern "C"

@@ -224,8 +224,6 @@ __global__ __launch_bounds__(256) void kaiser_tables_vjp_kernel(KGeom G, LcTable
     acc_end<PASS>(A, ntot, mxbits, out, bad);
 }
 
-__host__ inline bool aligned16(const void *q) { return (reinterpret_cast<uintptr_t>(q) & 15u) == 0; }
-
 struct KArgs {
     KGeom G;
     LcTables tb;
@@ -277,7 +275,7 @@ int mcpm_kaiser_sky_f32(mcpm_plan *p, const float *meshes, const float *phi, con
     MCPM_REQUIRE(p, meshes && out, MCPM_E_ARG, "mcpm_kaiser_sky_f32: bad argument");
     KArgs a;
     MCPM_TRY(kaiser_args(p, "mcpm_kaiser_sky_f32", geom, flags, tables, nchi, ngrow, g_obs, f_obs, b1E, fNL_bp, &a));
-    a.vec = a.vec && aligned16(meshes) && aligned16(phi) && aligned16(out);
+    a.vec = a.vec && mcpm_aligned(meshes) && mcpm_aligned(phi) && mcpm_aligned(out);
     const unsigned nb = (unsigned)((a.nslot + 255) / 256);
     StageTimer st_(p, ST_LPT, (4.0 * (a.curved ? 6 : 2) + 4.0 + (phi ? 4.0 : 0.0)) * p->M);
 #define K(C, L, V) kaiser_sky_kernel<C, L, V><<<nb, 256, 0, p->stream>>>(a.G, a.tb, a.P, meshes, phi, p->M, a.nslot, out)
@@ -295,7 +293,7 @@ int mcpm_kaiser_sky_vjp_f32(mcpm_plan *p, const float *meshes, const float *phi,
     MCPM_REQUIRE(p, (phi == nullptr) == (phi_bar == nullptr), MCPM_E_ARG, "mcpm_kaiser_sky_vjp_f32: phi and phi_bar go together");
     KArgs a;
     MCPM_TRY(kaiser_args(p, "mcpm_kaiser_sky_vjp_f32", geom, flags, tables, nchi, ngrow, g_obs, f_obs, b1E, fNL_bp, &a));
-    a.vec = a.vec && aligned16(meshes) && aligned16(phi) && aligned16(out_bar) && aligned16(meshes_bar) && aligned16(phi_bar);
+    a.vec = a.vec && mcpm_aligned(meshes) && mcpm_aligned(phi) && mcpm_aligned(out_bar) && mcpm_aligned(meshes_bar) && mcpm_aligned(phi_bar);
     const unsigned nb = (unsigned)((a.nslot + 255) / 256);
     DetSum s;
     MCPM_TRY(mcpm_det_begin(p, 4, nb, &s));

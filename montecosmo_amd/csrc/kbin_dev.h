@@ -55,4 +55,18 @@ __global__ __launch_bounds__(256) void kbin_lut_kernel(const double *__restrict_
 
 inline int kbin_nlut(int n_edges) { return n_edges * 4 < 16384 ? n_edges * 4 : 16384; }
 
+// Host side: the table of the edges `edges` (host, checked by the caller; their device copy `dev_edges` is already enqueued on `s`) with its
+// lookup table in lut [kbin_nlut(n_edges)] (device), which kbin_lut_kernel fills on `s`.  The caller checks the launch.
+inline KBinTable kbin_table(const double *edges, int n_edges, const double *dev_edges, int *lut, hipStream_t s) {
+    KBinTable t;
+    t.edges = dev_edges;
+    t.lut = lut;
+    t.nlut = kbin_nlut(n_edges);
+    t.lut_w = (edges[n_edges - 1] - edges[0]) / t.nlut;
+    t.lut_inv = 1. / t.lut_w;
+    t.n_edges = n_edges;
+    kbin_lut_kernel<<<(t.nlut + 255) / 256, 256, 0, s>>>(dev_edges, n_edges, t.lut_w, t.nlut, lut);
+    return t;
+}
+
 }  // namespace

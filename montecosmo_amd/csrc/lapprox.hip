@@ -165,7 +165,6 @@ __global__ void schur_mirror_kernel(double *__restrict__ out, int m) {
     if (i < m && i < j) out[j * m + i] = out[i * m + j];
 }
 
-inline bool aligned16(const void *a) { return (reinterpret_cast<uintptr_t>(a) & 15u) == 0; }      // (NULL counts as aligned)
 inline unsigned lap_blocks(int64_t work) { return (unsigned)std::min<int64_t>((std::max<int64_t>(work, 1) + 255) / 256, LAP_MAX_BLOCKS); }
 inline unsigned lap_blocks(int64_t d, bool vec) { return lap_blocks(vec ? d >> 2 : d); }
 
@@ -177,7 +176,7 @@ int mcpm_adam_step_f32(mcpm_plan *p, float *q, float *m, float *v, const float *
                        double c1, double c2) {
     if (!p) return MCPM_E_ARG;
     MCPM_REQUIRE(p, d >= 1 && q && m && v && g, MCPM_E_ARG, "mcpm_adam_step_f32: bad argument");
-    const bool vec = aligned16(q) && aligned16(m) && aligned16(v) && aligned16(g);
+    const bool vec = mcpm_aligned(q) && mcpm_aligned(m) && mcpm_aligned(v) && mcpm_aligned(g);
     const AdamCoef a{lr, b1, b2, eps, c1, c2};
     StageTimer st_(p, ST_AXPY, 28.0 * d);
     if (vec) adam_step_kernel<true><<<lap_blocks(d, true), 256, 0, p->stream>>>(q, m, v, g, d, a);
@@ -191,7 +190,7 @@ int mcpm_probe_shift_f32(mcpm_plan *p, const float *q, int64_t d, int64_t start,
     if (!p) return MCPM_E_ARG;
     MCPM_REQUIRE(p, d >= 1 && q && 0 <= start && start <= stop && stop <= d, MCPM_E_ARG, "mcpm_probe_shift_f32: bad argument");
     if (!q_plus && !q_minus) return MCPM_OK;
-    const bool vec = aligned16(q) && aligned16(q_plus) && aligned16(q_minus);
+    const bool vec = mcpm_aligned(q) && mcpm_aligned(q_plus) && mcpm_aligned(q_minus);
     const uint64_t key = probe_key(seed, probe);
     StageTimer st_(p, ST_AXPY, (4.0 + (q_plus ? 4.0 : 0.0) + (q_minus ? 4.0 : 0.0)) * d);
     if (vec) probe_shift_kernel<true><<<lap_blocks(d, true), 256, 0, p->stream>>>(q, d, start, stop, key, eps, q_plus, q_minus);
@@ -206,7 +205,7 @@ int mcpm_hutchinson_accum_f64(mcpm_plan *p, const float *g_plus, const float *g_
     MCPM_REQUIRE(p, d >= 1 && g_plus && g_minus && diag && 0 <= start && start <= stop && stop <= d, MCPM_E_ARG,
                  "mcpm_hutchinson_accum_f64: bad argument");
     if (start == stop) return MCPM_OK;
-    const bool vec = aligned16(g_plus) && aligned16(g_minus) && aligned16(diag);
+    const bool vec = mcpm_aligned(g_plus) && mcpm_aligned(g_minus) && mcpm_aligned(diag);
     const uint64_t key = probe_key(seed, probe);
     StageTimer st_(p, ST_AXPY, 24.0 * (stop - start));
     if (vec) hutchinson_accum_kernel<true><<<lap_blocks(d, true), 256, 0, p->stream>>>(g_plus, g_minus, d, start, stop, key, coef, diag);

@@ -134,7 +134,6 @@ __global__ __launch_bounds__(256) void mclmc_moments_kernel(const float *__restr
     }
 }
 
-inline bool aligned16(const void *a) { return (reinterpret_cast<uintptr_t>(a) & 15u) == 0; }      // (NULL counts as aligned)
 inline unsigned mclmc_blocks(int64_t d, bool vec) {
     const int64_t work = vec ? std::max<int64_t>(d >> 2, 1) : d;
     return (unsigned)std::min<int64_t>((work + 255) / 256, MCLMC_MAX_BLOCKS);
@@ -148,7 +147,7 @@ int mcpm_mclmc_kick_drift_f32(mcpm_plan *p, float *u, float *q, const float *g, 
                               double eps_drift, double *stats) {
     if (!p) return MCPM_E_ARG;
     MCPM_REQUIRE(p, d >= 2 && u && g && stats, MCPM_E_ARG, "mcpm_mclmc_kick_drift_f32: bad argument");
-    const bool vec = aligned16(u) && aligned16(q) && aligned16(g) && aligned16(s);
+    const bool vec = mcpm_aligned(u) && mcpm_aligned(q) && mcpm_aligned(g) && mcpm_aligned(s);
     const unsigned nb = mclmc_blocks(d, vec);
     DetSum sum;
     StageTimer st_(p, ST_AXPY, ((s ? 24.0 : 20.0) + (q ? 8.0 : 0.0)) * d);
@@ -166,7 +165,7 @@ int mcpm_mclmc_kick_drift_f32(mcpm_plan *p, float *u, float *q, const float *g, 
 int mcpm_mclmc_moments_f64(mcpm_plan *p, const float *q, int64_t d, double gamma, double w, double *xavg, double *x2avg) {
     if (!p) return MCPM_E_ARG;
     MCPM_REQUIRE(p, d >= 1 && q && xavg && x2avg, MCPM_E_ARG, "mcpm_mclmc_moments_f64: bad argument");
-    const bool vec = aligned16(q) && aligned16(xavg) && aligned16(x2avg);
+    const bool vec = mcpm_aligned(q) && mcpm_aligned(xavg) && mcpm_aligned(x2avg);
     StageTimer st_(p, ST_AXPY, 36.0 * d);
     if (vec) mclmc_moments_kernel<true><<<mclmc_blocks(d, true), 256, 0, p->stream>>>(q, d, gamma, w, xavg, x2avg);
     else mclmc_moments_kernel<false><<<mclmc_blocks(d, false), 256, 0, p->stream>>>(q, d, gamma, w, xavg, x2avg);

@@ -3,6 +3,8 @@
 #include <hip/hip_runtime.h>
 #include <rocfft/rocfft.h>
 
+#include <algorithm>
+#include <cmath>
 #include <cstdint>
 #include <cstdio>
 #include <map>
@@ -230,6 +232,59 @@ struct TabSum {
 };
 int mcpm_tab_begin(mcpm_plan *p, const char *who, int region, size_t ntot, int64_t nelem, TabSum *t);
 int mcpm_tab_finish(mcpm_plan *p, const TabSum &t, const int *kind_end, int nkinds, double *out);
+
+// One fold of workgroup partials (reduce.hip), for the binned statistics (spectrum.hip, binned.hip, bispectrum.hip): the producer kernel
+// leaves P[group][nblk][nout] in the caller's workspace, mcpm_fold_partials adds the workgroups up in a fixed order through Q[group]
+// [MCPM_FOLD_R][nout] (two launches on `s`) and leaves the sums where `o` says.  No plan, no ticket, any nout; the det fold above has a plan
+// and at most DET_MAXK values.
+constexpr int MCPM_FOLD_R = 32;      // first-level chunks of the fold
+struct FoldOut {
+    double *out;
+    int n_bins, rb, batch;      // n_bins 0: dense, out[g * nout + o].  Else nout = (2 + rb) * n_bins and out is [2 + batch][n_bins]: accumulators
+                                // 0, 1 of group 0 to rows 0, 1; accumulator 2 + r of group g to row 2 + g * rb + r where g * rb + r < batch
+};
+inline FoldOut fold_dense(double *out) { return FoldOut{out, 0, 0, 0}; }
+inline FoldOut fold_binned(double *out, int n_bins, int rb, int batch) { return FoldOut{out, n_bins, rb, batch}; }
+int mcpm_fold_partials(hipStream_t s, const double *P, int groups, unsigned nblk, int nout, double *Q, const FoldOut &o);
+
+// The layout of such a workspace: regions carved one after the other, each starting on a 256-byte boundary.
+inline size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
+struct Carve {
+    size_t bytes = 0;      // the running offset: the size of the workspace once every region is taken
+    size_t take(size_t n) {
+        const size_t off = bytes;
+        bytes += align256(n);
+        return off;
+    }
+};
+inline void mcpm_fold_carve(Carve &c, int groups, unsigned nblk, size_t nout, size_t *off_P, size_t *off_Q) {
+    *off_P = c.take((size_t)groups * nblk * nout * 8);
+    *off_Q = c.take((size_t)groups * MCPM_FOLD_R * nout * 8);
+}
+// Workgroups of a producer: enough to fill the chip, fewer when a group's partials (per_block doubles per workgroup) would pass `budget`
+// doubles, and never more than there are units of work.
+inline int64_t mcpm_fold_nblk(int64_t budget, int64_t per_block, int64_t units) {
+    return std::min(std::min<int64_t>(2048, std::max<int64_t>(64, budget / per_block)), units);
+}
+// Bins per tile (gridDim.z tiles) of a kernel that keeps one LDS histogram [n_acc][bt] per wave in lds_doubles doubles.
+inline void mcpm_hist_tiles(int n_bins, int lds_doubles, int waves, int n_acc, int *bt, int *tiles) {
+    *bt = std::min(n_bins, lds_doubles / (waves * n_acc));
+    *tiles = (n_bins + *bt - 1) / *bt;
+}
+
+// The small host checks of those entry points.
+inline int mcpm_check_edges(const char *who, const double *edges, int n_edges, bool strict) {
+    for (int i = 0; i < n_edges; ++i)
+        if (!std::isfinite(edges[i]) || (i > 0 && !(strict ? edges[i] > edges[i - 1] : edges[i] >= edges[i - 1])))
+            return mcpm_fail(nullptr, MCPM_E_ARG, std::string(who) + (strict ? ": edges must be finite and strictly increasing" : ": edges must be finite and non-decreasing"));
+    return MCPM_OK;
+}
+inline int mcpm_check_batch(const char *who, int batch) {      // gridDim.y / .z carry the batch
+    if (batch < 1 || batch > 65535) return mcpm_fail(nullptr, MCPM_E_ARG, std::string(who) + ": batch out of range");
+    return MCPM_OK;
+}
+inline bool mcpm_aligned(const void *p, uintptr_t a = 16) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }      // (NULL counts as aligned)
+
 void mcpm_slab_state_free(mcpm_plan *p);   // slab.hip
 #define MCPM_PITCH_MAX_SHIFT 17472      // floats: 64 KB + 4 KB + 256 B, the largest candidate shift between particle arrays
 static inline int64_t mcpm_pitch_max(const mcpm_plan *p) { return 3 * p->Np + MCPM_PITCH_MAX_SHIFT; }

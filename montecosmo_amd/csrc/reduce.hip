@@ -1,5 +1,11 @@
-// Second stages kept in one place: the fold of the deterministic f64 grid sums (first stage: reduce_dev.h) with its scratch and launcher, and the
-// host side of the order-independent integer table sums (device side: tables_dev.h) with its scale kernel.
+// Second stages kept in one place: the fold of the deterministic f64 grid sums (first stage: reduce_dev.h) with its scratch and launcher, the
+// fold of the binned statistics' workgroup partials (first stages: spectrum.hip, binned.hip, bispectrum.hip), and the host side of the
+// order-independent integer table sums (device side: tables_dev.h) with its scale kernel.
+//
+// The two folds.  mcpm_det_begin / mcpm_det_fold add up at most DET_MAXK values per call: scratch that grows with the plan, ONE launch whose
+// last workgroup (a ticket) finishes the sum, a scale and an accumulate flag on the way out.  mcpm_fold_partials adds up many outputs per
+// group (a histogram per batch row): no plan and no ticket, the caller's workspace holds P and Q, and two launches with one lane per output
+// walk the workgroups in increasing order, so an output is a fixed-order sum whatever the batch.
 #include <algorithm>
 
 #include "mcpm_internal.h"
@@ -90,6 +96,49 @@ int mcpm_det_begin(mcpm_plan *p, int K, unsigned nblk, DetSum *s) {
 int mcpm_det_fold(mcpm_plan *p, const DetSum &s, int K, double scale, const DetOuts &outs) {
     det_fold_kernel<<<det_R(s.nblk), 256, 0, p->stream>>>(s.P, s.nblk, K, det_Q(p), det_ticket(p), scale, outs);
     MCPM_LAUNCH_CHECK(p, "det_fold_kernel");      // on failure mcpm_fail marks the ticket stale
+    return MCPM_OK;
+}
+
+// ---- the fold of workgroup partials P[group][nblk][nout] (mcpm_internal.h: mcpm_fold_partials) -----------------------------------------
+// First level: Q[g][r][o] = sum over workgroups [r C, min((r + 1) C, nblk)) of P[g][i][o], C = ceil(nblk / MCPM_FOLD_R), from 0. in
+// increasing i (an empty chunk leaves +0.0).
+__global__ __launch_bounds__(256) void partial_fold_kernel(const double *__restrict__ P, unsigned nblk, int nout, double *__restrict__ Q) {
+    const int o = blockIdx.x * 256 + threadIdx.x, r = blockIdx.y, g = blockIdx.z;
+    if (o >= nout) return;
+    const unsigned C = (nblk + MCPM_FOLD_R - 1) / MCPM_FOLD_R, lo = r * C, hi = min(lo + C, nblk);
+    const double *Pg = P + (size_t)g * nblk * nout + o;
+    double t = 0.;
+    for (unsigned i = lo; i < hi; ++i) t += Pg[(size_t)i * nout];
+    Q[((size_t)g * MCPM_FOLD_R + r) * nout + o] = t;
+}
+
+// Second level: the sum over r of Q[g][r][o], from 0. in increasing r, written where `f` says (FoldOut).  In the binned form every group
+// holds the same bits in accumulators 0 and 1 (count and sum of values), and a short last group holds copies of the last row: both are dropped.
+__global__ __launch_bounds__(256) void partial_fold2_kernel(const double *__restrict__ Q, int nout, FoldOut f) {
+    const int o = blockIdx.x * 256 + threadIdx.x, g = blockIdx.y;
+    if (o >= nout) return;
+    const double *Qg = Q + (size_t)g * MCPM_FOLD_R * nout + o;
+    double t = 0.;
+    for (int r = 0; r < MCPM_FOLD_R; ++r) t += Qg[(size_t)r * nout];
+    if (f.n_bins == 0) {
+        f.out[(size_t)g * nout + o] = t;
+        return;
+    }
+    const int acc = o / f.n_bins, j = o - acc * f.n_bins;
+    if (acc < 2) {
+        if (g == 0) f.out[(size_t)acc * f.n_bins + j] = t;
+    } else {
+        const int row = g * f.rb + acc - 2;
+        if (row < f.batch) f.out[(size_t)(2 + row) * f.n_bins + j] = t;
+    }
+}
+
+int mcpm_fold_partials(hipStream_t s, const double *P, int groups, unsigned nblk, int nout, double *Q, const FoldOut &o) {
+    const unsigned nx = (unsigned)((nout + 255) / 256);
+    partial_fold_kernel<<<dim3(nx, MCPM_FOLD_R, groups), 256, 0, s>>>(P, nblk, nout, Q);
+    MCPM_LAUNCH_CHECK(nullptr, "partial_fold_kernel");
+    partial_fold2_kernel<<<dim3(nx, groups), 256, 0, s>>>(Q, nout, o);
+    MCPM_LAUNCH_CHECK(nullptr, "partial_fold2_kernel");
     return MCPM_OK;
 }
 

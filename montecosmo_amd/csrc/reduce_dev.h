@@ -46,6 +46,19 @@ __device__ __forceinline__ double wave_sum(double v) {
     return v;
 }
 
+// Epilogue of a histogram kernel of four waves (spectrum.hip, binned.hip), after its __syncthreads: the waves' LDS histograms
+// hist[4][n_acc][bt] (hsz = n_acc * bt), added in a fixed tree, become the workgroup's partials P[group][blk][acc][tile0 + j], j < nbt, for
+// mcpm_fold_partials (reduce.hip).
+__device__ __forceinline__ void hist4_partials(const double *hist, int hsz, int n_acc, int bt, int tile0, int nbt, double *P, int group,
+                                               unsigned nblk, unsigned blk, int n_bins) {
+    double *Pb = P + ((size_t)group * nblk + blk) * (size_t)n_acc * n_bins;
+    for (int i = threadIdx.x; i < n_acc * nbt; i += blockDim.x) {
+        const int acc = i / nbt, j = i - acc * nbt;
+        const int o = acc * bt + j;
+        Pb[(size_t)acc * n_bins + tile0 + j] = (hist[o] + hist[hsz + o]) + (hist[2 * hsz + o] + hist[3 * hsz + o]);
+    }
+}
+
 // DETERMINISTIC GRID SUMS (round 4).  Round 3 added every workgroup's float64 partial to one of NSLOT spread slots with atomicAdd: several
 // workgroups per slot, in arrival order, so the last bit of a scalar cotangent moved from call to call (4e-16 .. 7e-16 relative; invisible at
 // the float32 the samplers carry, visible to a float64 equality).  Now every workgroup WRITES its partials (fixed tree inside the

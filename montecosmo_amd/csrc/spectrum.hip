@@ -7,7 +7,7 @@
 // wave_sum, cut at segment heads) leaves every segment's sum in its last lane, and those lanes hold DISTINCT bins, so they add it to
 // the wave's own LDS histogram with a plain read-modify-write.  Rounds follow in program order, so every histogram cell is a
 // fixed-order sum.  At the end the four waves' histograms are added in a fixed tree and the workgroup writes its partials
-// P[b][blk][acc][bin]; spectrum_fold_kernel / spectrum_fold2_kernel add the workgroups up in a fixed order (two levels of R chunks).
+// P[b][blk][acc][bin] (reduce_dev.h: hist4_partials); mcpm_fold_partials (reduce.hip) adds the workgroups up in a fixed order.
 // The decomposition depends on the geometry, the number of accumulators and of edges only, never on the batch, so a batched row is
 // bitwise the single call.
 //
@@ -25,7 +25,6 @@ namespace {
 
 constexpr int SPEC_WAVES = 4;          // waves per workgroup, one LDS histogram each
 constexpr int SPEC_LDS_DOUBLES = 8192; // 64 KB per workgroup: SPEC_WAVES * n_acc * bins-per-tile <= this
-constexpr int SPEC_FOLD_R = 32;        // first-level chunks of the workgroup fold
 
 struct SpecArgs {
     const float2 *s0, *s1;  // [B][nx][ny][nzh]; s1 NULL: auto spectrum of s0 only
@@ -189,68 +188,36 @@ __global__ __launch_bounds__(64 * SPEC_WAVES) void spectrum_bins_kernel(SpecArgs
         }
     }
     __syncthreads();
-    double *Pb = a.P + ((size_t)b * a.nblk + blk) * (size_t)nacc * a.n_bins;
-    for (int i = threadIdx.x; i < nacc * nbt; i += blockDim.x) {
-        const int acc = i / nbt, j = i - acc * nbt;
-        const int o = acc * a.bt + j;
-        const double s = (hist[o] + hist[hsz + o]) + (hist[2 * hsz + o] + hist[3 * hsz + o]);
-        Pb[(size_t)acc * a.n_bins + t0 + j] = s;
-    }
-}
-
-// First level of the workgroup fold: Q[b][r][o] = sum over workgroups [r C, (r + 1) C) of P[b][blk][o], in order.
-__global__ __launch_bounds__(256) void spectrum_fold_kernel(const double *__restrict__ P, unsigned nblk, int nout, double *__restrict__ Q) {
-    const int o = blockIdx.x * 256 + threadIdx.x, r = blockIdx.y, b = blockIdx.z;
-    if (o >= nout) return;
-    const unsigned C = (nblk + SPEC_FOLD_R - 1) / SPEC_FOLD_R, lo = r * C, hi = min(lo + C, nblk);
-    const double *Pb = P + (size_t)b * nblk * nout + o;
-    double t = 0.;
-    for (unsigned i = lo; i < hi; ++i) t += Pb[(size_t)i * nout];
-    Q[((size_t)b * SPEC_FOLD_R + r) * nout + o] = t;
-}
-
-__global__ __launch_bounds__(256) void spectrum_fold2_kernel(const double *__restrict__ Q, int nout, double *__restrict__ out) {
-    const int o = blockIdx.x * 256 + threadIdx.x, b = blockIdx.y;
-    if (o >= nout) return;
-    const double *Qb = Q + (size_t)b * SPEC_FOLD_R * nout + o;
-    double t = 0.;
-    for (int r = 0; r < SPEC_FOLD_R; ++r) t += Qb[(size_t)r * nout];
-    out[(size_t)b * nout + o] = t;
+    hist4_partials(hist, hsz, nacc, a.bt, t0, nbt, a.P, b, a.nblk, blk, a.n_bins);
 }
 
 struct SpecLayout {
-    int n_acc, n_bins, bt, tiles, nlut, rows, rows_per_wave;
+    int n_acc, n_bins, bt, tiles, rows, rows_per_wave;
     unsigned nblk;
     size_t off_tab, off_lut, off_P, off_Q, bytes;
 };
-
-size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
 
 int spec_layout(int nx, int ny, int nz, int n_edges, int n_ells, int two, int batch, SpecLayout *L) {
     if (nx < 1 || ny < 1 || nz < 2 || (nz & 1)) return mcpm_fail(nullptr, MCPM_E_SHAPE, "mcpm_spectrum: bad mesh shape (nz must be even)");
     if (n_edges < 2 || n_edges > MCPM_SPECTRUM_MAX_EDGES)
         return mcpm_fail(nullptr, MCPM_E_ARG, "mcpm_spectrum: need 2 .. MCPM_SPECTRUM_MAX_EDGES edges");
     if (n_ells < 1 || n_ells > 9) return mcpm_fail(nullptr, MCPM_E_ARG, "mcpm_spectrum: 1 .. 9 multipoles");
-    if (batch < 1 || batch > 65535) return mcpm_fail(nullptr, MCPM_E_ARG, "mcpm_spectrum: batch out of range");
+    MCPM_TRY(mcpm_check_batch("mcpm_spectrum", batch));
     const int nzh = nz / 2 + 1;
     L->n_acc = 2 + n_ells * (two ? 4 : 1);
     L->n_bins = n_edges - 1;
-    L->bt = std::min(L->n_bins, SPEC_LDS_DOUBLES / (SPEC_WAVES * L->n_acc));
-    L->tiles = (L->n_bins + L->bt - 1) / L->bt;
-    L->nlut = kbin_nlut(n_edges);
+    mcpm_hist_tiles(L->n_bins, SPEC_LDS_DOUBLES, SPEC_WAVES, L->n_acc, &L->bt, &L->tiles);
     L->rows = nx * ny;
     const int64_t nout = (int64_t)L->n_acc * L->n_bins;
-    // workgroups: enough to fill the chip, fewer when the partials would pass 32 MB per spectrum
-    int64_t nblk = std::min<int64_t>(2048, std::max<int64_t>(64, ((int64_t)1 << 22) / nout));
-    nblk = std::min<int64_t>(nblk, (L->rows + SPEC_WAVES - 1) / SPEC_WAVES);
+    // workgroups: fewer when the partials would pass 32 MB per spectrum
+    const int64_t nblk = mcpm_fold_nblk((int64_t)1 << 22, nout, (L->rows + SPEC_WAVES - 1) / SPEC_WAVES);
     L->rows_per_wave = (int)((L->rows + nblk * SPEC_WAVES - 1) / (nblk * SPEC_WAVES));
     L->nblk = (unsigned)((L->rows + (int64_t)L->rows_per_wave * SPEC_WAVES - 1) / ((int64_t)L->rows_per_wave * SPEC_WAVES));
-    const size_t ntab = (size_t)(nx + ny + nzh) * 3 + n_edges;
-    L->off_tab = 0;
-    L->off_lut = align256(ntab * 8);
-    L->off_P = L->off_lut + align256((size_t)L->nlut * 4);
-    L->off_Q = L->off_P + align256((size_t)batch * L->nblk * nout * 8);
-    L->bytes = L->off_Q + align256((size_t)batch * SPEC_FOLD_R * nout * 8);
+    Carve c;
+    L->off_tab = c.take(((size_t)(nx + ny + nzh) * 3 + n_edges) * 8);
+    L->off_lut = c.take((size_t)kbin_nlut(n_edges) * 4);
+    mcpm_fold_carve(c, batch, L->nblk, (size_t)nout, &L->off_P, &L->off_Q);
+    L->bytes = c.bytes;
     return MCPM_OK;
 }
 
@@ -277,9 +244,7 @@ int mcpm_spectrum_bins_c64(void *stream, int nx, int ny, int nz, const float *sp
         return mcpm_fail(nullptr, MCPM_E_ARG, "mcpm_spectrum_bins_c64: null pointer");
     if (work_bytes < (int64_t)L.bytes) return mcpm_fail(nullptr, MCPM_E_ARG, "mcpm_spectrum_bins_c64: workspace too small");
     if (stride0 < 0 || stride1 < 0) return mcpm_fail(nullptr, MCPM_E_ARG, "mcpm_spectrum_bins_c64: negative stride");
-    for (int i = 0; i < n_edges; ++i)
-        if (!std::isfinite(edges[i]) || (i > 0 && !(edges[i] > edges[i - 1])))
-            return mcpm_fail(nullptr, MCPM_E_ARG, "mcpm_spectrum_bins_c64: edges must be finite and strictly increasing");
+    MCPM_TRY(mcpm_check_edges("mcpm_spectrum_bins_c64", edges, n_edges, true));
     int lmax = 0;
     for (int j = 0; j < n_ells; ++j) {
         if (ells[j] < 0 || ells[j] > 8) return mcpm_fail(nullptr, MCPM_E_ARG, "mcpm_spectrum_bins_c64: multipoles 0 .. 8");
@@ -310,12 +275,6 @@ int mcpm_spectrum_bins_c64(void *stream, int nx, int ny, int nz, const float *sp
     a.dc1 = deconv1 && two ? tab + 2 * nk : nullptr;
     a.dz0 = a.dc0 ? a.dc0 + nx + ny : nullptr;
     a.dz1 = a.dc1 ? a.dc1 + nx + ny : nullptr;
-    a.kb.edges = tab + 3 * nk;
-    a.kb.lut = (const int *)(ws + L.off_lut);
-    a.kb.nlut = L.nlut;
-    a.kb.lut_w = (edges[n_edges - 1] - edges[0]) / L.nlut;
-    a.kb.lut_inv = 1. / a.kb.lut_w;
-    a.kb.n_edges = n_edges;
     a.n_bins = L.n_bins;
     for (int i = 0; i < 3; ++i) a.los[i] = los[i];
     for (int j = 0; j < n_ells; ++j) a.ells |= (unsigned long long)ells[j] << (4 * j);
@@ -333,7 +292,7 @@ int mcpm_spectrum_bins_c64(void *stream, int nx, int ny, int nz, const float *sp
     a.nblk = L.nblk;
     a.P = (double *)(ws + L.off_P);
 
-    kbin_lut_kernel<<<(L.nlut + 255) / 256, 256, 0, s>>>(a.kb.edges, n_edges, a.kb.lut_w, L.nlut, (int *)(ws + L.off_lut));
+    a.kb = kbin_table(edges, n_edges, tab + 3 * nk, (int *)(ws + L.off_lut), s);
     MCPM_LAUNCH_CHECK(nullptr, "kbin_lut_kernel");
     const dim3 grid(L.nblk, batch, L.tiles);
     const size_t lds = (size_t)SPEC_WAVES * L.n_acc * L.bt * 8;
@@ -342,13 +301,7 @@ int mcpm_spectrum_bins_c64(void *stream, int nx, int ny, int nz, const float *sp
     else
         spectrum_bins_kernel<false><<<grid, 64 * SPEC_WAVES, lds, s>>>(a);
     MCPM_LAUNCH_CHECK(nullptr, "spectrum_bins_kernel");
-    const int nout = L.n_acc * L.n_bins;
-    double *Q = (double *)(ws + L.off_Q);
-    spectrum_fold_kernel<<<dim3((nout + 255) / 256, SPEC_FOLD_R, batch), 256, 0, s>>>(a.P, L.nblk, nout, Q);
-    MCPM_LAUNCH_CHECK(nullptr, "spectrum_fold_kernel");
-    spectrum_fold2_kernel<<<dim3((nout + 255) / 256, batch), 256, 0, s>>>(Q, nout, out);
-    MCPM_LAUNCH_CHECK(nullptr, "spectrum_fold2_kernel");
-    return MCPM_OK;
+    return mcpm_fold_partials(s, a.P, batch, L.nblk, L.n_acc * L.n_bins, (double *)(ws + L.off_Q), fold_dense(out));
 }
 
 }  // extern "C"

@@ -58,33 +58,45 @@ def _mesh_shape(t, real):
     return shape
 
 
+def _centred_edges(spec, lo, hi, check=None):
+    """n edges at the centres of n equal cells of [lo, hi): n = spec for an int, as many cells of width spec as fit (at least one) for a
+    float.  check(n), if given, may refuse the count before the edges are made."""
+    n = int(spec) if isinstance(spec, (int, np.integer)) else max(int((hi - lo) / float(spec)), 1)
+    if check is not None:
+        check(n)
+    d = (hi - lo) / n
+    edges = np.linspace(lo, hi, n, endpoint=False)
+    edges += d / 2
+    return edges
+
+
+def _valid_edges(edges, max_count, strict, min_count=0):
+    """The final checks of every list of edges -> float64 [n]: at most max_count of them (and, for a caller that cannot do with fewer, at
+    least min_count), finite, strictly increasing (`strict`) or non-decreasing."""
+    edges = np.asarray(edges, dtype=np.float64).reshape(-1)
+    if min_count and not min_count <= len(edges) <= max_count:
+        raise ValueError(f"{min_count - 1} .. {max_count - 1} bins ({min_count} .. {max_count} edges), got {len(edges)} edges")
+    if len(edges) > max_count:
+        raise ValueError(f"at most {max_count} bin edges, got {len(edges)}")
+    steps = np.diff(edges)
+    if not np.all(np.isfinite(edges)) or not np.all(steps > 0 if strict else steps >= 0):
+        raise ValueError("bin edges must be finite and " + ("strictly increasing" if strict else "non-decreasing"))
+    return edges
+
+
 def _kedges(mesh_shape, box_size, kedges=None, include_corners=True):
     """Bin edges of montecosmo/metrics.py:_waves (:60-110): None, an int (number of edges), a float (dk) or a list."""
     mesh_shape = np.asarray(mesh_shape)
     box_size = np.asarray(box_size, dtype=np.float64)
     if isinstance(kedges, (type(None), int, float)):
-        dim = len(mesh_shape)
-        kmin = 0.
         kmax = np.pi * (mesh_shape / box_size).min()
         if include_corners:      # the largest |k| of the half-spectrum: every axis at its largest |k_i|, summed as _waves does
             kvec = nbody.rfftk(tuple(mesh_shape), box_size)
             kmax = np.sqrt(sum(np.max(ki ** 2) for ki in kvec))
         if kedges is None:
-            dk = dim ** .5 * 2 * np.pi / box_size.min()
-            n_kedges = max(int((kmax - kmin) / dk), 1)
-        elif isinstance(kedges, int):
-            n_kedges = kedges
-        else:
-            n_kedges = max(int((kmax - kmin) / kedges), 1)
-        dk = (kmax - kmin) / n_kedges
-        kedges = np.linspace(kmin, kmax, n_kedges, endpoint=False)
-        kedges += dk / 2
-    kedges = np.asarray(kedges, dtype=np.float64).reshape(-1)
-    if len(kedges) > MAX_EDGES:
-        raise ValueError(f"at most {MAX_EDGES} bin edges, got {len(kedges)}")
-    if not np.all(np.isfinite(kedges)) or not np.all(np.diff(kedges) > 0):
-        raise ValueError("bin edges must be finite and strictly increasing")
-    return kedges
+            kedges = len(mesh_shape) ** .5 * 2 * np.pi / box_size.min()
+        kedges = _centred_edges(kedges, 0., kmax)
+    return _valid_edges(kedges, MAX_EDGES, True)
 
 
 def _ktable(mesh_shape, box_size):
@@ -133,6 +145,26 @@ def _f64p(a):
     return None if a is None else a.ctypes.data_as(C.POINTER(C.c_double))
 
 
+def _batch_chunks(dev, batch, row_bytes, res_shape, ws_fn, *ws_args):
+    """The batch in chunks of bounded memory: yields (lo, hi, work, work_bytes, res) with rows lo .. hi-1 of the batch, the workspace
+    `ws_fn(*ws_args, hi - lo)` asks for and a float64 result of shape res_shape(hi - lo), both fresh on the device.  A row takes row_bytes
+    besides its workspace; a chunk stays under CHUNK_BYTES (or is one row).  The one-row query is made at once, the rest as the loop runs."""
+    def ws_bytes(b):
+        ws = C.c_int64()
+        _lib.call(ws_fn, *ws_args, b, C.byref(ws))
+        return ws.value
+
+    chunk = int(max(1, min(batch, CHUNK_BYTES // (ws_bytes(1) + row_bytes))))
+
+    def chunks():
+        for lo in range(0, batch, chunk):
+            hi = min(lo + chunk, batch)
+            ws = ws_bytes(hi - lo)
+            yield (lo, hi, torch.empty(ws, dtype=torch.uint8, device=dev), ws,
+                   torch.empty(res_shape(hi - lo), dtype=torch.float64, device=dev))
+    return chunks()
+
+
 def _bin_sums(mesh0, mesh1, box_size, box_center, ells, kedges, include_corners, deconv):
     """Raw bin sums: (kedges, B or None, sums [B, n_acc, n_bins], mesh_shape, box_size); see include/mcpm.h for n_acc."""
     t0, real0, bat0, shape = _prepare(mesh0)
@@ -165,26 +197,19 @@ def _bin_sums(mesh0, mesh1, box_size, box_center, ells, kedges, include_corners,
     out = np.zeros((batch, n_acc, max(n_bins, 0)), dtype=np.float64)
     if n_bins < 1:      # fewer than two edges: no bin, as in the reference
         return edges, batched, out, np.asarray(shape), box_size, ell_list, two
-    ws1 = C.c_int64()
-    _lib.call("mcpm_spectrum_workspace", nx, ny, nz, len(edges), n_ells, int(two), 1, C.byref(ws1))
     mh = nx * ny * (nz // 2 + 1)
-    per_row = ws1.value + (16 * mh if two else 8 * mh) + 8 * nx * ny * nz
-    chunk = int(max(1, min(batch, CHUNK_BYTES // per_row)))
+    chunks = _batch_chunks(dev, batch, (16 * mh if two else 8 * mh) + 8 * nx * ny * nz, lambda b: (b, n_acc, n_bins),
+                           "mcpm_spectrum_workspace", nx, ny, nz, len(edges), n_ells, int(two))
     ells_c = (C.c_int * n_ells)(*ell_list)
     los_c = np.ascontiguousarray(los, dtype=np.float64)
     stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
     s0_fixed = None if bat0 else _to_spec(t0, real0, shape, dev)
     s1_fixed = None if (not two or bat1) else _to_spec(t1, real1, shape, dev)
-    for lo in range(0, batch, chunk):
-        hi = min(lo + chunk, batch)
+    for lo, hi, work, ws, res in chunks:
         s0 = _to_spec(t0[lo:hi], real0, shape, dev) if bat0 else s0_fixed
         s1 = (_to_spec(t1[lo:hi], real1, shape, dev) if bat1 else s1_fixed) if two else None
-        ws = C.c_int64()
-        _lib.call("mcpm_spectrum_workspace", nx, ny, nz, len(edges), n_ells, int(two), hi - lo, C.byref(ws))
-        work = torch.empty(ws.value, dtype=torch.uint8, device=dev)
-        res = torch.empty((hi - lo, n_acc, n_bins), dtype=torch.float64, device=dev)
         _lib.call("mcpm_spectrum_bins_c64", stream, nx, ny, nz, s0, mh if bat0 else 0, s1, mh if bat1 else 0, hi - lo, ktab, dc0, dc1, edges,
-                  len(edges), los_c, ells_c, n_ells, work, ws.value, res)
+                  len(edges), los_c, ells_c, n_ells, work, ws, res)
         out[lo:hi] = res.cpu().numpy()
     return edges, batched, out, np.asarray(shape), box_size, ell_list, two
 
@@ -263,25 +288,13 @@ def _bispec_edges(mesh_shape, box_size, kedges=None):
     if isinstance(kedges, (bool, np.bool_)):
         raise ValueError("edges must be None, an int, a float or a list")
     if isinstance(kedges, (type(None), int, float, np.integer, np.floating)):
-        kmin = 0.
+        def check(n):
+            if not 2 <= n <= MAX_BISPEC_BINS + 1:
+                raise ValueError(f"1 .. {MAX_BISPEC_BINS} bins (2 .. {MAX_BISPEC_BINS + 1} edges), got {n} edges: pass kedges")
+
         kmax = 2. / 3. * np.pi * (mesh_shape / box_size).min()
-        if kedges is None:
-            n_kedges = max(int((kmax - kmin) / (3 * 2 * np.pi / box_size.min())), 1)
-        elif isinstance(kedges, (int, np.integer)):
-            n_kedges = int(kedges)
-        else:
-            n_kedges = max(int((kmax - kmin) / float(kedges)), 1)
-        if not 2 <= n_kedges <= MAX_BISPEC_BINS + 1:
-            raise ValueError(f"1 .. {MAX_BISPEC_BINS} bins (2 .. {MAX_BISPEC_BINS + 1} edges), got {n_kedges} edges: pass kedges")
-        dk = (kmax - kmin) / n_kedges
-        kedges = np.linspace(kmin, kmax, n_kedges, endpoint=False)
-        kedges += dk / 2
-    kedges = np.asarray(kedges, dtype=np.float64).reshape(-1)
-    if not 2 <= len(kedges) <= MAX_BISPEC_BINS + 1:
-        raise ValueError(f"1 .. {MAX_BISPEC_BINS} bins (2 .. {MAX_BISPEC_BINS + 1} edges), got {len(kedges)} edges")
-    if not np.all(np.isfinite(kedges)) or not np.all(np.diff(kedges) > 0):
-        raise ValueError("bin edges must be finite and strictly increasing")
-    return kedges
+        kedges = _centred_edges(3 * 2 * np.pi / box_size.min() if kedges is None else kedges, 0., kmax, check)
+    return _valid_edges(kedges, MAX_BISPEC_BINS + 1, True, min_count=2)
 
 
 def _bispec_triangles(edges, triangles=None):
@@ -348,21 +361,14 @@ def _triple_sums(t, real, shape, ktab, dc, edges, tri_sorted):
     nx, ny, nz = shape
     n_bins, n_tri, m, mh = len(edges) - 1, len(tri_sorted), nx * ny * nz, nx * ny * (nz // 2 + 1)
     batch = 1 if t is None else int(t.shape[0])
-    ws1 = C.c_int64()
-    _lib.call("mcpm_bispectrum_workspace", nx, ny, nz, n_bins, n_tri, 1, C.byref(ws1))
-    per_row = ws1.value + (n_bins + 1) * (8 * mh + 4 * m)
-    chunk = int(max(1, min(batch, CHUNK_BYTES // per_row)))
+    chunks = _batch_chunks(dev, batch, (n_bins + 1) * (8 * mh + 4 * m), lambda b: (b, n_tri),
+                           "mcpm_bispectrum_workspace", nx, ny, nz, n_bins, n_tri)
     tri_dev = torch.from_numpy(np.ascontiguousarray(tri_sorted, dtype=np.int32)).to(dev)
     stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
     out = np.zeros((batch, n_tri), dtype=np.float64)
-    for lo in range(0, batch, chunk):
-        hi = min(lo + chunk, batch)
+    for lo, hi, work, ws, res in chunks:
         fields = _shell_fields(None if t is None else t[lo:hi], real, shape, dev, ktab, dc, edges)
-        ws = C.c_int64()
-        _lib.call("mcpm_bispectrum_workspace", nx, ny, nz, n_bins, n_tri, hi - lo, C.byref(ws))
-        work = torch.empty(ws.value, dtype=torch.uint8, device=dev)
-        res = torch.empty((hi - lo, n_tri), dtype=torch.float64, device=dev)
-        _lib.call("mcpm_bispectrum_sums_f32", stream, fields, m, n_bins, hi - lo, tri_dev, n_tri, work, ws.value, res)
+        _lib.call("mcpm_bispectrum_sums_f32", stream, fields, m, n_bins, hi - lo, tri_dev, n_tri, work, ws, res)
         out[lo:hi] = res.cpu().numpy()
     return out
 
@@ -421,12 +427,7 @@ def bispectrum(mesh, box_size=None, kedges: int | float | list = None, triangles
 # ------------------------------------------------------------------------------------------------
 # real-space bins (montecosmo/metrics.py:214-313, :545-553): host side
 def _check_edges(edges):
-    edges = np.asarray(edges, dtype=np.float64).reshape(-1)
-    if len(edges) > MAX_EDGES:
-        raise ValueError(f"at most {MAX_EDGES} bin edges, got {len(edges)}")
-    if not np.all(np.isfinite(edges)) or not np.all(np.diff(edges) >= 0):
-        raise ValueError("bin edges must be finite and non-decreasing")
-    return edges
+    return _valid_edges(edges, MAX_EDGES, False)
 
 
 def _quantiles(values, q):
@@ -468,12 +469,12 @@ def _vedges(values, vedges, min_count=1, cell_length=None):
             vmin, vmax = 0., 1.
         else:
             vmin, vmax = float(values.min()), float(values.max())
-        n = int(vedges) if is_int else max(int((vmax - vmin) / float(vedges)), 1)
-        if n > MAX_EDGES:
-            raise ValueError(f"at most {MAX_EDGES} bin edges, got {n}")
-        dv = (vmax - vmin) / n
-        vedges = np.linspace(vmin, vmax, n, endpoint=False)
-        vedges += dv / 2
+
+        def check(n):
+            if n > MAX_EDGES:
+                raise ValueError(f"at most {MAX_EDGES} bin edges, got {n}")
+
+        vedges = _centred_edges(vedges, vmin, vmax, check)
     vedges = np.asarray(vedges, dtype=np.float64).reshape(-1)
     if min_count is None:
         if len(vedges) > MAX_EDGES:
@@ -570,22 +571,15 @@ def _binned(values, t0, t1, scale, vedges, min_count, aggr_fn=None, mask=None, c
     f32 = lambda x, rows: x.detach().to(device=dev, dtype=torch.float32).reshape(rows, n).contiguous()
     bat = a0 if a1 is None else a1      # the input that may carry the batch axis
     fixed0 = f32(a0, 1) if (a1 is not None or batch is None) else None
-    ws1 = C.c_int64()
-    _lib.call("mcpm_binned_workspace", n, len(edges), 1, C.byref(ws1))
-    chunk = int(max(1, min(B, CHUNK_BYTES // (ws1.value + 4 * n))))
+    chunks = _batch_chunks(dev, B, 4 * n, lambda b: (2 + b, n_bins), "mcpm_binned_workspace", n, len(edges))
     stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
     out_t = np.zeros((B, n_bins), dtype=np.float64)
-    for lo in range(0, B, chunk):
-        hi = min(lo + chunk, B)
+    for lo, hi, work, ws, res in chunks:
         rows = f32(bat[lo:hi] if batch is not None else bat, hi - lo) if (a1 is not None or batch is not None) else None
         d0, s0 = (fixed0, 0) if fixed0 is not None else (rows, n)
         d1, s1 = (rows, n if batch is not None else 0) if a1 is not None else (None, 0)
-        ws = C.c_int64()
-        _lib.call("mcpm_binned_workspace", n, len(edges), hi - lo, C.byref(ws))
-        work = torch.empty(ws.value, dtype=torch.uint8, device=dev)
-        res = torch.empty((2 + hi - lo, n_bins), dtype=torch.float64, device=dev)
         _lib.call("mcpm_binned_sums_f32", stream, n, vd, int(vd.dtype == torch.float64), d0, s0, d1, s1, float(scale), md, hi - lo, edges,
-                  len(edges), work, ws.value, res)
+                  len(edges), work, ws, res)
         res = res.cpu().numpy()
         vcount, vsum = res[0], res[1]      # the same bits from every chunk
         out_t[lo:hi] = res[2:]

@@ -76,6 +76,35 @@ def test_flat_sizes_aligned_and_misaligned(gpu, n, vdtype):
     _bitwise(mixed, out[False][1])
 
 
+# ---- workgroup counts that are no multiple of the fold's 32 first-level chunks ---------------------------------------------------------
+# bin_layout (csrc/binned.hip) with 6 edges: nblk = min(2048, ceil(n / 1024)), cells_per_wave = 256, so n = 33 * 1024 gives 33 workgroups
+# and n = 41 * 1024 + 5 gives 42, the last one with 5 cells.  The fold (csrc/reduce.hip) then has C = ceil(nblk / 32) = 2 workgroups per
+# chunk: 33 leaves chunk 16 with one workgroup and chunks 17 .. 31 empty, 42 leaves chunks 21 .. 31 empty.  Batch 5 is two groups of
+# rb = 4 rows, the last one short.
+@pytest.mark.parametrize("n", [33 * 1024, 41 * 1024 + 5])
+def test_fold_of_ragged_workgroup_counts(gpu, n):
+    from montecosmo_amd import metrics
+    rng = np.random.default_rng(n)
+    v = rng.uniform(0., 10., n).astype(np.float32)
+    t0, t1 = rng.standard_normal(n).astype(np.float32), rng.standard_normal((5, n)).astype(np.float32)
+    edges = [1., 2.5, 2.5, 4., 7., 9.]
+    cell = 1.5
+    vabs = _vabs(v, edges)
+    dv, d0, d1 = _dev(v, gpu), _dev(t0, gpu), _dev(t1, gpu)
+    modes = {"plain": (lambda x: metrics.bin_and_aggregate(x, dv, edges), lambda x: ref.bin_and_aggregate(x, v, edges)),
+             "squared": (lambda x: metrics.mse_radius(d0, x, dv, cell, redges=edges), lambda x: ref.mse_radius(t0, x, v, cell, redges=edges))}
+    for name, (f, f_ref) in modes.items():
+        full = f(d1)                                   # batch 5
+        _check(full, f_ref(t1), vabs)
+        assert full[2].shape == (5, len(full[0]))
+        for b in range(5):                             # batch 1
+            one = f(d1[b])
+            if b == 0:
+                _check(one, f_ref(t1[0]), vabs)
+            _bitwise(one[:2], full[:2])
+            np.testing.assert_array_equal(one[2], full[2][b])
+
+
 # ---- 3-D meshes binned by radius, whole and through a mask ------------------------------------------------------------------------------
 def _bare_logdensity(fwd, mask, gpu):
     """A FieldLevelLogDensity with only what the diagnostics read (the geometry and the mask): its constructor sets a sampler up and

@@ -125,6 +125,29 @@ def test_bitwise_repeat_and_batch(gpu):
         assert np.array_equal(a[2], b, equal_nan=True)
 
 
+# spec_layout (csrc/spectrum.hip) gives the mesh (10, 15, 8) 150 rows of the half-spectrum, one per wave, so ceil(150 / 4) = 38 workgroups:
+# no multiple of the fold's 32 first-level chunks (csrc/reduce.hip).  C = ceil(38 / 32) = 2 workgroups per chunk, chunks 19 .. 31 empty.
+@pytest.mark.parametrize("cross", [False, True])
+def test_fold_of_ragged_workgroup_count(gpu, cross):
+    from montecosmo_amd import metrics
+    shape, box = (10, 15, 8), (100., 150., 80.)
+    kw = dict(box_size=box, box_center=(300., -800., 2000.), ells=[0, 2])
+    s = np.stack([_white_spec(shape, 20 + i) for i in range(4)])
+    assert s.shape == (4, 10, 15, 5)
+    d = torch.from_numpy(s).to(gpu)
+    # auto: the batch on mesh0; cross: one mesh0 against a batch of mesh1
+    a, a_dev, b, b_dev = (s[1:], d[1:], None, None) if not cross else (s[0], d[0], s[1:], d[1:])
+    row = lambda x, i: x[i] if x is not None and x.ndim == 4 else x
+    c128 = lambda x: None if x is None else x.astype(np.complex128)
+    got = metrics._spectrum(row(a_dev, 0), row(b_dev, 0), **kw)
+    _check(got, ref.spectrum(c128(row(a, 0)), c128(row(b, 0)), mesh_shape=shape, **kw))
+    args = (box, kw["box_center"], kw["ells"], None, True, (0, 0))
+    batched = metrics._bin_sums(a_dev, b_dev, *args)[2]
+    assert batched.shape[0] == 3
+    for i in range(3):
+        assert np.array_equal(batched[i], metrics._bin_sums(row(a_dev, i), row(b_dev, i), *args)[2][0])
+
+
 def test_many_workgroups_256(gpu):
     from montecosmo_amd import metrics
     shape, box = (256, 256, 256), (1000., 1000., 1000.)
